@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: training images/sec of the PacingPseudo step (256x256, 5 classes) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -16,6 +16,8 @@ step the reference uses from epoch 1 on (train_chaos.py:370).
 Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events around every launch of the dominant
 matrix-core kernel families during the timed steps; `cpu_baseline` times the CPU oracle
 (the reference path restated on PyTorch-CPU) on this box's host cores on a bounded sample.
+`--dump-outputs DIR` writes what the last timed step computed (inputs and weights are seeded: two builds of the project can
+be compared array for array) as DIR/<name>.npy, float32, at most 64 MB in all.
 """
 import argparse
 import json
@@ -55,7 +57,54 @@ def parse():
     ap.add_argument('--sync-bn', action='store_true',
                     help='N > 1: train-mode BatchNorm statistics over the GLOBAL batch (one packed all-reduce per BN call, as the '
                          "reference's single-process batch would see them); default: per-rank statistics (stated in the JSON line)")
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the LAST timed step computed (rank 0) as DIR/<name>.npy, float32: the '
+                         "model's outputs, the assembled loss, and the parameters / gradients / BatchNorm and memory buffers after its "
+                         f'update; an array of more than {DUMP_SAMPLE} elements is reduced to a fixed, seeded sample of that many')
+    cli = ap.parse_args()
+    if cli.steps < 1:
+        ap.error('--steps must be at least 1')
+    return cli
+
+
+DUMP_SAMPLE = 1 << 21              # elements kept of a larger array (8 MB of float32)
+DUMP_LIMIT = 64 << 20              # bytes written by --dump-outputs in all
+
+
+def step_arrays(model, out, loss):
+    """What one training step hands its caller, by name: the model's output dict, the assembled loss, and the state the
+    update leaves behind (every parameter and its gradient, the floating-point buffers), each concatenated in module order."""
+    import torch
+    arrays = {k.replace('/', '_'): v for k, v in out.items()}
+    arrays['loss'] = loss
+    params = [p for p in model.parameters() if p.requires_grad]
+    arrays['parameters'] = torch.cat([p.detach().reshape(-1) for p in params])
+    arrays['gradients'] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                     for p in params])
+    arrays['buffers'] = torch.cat([b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()])
+    return arrays
+
+
+def dump_outputs(path, arrays):
+    """Write every array as <path>/<name>.npy (float64 stays float64, anything else becomes float32).  An array of more than
+    DUMP_SAMPLE elements is flattened and reduced to DUMP_SAMPLE elements at positions drawn by torch.randperm from a generator
+    seeded 0: the same positions for the same size in every run.  Returns the bytes written (at most DUMP_LIMIT)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise RuntimeError(f'--dump-outputs: more than {DUMP_LIMIT} bytes at {name!r}')
+        np.save(os.path.join(path, name + '.npy'), a)
+    return total
 
 
 def build(args_model, device):
@@ -90,13 +139,16 @@ def assemble_loss(out, a, epoch):
     return weighted_loss_sum(terms, weights)        # as pacingpseudo_amd/train.py assembles it: one launch each way
 
 
-def train_iteration(model, opt, batch, a, epoch):
-    """train_chaos.py:272-315 (meters kept on the device: no per-loss .item() host sync)."""
+def train_iteration(model, opt, batch, a, epoch, keep=None):
+    """train_chaos.py:272-315 (meters kept on the device: no per-loss .item() host sync).  `keep`: a dict that receives the
+    model's output dict as 'out'."""
     out = model(batch, mode='train', step=epoch)
     loss = assemble_loss(out, a, epoch)
     opt.zero_grad()
     loss.backward()
     opt.step()
+    if keep is not None:
+        keep['out'] = out
     return loss
 
 
@@ -324,10 +376,11 @@ def main():
         lib.pp_prof_select(timed_mask)
         lib.pp_prof_enable(1)
         prof_collect()
+    last_out = {}                                  # the output dict of the last timed step (--dump-outputs)
     t0 = time.perf_counter()
     step_ev[0].record()
     for i in range(cli.steps):
-        loss = train_iteration(model, opt, batch, a, ep_main)
+        loss = train_iteration(model, opt, batch, a, ep_main, keep=last_out if i == cli.steps - 1 else None)
         step_ev[i + 1].record()
         host_t[i] = time.perf_counter()
     sync()
@@ -346,6 +399,12 @@ def main():
     host_stats = dict(enqueue_ms=_dist(enq_ms), lead_ms_min=round(min(lead_ms), 3), lead_ms_median=_dist(lead_ms)['median'],
                       what='enqueue_ms: host wall time to enqueue one step; lead_ms: GPU completion of step i minus the host clock '
                            'when its enqueue finished (<= 0 would mean the GPU waited for the host)')
+    dumped = None
+    if cli.dump_outputs and rank == 0:             # before any later step overwrites the last timed step's results
+        arrays = step_arrays(model, last_out['out'], loss)
+        dumped = dict(dir=cli.dump_outputs, files=sorted(arrays), bytes=dump_outputs(cli.dump_outputs, arrays))
+        del arrays
+    last_out.clear()
     lib.pp_prof_select((1 << 64) - 1)
     lib.pp_prof_enable(1)
     for _ in range(2):
@@ -727,6 +786,8 @@ def main():
             'input_pipeline_images_per_sec': round(aug_rate, 1) if aug_rate else None,
             'final_loss': round(final_loss, 6),
         }
+        if dumped:
+            line['dump_outputs'] = dumped
         if world == 1 and not cli.no_cpu_baseline:
             try:
                 line['cpu_baseline'] = cpu_baseline(a, cli.cpu_batch, S, cli.cpu_steps)

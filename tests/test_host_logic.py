@@ -318,6 +318,37 @@ def test_bench_refuses_more_gpus_than_visible():
     assert 'visible' in r.stderr and '{' not in r.stdout
 
 
+def test_bench_refuses_zero_steps():
+    """--steps is the number of timed steps and `ms_per_step` divides by it: 0 is a usage error before any device is touched."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], cwd=ROOT, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and '--steps' in r.stderr and '{' not in r.stdout
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: one float32 (float64 kept) .npy per array; an array larger than DUMP_SAMPLE is cut to DUMP_SAMPLE
+    elements at the same seeded positions in every run; more than DUMP_LIMIT bytes in all is refused."""
+    import bench
+    big = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float32)         # value = position (exact in float32)
+    arrays = {'big': big, 'small': torch.arange(6, dtype=torch.int64).reshape(2, 3), 'exact': torch.tensor([1.5], dtype=torch.float64),
+              'half': torch.ones(4, dtype=torch.bfloat16)}
+    n = bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    bench.dump_outputs(str(tmp_path / 'b'), {'big': big.clone()})
+    a = {k: np.load(tmp_path / 'a' / f'{k}.npy') for k in arrays}
+    assert a['big'].dtype == np.float32 and a['big'].shape == (bench.DUMP_SAMPLE,)
+    assert np.array_equal(a['big'], np.load(tmp_path / 'b' / 'big.npy'))
+    pos = a['big'].astype(np.int64)                                                # distinct positions, in order
+    assert (np.diff(pos) > 0).all() and pos[0] >= 0 and pos[-1] < big.numel() and pos[-1] - pos[0] > bench.DUMP_SAMPLE // 2
+    assert a['small'].dtype == np.float32 and a['small'].shape == (2, 3) and a['small'][1, 2] == 5
+    assert a['exact'].dtype == np.float64 and a['half'].dtype == np.float32
+    assert n == sum(v.nbytes for v in a.values()) <= bench.DUMP_LIMIT
+    many = {f'x{i}': big for i in range(bench.DUMP_LIMIT // (4 * bench.DUMP_SAMPLE) + 1)}
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / 'c'), many)
+
+
 def test_switch_surface():
     """DESIGN.md section 10 lists every PP_* environment variable the sources read -- no more (the
     surface was ~60, many selecting kernels that measurement had rejected), no fewer."""

@@ -47,7 +47,7 @@ typedef struct pp_lazy_in {
 } pp_lazy_in;
 
 /* ---- runtime ------------------------------------------------------------------------------------------ */
-/* 100 * round + revision; bumped whenever an entry point is removed or changes its arguments (600: round 6).  The Python
+/* 100 * round + revision; bumped whenever an entry point is removed or changes its arguments (600: round 6; 601: GroupNorm entry points).  The Python
  * binding refuses a library older than the header it was written against (pacingpseudo_amd/_lib.py: MIN_LIB_VERSION). */
 int pp_version(void);
 const char* pp_last_error(void);
@@ -311,6 +311,30 @@ int pp_bn_lrelu_bwd_eval_pool(const float* dy, int ld_dy, const float* dpool, in
                               const float* scale, const float* gamma, const float* beta, float* dz, int ld_dz, float* dgamma,
                               float* dbeta, float* dbias_conv, int accumulate_param_grads, int C, int B, int H, int W,
                               float slope, void* workspace, size_t workspace_bytes, float* dz_amax, void* stream);
+
+/* ---- GroupNorm + LeakyReLU (--norm_op group; the reference's ConvLayer with norm_op = nn.GroupNorm, models/unet.py:178-193) ----
+ * nn.GroupNorm(G, C, eps, affine) -> nn.LeakyReLU(slope) on N images of H*W pixels (HW = H*W), NHWC fp32 with row stride ld >= C.
+ * Statistics are per (image, channel group) in train and eval mode alike.  pp_gn_stats writes per-(image, channel) rows [N][C]:
+ * save_mean / save_invstd (the group's statistics, repeated for each channel of the group), save_xbar (mean over the image of
+ * xhat in that channel: the backward's conv-bias term), scale = gamma * invstd, shift = beta - mean * scale.  The forward apply
+ * is pp_bn_lrelu_fwd / pp_bn_lrelu_fwd_pool with P_per_group = HW and groups = N (one coefficient row per image).
+ * pp_gn_lrelu_bwd: dz, dgamma, dbeta and the conv-bias gradient (sum of dz), each (accumulate_param_grads) added to or stored;
+ * dz_amax nullable (max |dz|).  pp_gn_lrelu_bwd_pool: the same when the layer output also feeds a 2x2 max-pooling whose
+ * gradient dpool (N, H/2, W/2) is added to each window's winner.  All three share one workspace of pp_gn_workspace bytes.
+ * Deterministic (fixed-order reductions), C % 4 == 0, C <= 1024, G divides C.  fp32 storage only. */
+size_t pp_gn_workspace(int C, int HW, int N);
+int pp_gn_stats(const float* z, int ld, int C, int HW, int N, int G, float eps, const float* gamma, const float* beta,
+                float* save_mean, float* save_invstd, float* save_xbar, float* scale, float* shift, void* workspace,
+                size_t workspace_bytes, void* stream);
+int pp_gn_lrelu_bwd(const float* dy, int ld_dy, const float* z, int ld_z, const float* scale, const float* shift,
+                    const float* save_mean, const float* save_invstd, const float* save_xbar, const float* gamma, float* dz,
+                    int ld_dz, float* dgamma, float* dbeta, float* dbias_conv, int accumulate_param_grads, int C, int HW, int N,
+                    int G, float slope, void* workspace, size_t workspace_bytes, float* dz_amax, void* stream);
+int pp_gn_lrelu_bwd_pool(const float* dy, int ld_dy, const float* dpool, int ld_dpool, const float* z, int ld_z,
+                         const float* scale, const float* shift, const float* save_mean, const float* save_invstd,
+                         const float* save_xbar, const float* gamma, float* dz, int ld_dz, float* dgamma, float* dbeta,
+                         float* dbias_conv, int accumulate_param_grads, int C, int N, int H, int W, int G, float slope,
+                         void* workspace, size_t workspace_bytes, float* dz_amax, void* stream);
 /* BatchNorm + LeakyReLU backward of the network's FIRST layer (models/unet.py:188-193 on `input_ch` = 1, every dataset of the
  * reference) with that layer's weight gradient folded in: nobody asks for the data gradient of the first convolution, so dz had
  * one reader -- the weight gradient, the last kernel of the backward pass.  The pass that forms dz multiplies it with the 3x3

@@ -99,6 +99,12 @@ _PROTOS = {
                                        i32, f32, vp, sz, vp]),
     'pp_bn_lrelu_bwd_eval_wgrad_c1': (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, f32,
                                             vp, sz, vp]),
+    'pp_gn_workspace': (sz, [i32, i32, i32]),
+    'pp_gn_stats': (i32, [vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'pp_gn_lrelu_bwd': (i32, [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, sz,
+                              vp, vp]),
+    'pp_gn_lrelu_bwd_pool': (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32,
+                                   i32, f32, vp, sz, vp, vp]),
     'pp_bn_lrelu_bwd_pool': (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32,
                                    f32, vp, sz, vp, vp]),
     'pp_bn_lrelu_bwd_eval_pool': (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp,
@@ -203,7 +209,7 @@ for _n in H16_ENTRIES:
 _H16_SET = frozenset(H16_ENTRIES) | {'pp_memory_update'}
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
-MIN_LIB_VERSION = 600      # include/pacingpseudo_hip.h of round 6 (pp_runtime.cpp: PP_VERSION)
+MIN_LIB_VERSION = 601      # include/pacingpseudo_hip.h with the GroupNorm entry points (pp_runtime.cpp: PP_VERSION)
 PROF_KINDS = ('conv_igemm', 'conv_wgrad', 'bn', 'spatial', 'loss', 'optim', 'misc', 'wino_gemm', 'wino_wgrad',
               'wino_xform', 'conv_f16x3', 'wino_gemm_f16x3', 'wino_wgrad_f16x3', 'conv_wgrad_f16x3', 'conv_halo_f16x3')
 

@@ -1368,4 +1368,229 @@ extern "C" int PP_FN(pp_bn_lrelu_bwd_eval_wgrad_c1)(const pp_act* dy, int ld_dy,
   pp_prof_end(s);
   return pp_launch_status("bn_lrelu_bwd_eval_wgrad_c1");
 }
+#ifndef PP_ACT_16      // GroupNorm (--norm_op group): fp32 storage only, one copy in the fp32 build
+// ---- GroupNorm2d (+ LeakyReLU) for NHWC fp32 activations ----
+// nn.GroupNorm(G, C, eps, affine) followed by nn.LeakyReLU(0.01) -- the reference's ConvLayer with norm_op = GroupNorm
+// (models/unet.py:178-193).  Statistics are taken per (image, channel group) over H*W*(C/G) elements, in train and eval mode
+// alike (no running state).  The work is phrased in the per-(group, channel) layout of the BatchNorm kernels above with one
+// statistics group per IMAGE: the per-channel passes (bn_stats_partial_kernel, bn_bwd_partial_kernel, bn_bwd_apply_kernel,
+// bn_bwd_pool_kernel, and pp_bn_lrelu_fwd[_pool] on the caller's side) run unchanged over (blocks, N), and only the finalize
+// steps, which fold the per-(image, channel) sums into per-(image, group) statistics, are GroupNorm's own.  The coefficient
+// rows are expanded per channel: save_mean / save_invstd [N][C] repeat the group's statistics for each of its channels,
+// scale = gamma * rstd and shift = beta - mean * scale, save_xbar [N][C] = mean over H*W of xhat for that channel (the
+// backward needs it for the conv-bias gradient, which does not vanish per channel under GroupNorm).  Every reduction is
+// fixed-order double accumulation (deterministic: no float atomics).
+#define GN_THREADS 256
+
+// fixed-order tree reduction of two doubles over the block; every thread returns the totals
+__device__ __forceinline__ void gn_block_sum2(double (*red)[GN_THREADS], double& a, double& b) {
+  const int tid = threadIdx.x;
+  red[0][tid] = a;
+  red[1][tid] = b;
+  __syncthreads();
+#pragma unroll
+  for (int o = GN_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
+    __syncthreads();
+  }
+  a = red[0][0];
+  b = red[1][0];
+}
+
+// one block per (group, image): partial[n][blk][2][C] (sum z, sum z^2) -> statistics of the group and its coefficient rows
+__global__ __launch_bounds__(GN_THREADS) void gn_stats_finalize_kernel(const double* __restrict__ partial, int nblk, int C, int G,
+                                                                     int HW, float eps, const float* __restrict__ gamma,
+                                                                     const float* __restrict__ beta, float* __restrict__ save_mean,
+                                                                     float* __restrict__ save_invstd, float* __restrict__ save_xbar,
+                                                                     float* __restrict__ scale, float* __restrict__ shift) {
+  __shared__ double red[2][GN_THREADS];
+  const int g = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+  const int cpg = C / G, c0 = g * cpg;
+  const double* pn = partial + (size_t)n * nblk * 2 * C;
+  double s = 0.0, q = 0.0;
+  for (int i = tid; i < nblk * cpg; i += GN_THREADS) {           // consecutive threads read consecutive channels of a row
+    const int blk = i / cpg, c = c0 + (i - blk * cpg);
+    s += pn[(size_t)blk * 2 * C + c];
+    q += pn[(size_t)blk * 2 * C + C + c];
+  }
+  gn_block_sum2(red, s, q);
+  const double m = (double)cpg * HW;
+  const double mean = s / m;
+  double var = q / m - mean * mean;
+  if (var < 0.0) var = 0.0;
+  const float meanf = (float)mean;
+  const float invstd = 1.0f / sqrtf((float)var + eps);           // the arithmetic of bn_stats_finalize_kernel
+  for (int cc = tid; cc < cpg; cc += GN_THREADS) {
+    const int c = c0 + cc;
+    double cs = 0.0;
+    for (int blk = 0; blk < nblk; ++blk) cs += pn[(size_t)blk * 2 * C + c];
+    const float sc = invstd * gamma[c];
+    const size_t o = (size_t)n * C + c;
+    save_mean[o] = meanf;
+    save_invstd[o] = invstd;
+    save_xbar[o] = (float)((cs / (double)HW - mean) * (double)invstd);
+    scale[o] = sc;
+    shift[o] = beta[c] - meanf * sc;
+  }
+}
+
+// one block per (group, image): partial[n][blk][2][C] (s1 = sum g, s2 = sum g xhat; g = lrelu' dy) -> per-(image, channel) sums
+// rows[n][0..1][C], the coefficients of dz = kA g + kB z + kC and the per-(image, channel) conv-bias gradient rows[n][2][C]:
+//   A1 = sum_{c in group} gamma_c s1_c, A2 = sum gamma_c s2_c, m = H*W*C/G,
+//   dz = rstd (gamma_c g - A1 / m - xhat A2 / m),   sum_p dz = rstd (gamma_c s1_c - HW A1 / m - HW xbar_c A2 / m).
+__global__ __launch_bounds__(GN_THREADS) void gn_bwd_finalize_kernel(const double* __restrict__ partial, int nblk, int C, int G, int HW,
+                                                                   const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                                   const float* __restrict__ invstd, const float* __restrict__ xbar,
+                                                                   float* __restrict__ kA, float* __restrict__ kB,
+                                                                   float* __restrict__ kC, double* __restrict__ rows,
+                                                                   float* __restrict__ amax) {
+  __shared__ double red[2][GN_THREADS];
+  const int g = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+  if (amax && g == 0 && n == 0 && tid == 0) *amax = 0.f;        // the apply pass accumulates max |dz| into it
+  const int cpg = C / G, c0 = g * cpg;
+  const double* pn = partial + (size_t)n * nblk * 2 * C;
+  double* rn = rows + (size_t)n * 3 * C;
+  double a1 = 0.0, a2 = 0.0;
+  for (int cc = tid; cc < cpg; cc += GN_THREADS) {
+    const int c = c0 + cc;
+    double s1 = 0.0, s2 = 0.0;
+    for (int blk = 0; blk < nblk; ++blk) {
+      s1 += pn[(size_t)blk * 2 * C + c];
+      s2 += pn[(size_t)blk * 2 * C + C + c];
+    }
+    rn[c] = s1;
+    rn[C + c] = s2;
+    a1 += (double)gamma[c] * s1;
+    a2 += (double)gamma[c] * s2;
+  }
+  gn_block_sum2(red, a1, a2);
+  const double m = (double)cpg * HW;
+  for (int cc = tid; cc < cpg; cc += GN_THREADS) {
+    const int c = c0 + cc;
+    const size_t o = (size_t)n * C + c;
+    const double r = (double)invstd[o];
+    const double A = (double)gamma[c] * r;
+    const double B = -r * r * a2 / m;
+    kA[o] = (float)A;
+    kB[o] = (float)B;
+    kC[o] = (float)(-r * a1 / m - B * (double)mean[o]);
+    rn[2 * C + c] = r * ((double)gamma[c] * rn[c] - (double)HW * a1 / m - (double)HW * (double)xbar[o] * a2 / m);
+  }
+}
+
+// parameter gradients: sums over the images, in image order
+__global__ void gn_param_grads_kernel(const double* __restrict__ rows, int C, int N, float* dgamma, float* dbeta, float* dbias,
+                                      int accumulate) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double db = 0.0, dg = 0.0, dbc = 0.0;
+  for (int n = 0; n < N; ++n) {
+    const double* rn = rows + (size_t)n * 3 * C;
+    db += rn[c];
+    dg += rn[C + c];
+    dbc += rn[2 * C + c];
+  }
+  if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)dg;
+  if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)db;
+  if (dbias) dbias[c] = (accumulate ? dbias[c] : 0.f) + (float)dbc;
+}
+
+extern "C" size_t pp_gn_workspace(int C, int HW, int N) {
+  return pp_bn_workspace(C, HW, N) + (size_t)N * 3 * C * sizeof(double) + (size_t)3 * N * C * sizeof(float) + 64;
+}
+
+static int gn_check(const float* z, int ld, int C, int HW, int N, int G, const void* workspace, size_t workspace_bytes,
+                    const char* who) {
+  if (int rc = bn_check(z, ld, C, HW, N)) return rc;
+  PP_CHECK_ARG(G > 0 && C % G == 0, "%s: G=%d must divide C=%d", who, G, C);
+  PP_CHECK_ARG(workspace != nullptr, "%s: null workspace", who);
+  if (workspace_bytes < pp_gn_workspace(C, HW, N)) {
+    pp_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, pp_gn_workspace(C, HW, N));
+    return PP_ERR_WORKSPACE;
+  }
+  return 0;
+}
+
+struct GnWs { double* partial; double* rows; float *kA, *kB, *kC; };
+
+static GnWs gn_ws(void* workspace, int C, int HW, int N) {
+  GnWs w;
+  w.partial = reinterpret_cast<double*>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+  w.rows = w.partial + (size_t)N * col_plan(C, HW, N).nblk * 2 * C;     // the pooled form's plan has no more blocks than this one
+  w.kA = reinterpret_cast<float*>(w.rows + (size_t)N * 3 * C);
+  w.kB = w.kA + (size_t)N * C;
+  w.kC = w.kB + (size_t)N * C;
+  return w;
+}
+
+extern "C" int pp_gn_stats(const float* z, int ld, int C, int HW, int N, int G, float eps, const float* gamma, const float* beta,
+                           float* save_mean, float* save_invstd, float* save_xbar, float* scale, float* shift, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = gn_check(z, ld, C, HW, N, G, workspace, workspace_bytes, "gn_stats")) return rc;
+  PP_CHECK_ARG(gamma && beta && save_mean && save_invstd && save_xbar && scale && shift, "gn_stats: null pointer");
+  ColPlan p = col_plan(C, HW, N);
+  GnWs w = gn_ws(workspace, C, HW, N);
+  pp_prof_begin(PP_K_BN, 0.0, 4.0 * (double)N * HW * C, s);
+  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(p.nblk, N), dim3(NORM_THREADS), 0, s, z, ld, C, HW, p.chunk, p.rows, w.partial);
+  hipLaunchKernelGGL(gn_stats_finalize_kernel, dim3(G, N), dim3(GN_THREADS), 0, s, w.partial, p.nblk, C, G, HW, eps, gamma, beta,
+                     save_mean, save_invstd, save_xbar, scale, shift);
+  pp_prof_end(s);
+  return pp_launch_status("gn_stats");
+}
+
+extern "C" int pp_gn_lrelu_bwd(const float* dy, int ld_dy, const float* z, int ld_z, const float* scale, const float* shift,
+                               const float* save_mean, const float* save_invstd, const float* save_xbar, const float* gamma,
+                               float* dz, int ld_dz, float* dgamma, float* dbeta, float* dbias_conv, int accumulate_param_grads,
+                               int C, int HW, int N, int G, float slope, void* workspace, size_t workspace_bytes, float* dz_amax,
+                               void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = gn_check(z, ld_z, C, HW, N, G, workspace, workspace_bytes, "gn_lrelu_bwd")) return rc;
+  PP_CHECK_ARG(dy && dz && scale && shift && save_mean && save_invstd && save_xbar && gamma, "gn_lrelu_bwd: null pointer");
+  PP_CHECK_ARG(ld_dy % 4 == 0 && ld_dz % 4 == 0 && ld_dy >= C && ld_dz >= C, "gn_lrelu_bwd: bad ld");
+  PP_CHECK_ARG(((((uintptr_t)dy) | ((uintptr_t)dz)) & PP_ACT_ALIGN) == 0, "gn_lrelu_bwd: tensors must be 16-byte aligned");
+  ColPlan p = col_plan(C, HW, N);
+  GnWs w = gn_ws(workspace, C, HW, N);
+  pp_prof_begin(PP_K_BN, 0.0, 20.0 * (double)N * HW * C, s);
+  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(p.nblk, N), dim3(NORM_THREADS), 0, s, dy, ld_dy, z, ld_z, scale, shift, save_mean,
+                     save_invstd, C, HW, p.chunk, p.rows, slope, w.partial);
+  hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(G, N), dim3(GN_THREADS), 0, s, w.partial, p.nblk, C, G, HW, gamma, save_mean,
+                     save_invstd, save_xbar, w.kA, w.kB, w.kC, w.rows, dz_amax);
+  hipLaunchKernelGGL(gn_param_grads_kernel, dim3(pp_cdiv(C, 64)), dim3(64), 0, s, w.rows, C, N, dgamma, dbeta, dbias_conv,
+                     accumulate_param_grads);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(p.nblk, N), dim3(NORM_THREADS), 0, s, dy, ld_dy, z, ld_z, scale, shift, w.kA, w.kB,
+                     w.kC, dz, ld_dz, C, HW, p.chunk, p.rows, slope, dz_amax);
+  pp_prof_end(s);
+  return pp_launch_status("gn_lrelu_bwd");
+}
+
+// the same for a layer whose output also feeds a 2x2 max-pooling: dpool (N, H/2, W/2) is added to each window's winner on the fly
+// (the window walk of bn_bwd_pool_kernel, modes 0 and 1)
+extern "C" int pp_gn_lrelu_bwd_pool(const float* dy, int ld_dy, const float* dpool, int ld_dpool, const float* z, int ld_z,
+                                    const float* scale, const float* shift, const float* save_mean, const float* save_invstd,
+                                    const float* save_xbar, const float* gamma, float* dz, int ld_dz, float* dgamma, float* dbeta,
+                                    float* dbias_conv, int accumulate_param_grads, int C, int N, int H, int W, int G, float slope,
+                                    void* workspace, size_t workspace_bytes, float* dz_amax, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = bn_pool_check(dy, ld_dy, dpool, ld_dpool, dz, ld_dz, C, N, H, W, N)) return rc;
+  const int HW = H * W, Wpg = HW / 4;
+  if (int rc = gn_check(z, ld_z, C, HW, N, G, workspace, workspace_bytes, "gn_lrelu_bwd_pool")) return rc;
+  PP_CHECK_ARG(scale && shift && save_mean && save_invstd && save_xbar && gamma, "gn_lrelu_bwd_pool: null pointer");
+  ColPlan p = col_plan(C, Wpg, N);
+  GnWs w = gn_ws(workspace, C, HW, N);
+  pp_prof_begin(PP_K_BN, 0.0, 22.0 * (double)N * HW * C, s);
+  hipLaunchKernelGGL(bn_bwd_pool_kernel<0>, dim3(p.nblk, N), dim3(NORM_THREADS), 0, s, dy, ld_dy, dpool, ld_dpool, z, ld_z, scale,
+                     shift, save_mean, save_invstd, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                     (act_t*)nullptr, 0, C, H, W, Wpg, p.chunk, p.rows, slope, 1.0f / slope, w.partial, (float*)nullptr);
+  hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(G, N), dim3(GN_THREADS), 0, s, w.partial, p.nblk, C, G, HW, gamma, save_mean,
+                     save_invstd, save_xbar, w.kA, w.kB, w.kC, w.rows, dz_amax);
+  hipLaunchKernelGGL(gn_param_grads_kernel, dim3(pp_cdiv(C, 64)), dim3(64), 0, s, w.rows, C, N, dgamma, dbeta, dbias_conv,
+                     accumulate_param_grads);
+  hipLaunchKernelGGL(bn_bwd_pool_kernel<1>, dim3(p.nblk, N), dim3(NORM_THREADS), 0, s, dy, ld_dy, dpool, ld_dpool, z, ld_z, scale,
+                     shift, (const float*)nullptr, (const float*)nullptr, w.kA, w.kB, w.kC, dz, ld_dz, C, H, W, Wpg, p.chunk, p.rows,
+                     slope, 1.0f / slope, (double*)nullptr, dz_amax);
+  pp_prof_end(s);
+  return pp_launch_status("gn_lrelu_bwd_pool");
+}
+#endif  // !PP_ACT_16
 PP_NS_END

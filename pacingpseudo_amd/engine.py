@@ -26,6 +26,7 @@ from collections import OrderedDict
 from typing import Dict, List, Optional
 
 import torch
+import torch.nn as nn
 
 from ._lib import PpBnCoefItem, PpLazyIn, PpPackItem, PpWinoPackItem, lib, lib_for, prof_range, stream_ptr
 
@@ -167,6 +168,8 @@ class _Layer:
 
     def __init__(self, name, conv, bn, dil):
         self.name, self.conv, self.bn, self.dil = name, conv, bn, dil
+        # nn.GroupNorm holder (--norm_op group): per-(image, channel group) statistics in both modes, no running state
+        self.gn = isinstance(bn, nn.GroupNorm)
         self.stride = int(conv.stride[0])     # 2: first convolution of a down-sampling stage under --is_stride_conv (unet.py:113-116)
         self.cout, self.cin = conv.weight.shape[0], conv.weight.shape[1]
         self.cin_pad = _pad4(self.cin)
@@ -350,7 +353,8 @@ class _Plan:
             # fused epilogue), so only the other layers -- and every layer of the unfused A/B path -- own a z buffer
             if not (self.lazy_out[L.name] and FUSE_BN):
                 self.zbuf[L.name] = act(n, h, w, L.cout)[0]
-            self.coef[L.name] = torch.empty((4, groups, L.cout), **f32)
+            # GroupNorm: [mean, invstd, scale, shift, xbar] rows per IMAGE (pp_gn_stats), whatever the statistics groups
+            self.coef[L.name] = torch.empty((5, n, L.cout) if L.gn else (4, groups, L.cout), **f32)
             # per-channel sums of the split (synchronised) BatchNorm calls: [0] forward, [1] backward local, [2] backward global
             self.bn_sums[L.name] = torch.zeros((3, groups, 2, L.cout), device=dev, dtype=torch.float64)
             if L.stride == 2:                  # (h, w) = output size; the convolution itself runs at (2 h, 2 w)
@@ -483,6 +487,8 @@ class _Plan:
                 wg = max(wg, lib.pp_conv3x3_bwd_weight_workspace(L.cout, L.cin_pad, n, hL, wL))
                 self.wg_ws_bytes = max(self.wg_ws_bytes, lib.pp_conv3x3_bwd_weight_workspace(L.cout, L.cin_pad, n, hL, wL))
             bn = max(bn, lib.pp_bn_workspace(L.cout, (n // g) * hL * wL, g) + 12 * g * L.cout)
+            if L.gn:
+                bn = max(bn, lib.pp_gn_workspace(L.cout, hL * wL, n))
             if trainable and L.cin == 1:
                 bn = max(bn, lib.pp_bn_lrelu_bwd_wgrad_c1_workspace(L.cout, (n // g) * hL * wL, g),
                          lib.pp_bn_lrelu_bwd_wgrad_c1_workspace(L.cout, n * hL * wL, 1))
@@ -560,6 +566,8 @@ class _Plan:
         if eng.aux_layer is not None:
             out[eng.aux_layer.name] = False
         if not (LAZY_BN and FUSE_BN):       # the lazy forms hang off the fused conv + BN entry points
+            return out
+        if any(L.gn for L in eng.layers):   # GroupNorm outputs are always materialised (the lazy consumers know <= 2 statistics groups)
             return out
         # stage outputs (skip connections, pooled / up-sampled / concatenated tensors, the auxiliary input) are always
         # materialised: their consumers (max-pooling, bilinear x2, Winograd input transform) have no on-load form (measured
@@ -647,6 +655,11 @@ class StepEngine:
                 raise NotImplementedError('16-bit storage: the strided / transposed-convolution U-Net variant has no fp16 kernels')
             if not (F16X3_ENABLED and FUSE_BN):
                 raise NotImplementedError('16-bit storage needs the split-fp16 matrix kernels and the fused BatchNorm epilogues')
+        if any(L.gn for L in self.layers):
+            if self.h16:
+                raise NotImplementedError(f'--norm_op group has fp32 kernels only: --storage {self.storage} is not supported with it')
+            if any(L.stride != 1 for L in self.layers) or any(d.trans for d in backbone.dec_blocks().values()):
+                raise NotImplementedError('--norm_op group: the strided / transposed-convolution U-Net variant is not supported')
 
     # ------------------------------------------------------------------ plumbing
     @property
@@ -805,6 +818,8 @@ class StepEngine:
             # what this step's backward reads (kept with the step, not the layer): input view (+ whether it was lazy),
             # output view, groups, whether the output is lazy (then the output buffer holds z)
             self._rec[L.name] = (x, y, groups, lazy, x.lazy)
+        if L.gn:
+            return self._convgn_fwd(plan, L, x, y, zptr, zld, st, pool_out)
 
         def finalize(sums_ptr, rows, n_per_group):
             args = (sums_ptr, rows, C, n_per_group, groups, BN_EPS, BN_MOM, bn.weight.data_ptr(), bn.bias.data_ptr(),
@@ -886,6 +901,33 @@ class StepEngine:
         if not lazy:
             plan.K.pp_bn_lrelu_fwd(zptr, zld, scale, shift, y.ptr, y.ld, C, ppg, groups, SLOPE, st)
 
+    def _convgn_fwd(self, plan, L: _Layer, x: View, y: View, zptr, zld, st, pool_out: Optional[View] = None):
+        """conv3x3 + GroupNorm + LeakyReLU of one layer, the same in train and eval mode: z = conv(x) (no fused epilogue),
+        per-(image, group) statistics (pp_gn_stats), then the BatchNorm apply pass with one coefficient row per image."""
+        C, gn = L.cout, L.bn
+        assert x.lazy_arg() is None and L.stride == 1
+        if plan.wino[L.name]:
+            vk = plan.vkeep[L.name].data_ptr() if L.name in plan.vkeep else None
+            fwd = plan.K.pp_conv3x3_wino_fwd_f16x3 if plan.wino16_fwd[L.name] else plan.K.pp_conv3x3_wino_fwd
+            fwd(x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), zptr, zld, C, x.N, x.H, x.W, L.dil, 0, vk,
+                *plan.ws_args(), st)
+        elif plan.f16[L.name]:
+            plan.K.pp_conv3x3_fwd_f16x3(x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), zptr, zld, C,
+                                     x.N, x.H, x.W, L.dil, 0, None, st)
+        else:
+            plan.K.pp_conv3x3_fwd(x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), zptr, zld, C,
+                               x.N, x.H, x.W, L.dil, 0, st)
+        coef = plan.coef[L.name]
+        mean, invstd, scale, shift, xbar = (coef[i].data_ptr() for i in range(5))
+        N, HW = x.N, x.H * x.W
+        plan.K.pp_gn_stats(zptr, zld, C, HW, N, gn.num_groups, float(gn.eps), gn.weight.data_ptr(), gn.bias.data_ptr(),
+                           mean, invstd, xbar, scale, shift, *plan.ws_args(), st)
+        if pool_out is not None and FUSE_POOL_FWD:
+            plan.K.pp_bn_lrelu_fwd_pool(zptr, zld, scale, shift, y.ptr, y.ld, pool_out.ptr, pool_out.ld, C, N, y.H, y.W, N, SLOPE, st)
+            return True
+        plan.K.pp_bn_lrelu_fwd(zptr, zld, scale, shift, y.ptr, y.ld, C, HW, N, SLOPE, st)
+        return False
+
     def _convbn_bwd(self, plan, L: _Layer, dy: View, dx: Optional[View], dx_accumulate, training, grads, st, pool: Optional[View] = None):
         """dy: gradient wrt the layer output.  Writes parameter gradients, and dx (+)= data gradient.  pool: gradient of the
         2x2-max-pooled copy of the layer output (half the size of dy), added to each window's winner inside the BatchNorm backward."""
@@ -899,7 +941,7 @@ class StepEngine:
         ppg = (x.N // groups) * (x.H // L.stride) * (x.W // L.stride)        # pixels of the layer OUTPUT per group
         mean, invstd, scale, shift = (coef[i].data_ptr() for i in range(4))
         gw, gb, gg, gbeta = grads[L.conv.weight], grads[L.conv.bias], grads[L.bn.weight], grads[L.bn.bias]
-        if (FUSE_WG1 and dx is None and pool is None and L.cin == 1 and L.stride == 1 and L.dil == 1 and not x_lazy
+        if (FUSE_WG1 and not L.gn and dx is None and pool is None and L.cin == 1 and L.stride == 1 and L.dil == 1 and not x_lazy
                 and not plan.wino[L.name] and not plan.f16[L.name] and not (training and self.comm is not None and self.sync_bn)):
             # the first layer: dz has one reader, the weight gradient -- formed and consumed in one pass, never written
             if FUSE_BN and not training:
@@ -922,7 +964,20 @@ class StepEngine:
         dz = (plan.s1b if slot else plan.s1).data_ptr()
         f16 = plan.f16[L.name]
         need_amax = L.name in plan.amax                      # split-fp16 consumers scale dz by a power of two from max |dz|
-        if pool is not None:
+        if L.gn:
+            # GroupNorm: statistics of this forward per (image, group), whatever `training` and sync_bn say
+            am = plan.amax[L.name].data_ptr() if need_amax else None
+            xbar, gn = coef[4].data_ptr(), L.bn
+            if pool is not None:
+                y = y_rec
+                plan.K.pp_gn_lrelu_bwd_pool(dy.ptr, dy.ld, pool.ptr, pool.ld, zptr, zld, scale, shift, mean, invstd, xbar,
+                                            gn.weight.data_ptr(), dz, C, gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C, y.N,
+                                            y.H, y.W, gn.num_groups, SLOPE, plan.ws.data_ptr(), plan.ws_bytes, am, st)
+            else:
+                plan.K.pp_gn_lrelu_bwd(dy.ptr, dy.ld, zptr, zld, scale, shift, mean, invstd, xbar, gn.weight.data_ptr(), dz, C,
+                                       gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C, x.H * x.W, x.N, gn.num_groups, SLOPE,
+                                       plan.ws.data_ptr(), plan.ws_bytes, am, st)
+        elif pool is not None:
             am = plan.amax[L.name].data_ptr() if need_amax else None
             y = y_rec
             if FUSE_BN and not training:
@@ -1039,7 +1094,9 @@ class StepEngine:
         parameters and running statistics only, so ONE launch at the start of the forward writes all 22 coefficient rows
         (pp_bn_eval_coeffs_batch; bit-identical to the per-layer pp_bn_eval_coeffs it replaces, which sat between the convolutions
         of the critical chain).  The item table is rebuilt when a parameter or a buffer moved."""
-        layers = [L for L in self.layers if L.stride == 1]
+        layers = [L for L in self.layers if L.stride == 1 and not L.gn]
+        if not layers:                  # a GroupNorm backbone: no BatchNorm coefficient rows to write
+            return frozenset()
         key = tuple((L.bn.weight.data_ptr(), L.bn.running_mean.data_ptr(), plan.coef[L.name].data_ptr()) for L in layers)
         if getattr(plan, 'coef_batch_key', None) != key:
             items = []

@@ -51,10 +51,16 @@ parser.add_argument('--elab_end_points', type=bool, default=False)
 # ---- additions of this implementation
 parser.add_argument('--image_size', type=int, default=0, help='size of the --synthetic phantoms (0 = the data set\'s training crop); real slices are evaluated at their native size')
 parser.add_argument('--synthetic', type=int, default=0, help='evaluate N phantom slices instead of ./data')
+parser.add_argument('--norm_op', type=str, default='batch', choices=['batch', 'group'],
+                    help='block normaliser the checkpoint was trained with: batch = nn.BatchNorm2d (the reference); group = nn.GroupNorm(--norm_groups, C): '
+                         'per-image statistics, no running state, the same function in train and eval mode (fp32 storage only)')
+parser.add_argument('--norm_groups', type=int, default=8, help='channel groups of --norm_op group; must divide every block width')
 
 
 def load_backbone(model, state_dict):
     """inference.py:138-146: a full-model checkpoint is reduced to its `backbone.` entries."""
+    from .models.unet import check_checkpoint_norm
+    check_checkpoint_norm(model, state_dict)
     try:
         model.load_state_dict(state_dict)
     except RuntimeError:
@@ -88,6 +94,7 @@ def evaluate(model, loader, num_classes, spacing, device):
 def main_interface(args):
     from .data import NpzSlices, SyntheticPhantoms, collate_by_shape, loader_context
     from .models import UNet
+    from .models.unet import norm_kwargs
     from .utils import AvgMeter
     num_classes, spacing = CLASSES[args.dataset], SPACING[args.dataset]
     size = args.image_size or CROP[args.dataset]          # only the size of --synthetic phantoms; real slices keep theirs
@@ -96,7 +103,7 @@ def main_interface(args):
     device = torch.device('cuda', 0)
     model = UNet(input_ch=args.input_ch, init_ch=args.init_ch, max_ch=args.max_ch, num_classes=num_classes,
                  output_stride=args.output_stride, is_stride_conv=args.is_stride_conv, is_trans_conv=args.is_trans_conv,
-                 elab_end_points=args.elab_end_points).to(device)
+                 elab_end_points=args.elab_end_points, **norm_kwargs(args)).to(device)
     if args.synthetic:
         test_dataset = SyntheticPhantoms(args.synthetic, num_classes, size=size, train=False, seed=args.seed, native=True, compact=True)
     else:

@@ -137,7 +137,11 @@ parser.add_argument('--graph_step', action='store_true',
 parser.add_argument('--sync_bn', action='store_true',
                     help='data-parallel runs: BatchNorm batch statistics over the GLOBAL batch during epoch 0 '
                          '(= the single-process step on the concatenated batch); default: per-rank statistics, '
-                         'running buffers averaged before the switch to eval mode')
+                         'running buffers averaged before the switch to eval mode; no effect on --norm_op group blocks')
+parser.add_argument('--norm_op', type=str, default='batch', choices=['batch', 'group'],
+                    help='block normaliser of the U-Net: batch = nn.BatchNorm2d (the reference); group = nn.GroupNorm(--norm_groups, C): '
+                         'per-image statistics, no running state, the same function in train and eval mode (fp32 storage only)')
+parser.add_argument('--norm_groups', type=int, default=8, help='channel groups of --norm_op group; must divide every block width')
 
 
 # The reference ships ONE driver (train_chaos.py) and three dataset packages that differ only in class tables and
@@ -179,6 +183,7 @@ def train_interface(args):
     from . import parallel
     from .data import SyntheticPhantoms, collate_by_shape, dataset_class, expand_compact, loader_context
     from .models import ConsistencyRegulr
+    from .models.unet import norm_kwargs
     from .optim import FusedAdam, FusedSGD
     from .utils import AvgMeter, cosine_lr_decay, gaussian_ramp_up, linear_lr_decay, poly_lr_decay
     from .losses.losses import weighted_loss_sum
@@ -196,7 +201,7 @@ def train_interface(args):
         kwargs_unet=dict(input_ch=args.input_ch, init_ch=args.init_ch, max_ch=args.max_ch,
                          num_classes=args.num_classes, output_stride=args.output_stride,
                          is_stride_conv=args.is_stride_conv, is_trans_conv=args.is_trans_conv,
-                         elab_end_points=args.elab_end_points),
+                         elab_end_points=args.elab_end_points, **norm_kwargs(args)),
         kwargs_aux_path=dict(num_classes=args.num_classes, feat_stage=args.feat_stage, feat_ch=args.feat_ch,
                              hid_ch=args.hid_ch, aux_drop_prob=args.aux_drop_prob, do_memory=args.do_memory,
                              max_step=args.epoch, update_momentum=args.update_momentum,

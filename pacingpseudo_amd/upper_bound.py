@@ -61,6 +61,10 @@ parser.add_argument('--max_iters', type=int, default=0)
 parser.add_argument('--cpu_input', action='store_true',
                     help='minimal CPU input path of data.py (MeanStdNorm + centre crop only) instead of the weak augmentation '
                          'pipeline on the GPU')
+parser.add_argument('--norm_op', type=str, default='batch', choices=['batch', 'group'],
+                    help='block normaliser of the U-Net: batch = nn.BatchNorm2d (the reference); group = nn.GroupNorm(--norm_groups, C): '
+                         'per-image statistics, no running state, the same function in train and eval mode (fp32 storage only)')
+parser.add_argument('--norm_groups', type=int, default=8, help='channel groups of --norm_op group; must divide every block width')
 parser.add_argument('--gpu_augment', action='store_true', help='accepted for compatibility: the GPU pipeline is the default')
 
 
@@ -69,6 +73,7 @@ def train_interface(args):
     from .data import SyntheticPhantoms, collate_by_shape, dataset_class, expand_compact, loader_context
     from .losses.losses import dice_loss_fn, partial_cross_entropy_loss
     from .models import UNet
+    from .models.unet import norm_kwargs
     from .optim import FusedAdam
     from .train import _class_names
     from .utils import cosine_lr_decay, linear_lr_decay, poly_lr_decay
@@ -80,7 +85,7 @@ def train_interface(args):
     best_avg, best_epoch, best_avg_class = 0, 0, []
     model = UNet(input_ch=args.input_ch, init_ch=args.init_ch, max_ch=args.max_ch, num_classes=args.num_classes,
                  output_stride=args.output_stride, is_stride_conv=args.is_stride_conv, is_trans_conv=args.is_trans_conv,
-                 elab_end_points=args.elab_end_points).cuda()
+                 elab_end_points=args.elab_end_points, **norm_kwargs(args)).cuda()
     logging.info(model)
     optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd)
     ds_kw = dict(num_classes=args.num_classes, size=args.image_size, seed=args.seed)

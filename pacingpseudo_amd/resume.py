@@ -1,0 +1,236 @@
+"""Epoch-boundary run state for the training drivers (``--state_interval N`` / ``--resume PATH``).
+
+``ckps/ckp_<epoch>.pth`` and ``best_ckp.pth`` keep the reference's layout (``model.state_dict()`` only; inference.py and the
+reference load them).  A state file ``ckps/state_<epoch>.pth`` holds everything else a run keeps in its process, so that a
+run stopped after epoch e and resumed ends exactly where the uninterrupted run ends, bit for bit: the model (BatchNorm buffers
+and memory bank included), the optimiser (slab moments, per-segment step counts), the 16-bit storage loss scale and its
+overflow-guard counters, eval mode, the best-Dice bookkeeping, ``valdice[:e+1]`` and, for every rank, the python / numpy /
+torch CPU / torch CUDA generators and the ``DeviceAugmenter``'s host ``RandomState``.
+
+Everything in the file is a tensor or a plain python value, so it loads with ``torch.load(weights_only=True)``.
+"""
+from __future__ import annotations
+
+import glob
+import json
+import os
+import random
+import re
+import tempfile
+
+import numpy as np
+import torch
+
+FORMAT = 'pacingpseudo_amd run state'
+VERSION = 1
+
+# flags that select where a run writes or how its host side is organised, never what it computes: they may differ on resume.
+# (--graph_step replays the eager step bit for bit; --root / --tag only name the run directory, and a resumed run continues in
+# the directory its state file belongs to; --gpu_augment is an accepted no-op.)
+MAY_DIFFER = frozenset({'gpu', 'num_workers', 'graph_step', 'resume', 'state_interval', 'root', 'tag', 'gpu_augment'})
+# attributes the drivers add to the namespace after parsing (not flags)
+_DERIVED = frozenset({'child', 'train_ls', 'val_ls'})
+
+
+class ResumeError(ValueError):
+    """A state file that cannot be resumed from, or a command line that does not match it."""
+
+
+def add_flags(parser) -> None:
+    parser.add_argument('--state_interval', type=int, default=0,
+                        help='write ckps/state_<epoch>.pth (everything needed to resume the run bit for bit) every this many '
+                             'epochs and after the last one; 0 = never')
+    parser.add_argument('--resume', type=str, default=None,
+                        help='continue the run of this state file (or of the highest-numbered ckps/state_*.pth of this run '
+                             'directory) in its own directory, from the epoch after the saved one')
+
+
+def flag_dict(args) -> dict:
+    """The parsed (and preset-resolved) flags of a run, without the attributes the drivers derive from them."""
+    return {k: v for k, v in vars(args).items() if k not in _DERIVED}
+
+
+# ---- files ---------------------------------------------------------------------------------------------------------------
+def state_path(run_dir: str, epoch: int) -> str:
+    return os.path.join(run_dir, 'ckps', f'state_{epoch:d}.pth')
+
+
+def resolve(path: str) -> str:
+    """A state file as given, or the highest-numbered ``ckps/state_<e>.pth`` of a run directory."""
+    if os.path.isdir(path):
+        found = []
+        for f in glob.glob(os.path.join(path, 'ckps', 'state_*.pth')):
+            m = re.fullmatch(r'state_(\d+)\.pth', os.path.basename(f))
+            if m:
+                found.append((int(m.group(1)), f))
+        if not found:
+            raise ResumeError(f'--resume {path}: the run directory holds no ckps/state_<epoch>.pth '
+                              '(state files are written with --state_interval N)')
+        return max(found)[1]
+    if not os.path.isfile(path):
+        raise ResumeError(f'--resume {path}: no such state file or run directory')
+    return path
+
+
+def run_dir_of(path: str) -> str:
+    """The run directory a state file belongs to (<run>/ckps/state_<e>.pth)."""
+    return os.path.dirname(os.path.dirname(os.path.abspath(path)))
+
+
+def atomic_save(obj, path: str) -> None:
+    """torch.save through a temporary file in the same directory + os.replace: a kill during the write never leaves a
+    truncated file under `path`."""
+    d = os.path.dirname(os.path.abspath(path))
+    fd, tmp = tempfile.mkstemp(prefix='.' + os.path.basename(path) + '.', suffix='.tmp', dir=d)
+    try:
+        with os.fdopen(fd, 'wb') as f:
+            torch.save(obj, f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+
+
+def load(path: str) -> dict:
+    """Read and validate a state file (CPU tensors)."""
+    try:
+        st = torch.load(path, map_location='cpu', weights_only=True)
+    except Exception as e:                      # truncated / not a torch file / foreign pickle
+        raise ResumeError(f'--resume {path}: not a readable run-state file ({type(e).__name__}: {str(e).splitlines()[0] if str(e) else ""})') from None
+    if not isinstance(st, dict) or st.get('format') != FORMAT:
+        raise ResumeError(f'--resume {path}: not a run-state file (ckps/state_<epoch>.pth written with --state_interval); '
+                          'ckp_*.pth / best_ckp.pth hold model weights only and cannot be resumed from')
+    if st.get('version') != VERSION:
+        raise ResumeError(f'--resume {path}: unknown state format version {st.get("version")!r} (this build reads version {VERSION})')
+    return st
+
+
+def check_compatible(saved: dict, new: dict, world: int, saved_world: int) -> None:
+    """Refuse a resume whose command line would compute something else than the saved run: every flag outside MAY_DIFFER
+    must match, and so must the number of ranks."""
+    if int(world) != int(saved_world):
+        raise ResumeError(f'--resume: the run was saved with world size {saved_world} and is resumed with world size {world}; '
+                          'the data shards, batch statistics and RNG streams are per rank, so the world size must match')
+    keys = sorted((set(saved) | set(new)) - MAY_DIFFER)
+    diff = [k for k in keys if saved.get(k) != new.get(k)]
+    if diff:
+        raise ResumeError('--resume: these flags differ from the saved run and would change what it computes: '
+                          + ', '.join(f'--{k} (saved {saved.get(k)!r}, now {new.get(k)!r})' for k in diff))
+
+
+def truncate_scalars(path: str, last_epoch: int) -> None:
+    """Keep the lines of tb_summary/scalars.jsonl whose step is <= last_epoch (an epoch cut short leaves none behind)."""
+    if not os.path.isfile(path):
+        return
+    keep = []
+    with open(path) as f:
+        for line in f:
+            try:
+                rec = json.loads(line)
+            except ValueError:
+                continue                        # a line the killed run did not finish
+            if int(rec.get('step', last_epoch + 1)) <= last_epoch:
+                keep.append(line if line.endswith('\n') else line + '\n')
+    d = os.path.dirname(os.path.abspath(path))
+    fd, tmp = tempfile.mkstemp(prefix='.scalars.', suffix='.tmp', dir=d)
+    with os.fdopen(fd, 'w') as f:
+        f.writelines(keep)
+    os.replace(tmp, path)
+
+
+# ---- random generators -----------------------------------------------------------------------------------------------------
+def _np_state_out(s):
+    return (s[0], torch.from_numpy(s[1].astype(np.int64)), int(s[2]), int(s[3]), float(s[4]))
+
+
+def _np_state_in(s):
+    return (s[0], s[1].numpy().astype(np.uint32), int(s[2]), int(s[3]), float(s[4]))
+
+
+def rng_states(device, augmenter=None) -> dict:
+    return dict(python=random.getstate(), numpy=_np_state_out(np.random.get_state()), torch=torch.get_rng_state(),
+                cuda=torch.cuda.get_rng_state(device),
+                augmenter=_np_state_out(augmenter.rng.get_state()) if augmenter is not None else None)
+
+
+def set_rng_states(st: dict, device, augmenter=None) -> None:
+    random.setstate(st['python'])
+    np.random.set_state(_np_state_in(st['numpy']))
+    torch.set_rng_state(st['torch'])
+    torch.cuda.set_rng_state(st['cuda'], device)
+    if augmenter is not None:
+        augmenter.rng.set_state(_np_state_in(st['augmenter']))
+
+
+def gather_rng_states(device, augmenter, world: int) -> list:
+    """Every rank's generator states, in rank order (a collective when world > 1: every rank calls it)."""
+    mine = rng_states(device, augmenter)
+    if world == 1:
+        return [mine]
+    import torch.distributed as dist
+    out = [None] * world
+    dist.all_gather_object(out, mine)
+    return out
+
+
+def prime_persistent_loaders(loaders) -> None:
+    """A loader with persistent workers draws its worker base seed from the torch default generator once, when its iterator
+    is created (epoch 0 of an uninterrupted run); every epoch draws the sampler's seed.  A resumed process creates the
+    iterators here, BEFORE the saved generator state is restored, so that the restored state is next drawn from by the first
+    resumed epoch's shuffle, as in the uninterrupted run.  The prefetched batches of this iterator are dropped by the
+    iterator's reset at the start of that epoch."""
+    for loader in loaders:
+        if loader.num_workers > 0 and loader.persistent_workers:
+            iter(loader)
+
+
+# ---- the state file ----------------------------------------------------------------------------------------------------------
+def capture(args, epoch: int, model, optimizer, best, valdice, rngs, world: int) -> dict:
+    flat = getattr(model, 'flat', None)
+    engine = getattr(model, 'engine', None)
+    best_avg, best_epoch, best_avg_class = best
+    return dict(
+        format=FORMAT, version=VERSION, args=flag_dict(args), world_size=int(world), epoch=int(epoch),
+        model={k: v.detach().cpu() for k, v in model.state_dict().items()},
+        optimizer=optimizer.state_dict(),
+        loss_scale=float(engine.loss_scale) if engine is not None else None,
+        guard=flat.guard.detach().cpu() if flat is not None else None,
+        skipped_logged=int(getattr(flat, '_skipped_logged', 0)) if flat is not None else 0,
+        training=bool(model.training),
+        best_avg=float(best_avg), best_epoch=int(best_epoch), best_avg_class=[float(v) for v in best_avg_class],
+        valdice=torch.from_numpy(np.asarray(valdice[:epoch + 1], dtype=np.float64).copy()),
+        rng=rngs)
+
+
+def restore(st: dict, model, optimizer, valdice):
+    """Load the model / optimiser / loss-scale state of `st` into a freshly built run (in place: the flat parameter slab and
+    every pointer the engine baked stay valid).  Returns (best_avg, best_epoch, best_avg_class)."""
+    model.load_state_dict(st['model'])
+    if not st['training']:
+        model.eval()
+    optimizer.load_state_dict(st['optimizer'])
+    engine = getattr(model, 'engine', None)
+    if engine is not None and st.get('loss_scale') is not None:
+        engine.set_loss_scale(st['loss_scale'])
+    flat = getattr(model, 'flat', None)
+    if flat is not None and st.get('guard') is not None:
+        flat.guard.copy_(st['guard'].to(flat.guard.device))
+        flat._skipped_logged = int(st['skipped_logged'])
+    e = int(st['epoch'])
+    valdice[:e + 1] = st['valdice'].numpy()
+    return st['best_avg'], st['best_epoch'], list(st['best_avg_class'])
+
+
+def open_state(parser, args, world: int):
+    """--resume: (state file, its contents), checked against this command line before anything touches the GPU.  A refusal
+    is a usage error of `parser` (message on stderr, exit status 2)."""
+    try:
+        path = resolve(args.resume)
+        st = load(path)
+        check_compatible(st['args'], flag_dict(args), world, st['world_size'])
+    except ResumeError as e:
+        parser.error(str(e))
+    return path, st

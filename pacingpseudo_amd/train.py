@@ -28,6 +28,8 @@ import time
 import numpy as np
 import torch
 
+from . import resume
+
 parser = argparse.ArgumentParser(description='PacingPseudo training on MI355X (flag surface of the reference driver)')
 
 
@@ -142,6 +144,7 @@ parser.add_argument('--norm_op', type=str, default='batch', choices=['batch', 'g
                     help='block normaliser of the U-Net: batch = nn.BatchNorm2d (the reference); group = nn.GroupNorm(--norm_groups, C): '
                          'per-image statistics, no running state, the same function in train and eval mode (fp32 storage only)')
 parser.add_argument('--norm_groups', type=int, default=8, help='channel groups of --norm_op group; must divide every block width')
+resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
 
 
 # The reference ships ONE driver (train_chaos.py) and three dataset packages that differ only in class tables and
@@ -179,7 +182,7 @@ def apply_dataset_preset(args, argv=None):
     return args
 
 
-def train_interface(args):
+def train_interface(args, resume_state=None):
     from . import parallel
     from .data import SyntheticPhantoms, collate_by_shape, dataset_class, expand_compact, loader_context
     from .models import ConsistencyRegulr
@@ -265,7 +268,14 @@ def train_interface(args):
     valdice = np.zeros(args.epoch)
     graph_step = None                            # --graph_step: pacingpseudo_amd.graph.GraphedStep, built on first use
     aug_stream = torch.cuda.Stream() if (augmenter is not None and os.environ.get('PP_AUG_STREAM', '1') != '0') else None
-    for curr_epoch in range(args.epoch):
+    start_epoch = 0
+    if resume_state is not None:
+        best_avg, best_epoch, best_avg_class = resume.restore(resume_state, model, optimizer, valdice)
+        train_dataset.set_epoch(0)                 # what the uninterrupted run's persistent workers were forked with
+        resume.prime_persistent_loaders([train_loader, val_loader])
+        resume.set_rng_states(resume_state['rng'][rank], device, augmenter)
+        start_epoch = resume_state['epoch'] + 1
+    for curr_epoch in range(start_epoch, args.epoch):
         epoch_tic = time.time()
         if sampler is not None:
             sampler.set_epoch(curr_epoch)
@@ -402,6 +412,11 @@ def train_interface(args):
                 best_epoch, best_avg = curr_epoch, avg_all
                 best_avg_class = [dsc[_] for _ in range(1, args.num_classes)]
                 torch.save(model.state_dict(), args.child + '/best_ckp.pth')
+        if args.state_interval and ((curr_epoch + 1) % args.state_interval == 0 or curr_epoch + 1 == args.epoch):
+            rngs = resume.gather_rng_states(device, augmenter, world)          # every rank's generators (a collective)
+            if rank == 0:
+                resume.atomic_save(resume.capture(args, curr_epoch, model, optimizer, (best_avg, best_epoch, best_avg_class),
+                                                  valdice, rngs, world), resume.state_path(args.child, curr_epoch))
     if rank == 0:
         logging.info("The best at epoch: {:d}, ".format(best_epoch)
                      + ", ".join("{}: {:.4f}".format(nm, v) for nm, v in zip(names[1:], best_avg_class))
@@ -412,6 +427,7 @@ def train_interface(args):
 
 def train_main(argv=None):
     args = apply_dataset_preset(parser.parse_args(argv), argv)
+    state_file, resume_state = resume.open_state(parser, args, int(os.environ.get('WORLD_SIZE', '1'))) if args.resume else (None, None)
     if 'LOCAL_RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
     random.seed(args.seed)
@@ -419,14 +435,20 @@ def train_main(argv=None):
     torch.manual_seed(args.seed)
     rank = int(os.environ.get('RANK', '0'))
     sub = DATASETS.get(args.dataset, DATASETS['chaos'])['split_subdir'].format(modality=args.modality)
-    args.child = os.path.join(os.path.join(args.root, sub) if sub else args.root, args.session,
-                              f'{args.session}-{time.strftime("%H-%M-%S-%m%d")}-fold{args.fold}-{args.tag}')
+    if resume_state is not None:
+        args.child = resume.run_dir_of(state_file)          # the run continues in its own directory
+    else:
+        args.child = os.path.join(os.path.join(args.root, sub) if sub else args.root, args.session,
+                                  f'{args.session}-{time.strftime("%H-%M-%S-%m%d")}-fold{args.fold}-{args.tag}')
     if rank == 0:
-        os.makedirs(args.child, exist_ok=False)
-        os.makedirs(os.path.join(args.child, 'ckps'), exist_ok=True)
-        os.makedirs(os.path.join(args.child, 'tb_summary'), exist_ok=True)        # train_chaos.py:184-185
-        if os.path.isfile(sys.argv[0]):
-            shutil.copy(sys.argv[0], os.path.join(args.child, os.path.basename(sys.argv[0])))
+        if resume_state is not None:
+            resume.truncate_scalars(os.path.join(args.child, 'tb_summary', 'scalars.jsonl'), resume_state['epoch'])
+        else:
+            os.makedirs(args.child, exist_ok=False)
+            os.makedirs(os.path.join(args.child, 'ckps'), exist_ok=True)
+            os.makedirs(os.path.join(args.child, 'tb_summary'), exist_ok=True)        # train_chaos.py:184-185
+            if os.path.isfile(sys.argv[0]):
+                shutil.copy(sys.argv[0], os.path.join(args.child, os.path.basename(sys.argv[0])))
         log = logging.getLogger()
         log.setLevel(logging.INFO)
         fh = logging.FileHandler(args.child + "/log.txt")
@@ -434,6 +456,9 @@ def train_main(argv=None):
         log.addHandler(fh)
         log.addHandler(logging.StreamHandler(sys.stdout))
         logging.info(''.join(f'{k}={v}\n' for k, v in args._get_kwargs()))
+        if resume_state is not None:
+            logging.info("resumed from {} (epoch {:03d} done): continuing at epoch {:03d}".format(
+                state_file, resume_state['epoch'], resume_state['epoch'] + 1))
     if not args.synthetic:
         data_root, base = split_dir(args.dataset, args.modality)
         with open(f'{base}/train_fold{args.fold}.txt', 'r') as f:
@@ -442,7 +467,7 @@ def train_main(argv=None):
             val_ls = f.readlines()
         args.train_ls = [(data_root + '/' + p).rstrip('\n') for p in train_ls]
         args.val_ls = [(data_root + '/' + p).rstrip('\n') for p in val_ls]
-    return train_interface(args)
+    return train_interface(args, resume_state)
 
 
 if __name__ == '__main__':

@@ -24,6 +24,8 @@ import time
 import numpy as np
 import torch
 
+from . import resume
+
 parser = argparse.ArgumentParser()
 parser.add_argument('--gpu', type=str, default='1')
 parser.add_argument('--seed', type=int, default=1)
@@ -66,9 +68,10 @@ parser.add_argument('--norm_op', type=str, default='batch', choices=['batch', 'g
                          'per-image statistics, no running state, the same function in train and eval mode (fp32 storage only)')
 parser.add_argument('--norm_groups', type=int, default=8, help='channel groups of --norm_op group; must divide every block width')
 parser.add_argument('--gpu_augment', action='store_true', help='accepted for compatibility: the GPU pipeline is the default')
+resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
 
 
-def train_interface(args):
+def train_interface(args, resume_state=None):
     from .augment import AugConfig, DeviceAugmenter, collate_raw
     from .data import SyntheticPhantoms, collate_by_shape, dataset_class, expand_compact, loader_context
     from .losses.losses import dice_loss_fn, partial_cross_entropy_loss
@@ -117,7 +120,13 @@ def train_interface(args):
         raise ValueError('Unimplemented learning rate decay policy.')
     valdice = np.zeros(args.epoch)
     aug_stream = torch.cuda.Stream() if (augmenter is not None and os.environ.get('PP_AUG_STREAM', '1') != '0') else None
-    for curr_epoch in range(args.epoch):
+    start_epoch = 0
+    if resume_state is not None:
+        best_avg, best_epoch, best_avg_class = resume.restore(resume_state, model, optimizer, valdice)
+        resume.prime_persistent_loaders([train_loader, val_loader])      # see pacingpseudo_amd/train.py
+        resume.set_rng_states(resume_state['rng'][0], device, augmenter)
+        start_epoch = resume_state['epoch'] + 1
+    for curr_epoch in range(start_epoch, args.epoch):
         epoch_tic = time.time()
         optimizer, new_lr = decay[args.lr_decay](optimizer, curr_epoch, args.epoch, args.lr)
         acc = torch.zeros(3, device=device, dtype=torch.float64)        # sum ce*n, sum dice*n, n (read once per epoch)
@@ -183,6 +192,10 @@ def train_interface(args):
             best_epoch, best_avg = curr_epoch, avg_all
             best_avg_class = [dsc[_] for _ in range(1, args.num_classes)]
             torch.save(model.state_dict(), args.child + '/best_ckp.pth')
+        if args.state_interval and ((curr_epoch + 1) % args.state_interval == 0 or curr_epoch + 1 == args.epoch):
+            resume.atomic_save(resume.capture(args, curr_epoch, model, optimizer, (best_avg, best_epoch, best_avg_class), valdice,
+                                              resume.gather_rng_states(device, augmenter, 1), 1),
+                               resume.state_path(args.child, curr_epoch))
     logging.info("The best at epoch: {:d}, ".format(best_epoch)
                  + ", ".join("{}: {:.4f}".format(nm, v) for nm, v in zip(names[1:], best_avg_class))
                  + ", All: {:.4f}".format(best_avg))
@@ -193,19 +206,25 @@ def train_interface(args):
 def train_main(argv=None):
     from .train import DATASETS, apply_dataset_preset, split_dir
     args = apply_dataset_preset(parser.parse_args(argv))
+    # one process: the upper bound has no data-parallel path
+    state_file, resume_state = resume.open_state(parser, args, 1) if args.resume else (None, None)
     if 'LOCAL_RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     sub = DATASETS.get(args.dataset, DATASETS['chaos'])['split_subdir'].format(modality=args.modality)
-    args.child = os.path.join(os.path.join(args.root, sub) if sub else args.root, args.session,
-                              f'{args.session}-{time.strftime("%H-%M-%S-%m%d")}-fold{args.fold}-{args.tag}')
-    os.makedirs(args.child, exist_ok=False)
-    os.makedirs(os.path.join(args.child, 'ckps'), exist_ok=True)
-    os.makedirs(os.path.join(args.child, 'tb_summary'), exist_ok=True)
-    if os.path.isfile(sys.argv[0]):
-        shutil.copy(sys.argv[0], os.path.join(args.child, os.path.basename(sys.argv[0])))
+    if resume_state is not None:
+        args.child = resume.run_dir_of(state_file)          # the run continues in its own directory
+        resume.truncate_scalars(os.path.join(args.child, 'tb_summary', 'scalars.jsonl'), resume_state['epoch'])
+    else:
+        args.child = os.path.join(os.path.join(args.root, sub) if sub else args.root, args.session,
+                                  f'{args.session}-{time.strftime("%H-%M-%S-%m%d")}-fold{args.fold}-{args.tag}')
+        os.makedirs(args.child, exist_ok=False)
+        os.makedirs(os.path.join(args.child, 'ckps'), exist_ok=True)
+        os.makedirs(os.path.join(args.child, 'tb_summary'), exist_ok=True)
+        if os.path.isfile(sys.argv[0]):
+            shutil.copy(sys.argv[0], os.path.join(args.child, os.path.basename(sys.argv[0])))
     log = logging.getLogger()
     log.setLevel(logging.INFO)
     fh = logging.FileHandler(args.child + "/log.txt")
@@ -213,13 +232,16 @@ def train_main(argv=None):
     log.addHandler(fh)
     log.addHandler(logging.StreamHandler(sys.stdout))
     logging.info(''.join(f'{k}={v}\n' for k, v in args._get_kwargs()))
+    if resume_state is not None:
+        logging.info("resumed from {} (epoch {:03d} done): continuing at epoch {:03d}".format(
+            state_file, resume_state['epoch'], resume_state['epoch'] + 1))
     if not args.synthetic:
         data_root, base = split_dir(args.dataset, args.modality)
         with open(f'{base}/train_fold{args.fold}.txt', 'r') as f:
             args.train_ls = [(data_root + '/' + p).rstrip('\n') for p in f.readlines()]
         with open(f'{base}/test_fold{args.fold}.txt', 'r') as f:
             args.val_ls = [(data_root + '/' + p).rstrip('\n') for p in f.readlines()]
-    return train_interface(args)
+    return train_interface(args, resume_state)
 
 
 if __name__ == '__main__':

@@ -1,21 +1,25 @@
 #!/usr/bin/env python
 """Headline benchmark: training images/sec of the PacingPseudo step (256x256, 5 classes) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-           bench.py --gpus N --steps K --warmup W
+           bench.py --gpus N --steps K --warmup W [--full]
 
 Workload = BASELINE.json configs[1]: PacingPseudo full flags (entropy + decoder consistency + aux path + memory),
 synthetic 256x256x1 slices, 5 classes, batch 32 per GPU (weak scaling: global batch 32*N), fp32, random-init
 weights (seed 1).  A "step" is one full iteration of train_chaos.py:263-315: both siamese passes, all five losses,
 backward, gradient all-reduce (N>1) and the Adam update; the batch is resident in HBM before the clock starts.
 BatchNorm runs in train mode (batch statistics + running-stat updates), i.e. the state the reference trains in
-during its first epoch and the more expensive of its two modes; `bn_eval_images_per_sec` reports the eval-mode
-step the reference uses from epoch 1 on (train_chaos.py:370).
+during its first epoch and the more expensive of its two modes.
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events around every launch of the dominant
-matrix-core kernel families during the timed steps; `cpu_baseline` times the CPU oracle
-(the reference path restated on PyTorch-CPU) on this box's host cores on a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: it sets up, warms up, times K steps,
+writes --dump-outputs and prints.  `roofline` is measured live with HIP events around every launch of the dominant
+matrix-core kernel family during the timed steps (chosen in the profiled last warm-up step), so it costs no step of its own.
+`--full` adds everything that does: the per-family and single-stream profiles of untimed steps after the timed region
+(`kernels`, `roofline.matrix_families`, `roofline.single_stream`), the eval-mode BatchNorm step the reference uses from
+epoch 1 on (`bn_eval`, train_chaos.py:370), the mixed-precision, 16-bit storage, hipGraph-replay, Control and
+input-pipeline legs, and `cpu_baseline`, which times the CPU oracle (the reference path restated on PyTorch-CPU) on the
+host's cores on a bounded sample.  --no-bn-eval / --no-cpu-baseline drop legs of a --full run.
 `--dump-outputs DIR` writes what the last timed step computed (inputs and weights are seeded: two builds of the project can
 be compared array for array) as DIR/<name>.npy, float32, at most 64 MB in all.
 """
@@ -43,8 +47,12 @@ def parse():
     ap.add_argument('--batch', type=int, default=32, help='images per GPU')
     ap.add_argument('--size', type=int, default=256)
     ap.add_argument('--session', default='Experiment', choices=['Experiment', 'Control'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-bn-eval', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run the untimed profile steps (per-family and single-stream kernel times), the '
+                         'extra legs (eval-mode BatchNorm, mixed precision, 16-bit storage, graph replay, Control, input pipeline) '
+                         'and the CPU baseline; a plain run only warms up, times --steps steps, dumps and prints the line')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-bn-eval', action='store_true', help='--full without the extra GPU legs (profile steps and CPU baseline stay)')
     ap.add_argument('--cpu-batch', type=int, default=8)
     ap.add_argument('--cpu-steps', type=int, default=5)
     ap.add_argument('--prof-timed', default='dominant', choices=['dominant', 'matrix', 'none'],
@@ -405,14 +413,19 @@ def main():
         dumped = dict(dir=cli.dump_outputs, files=sorted(arrays), bytes=dump_outputs(cli.dump_outputs, arrays))
         del arrays
     last_out.clear()
-    lib.pp_prof_select((1 << 64) - 1)
-    lib.pp_prof_enable(1)
-    for _ in range(2):
-        train_iteration(model, opt, batch, a, ep_main)
-    sync()
-    lib.pp_prof_enable(0)
-    prof_all = prof_collect()
-    if cli.prof_timed != 'matrix':       # families not timed inside the timed region: from the two untimed steps (per-step scale)
+    # the profile steps and legs below run with --full only: steps, models and CPU work of their own, outside the timed region
+    full = cli.full
+    legs = full and not cli.no_bn_eval
+    prof_all = None
+    if full:
+        lib.pp_prof_select((1 << 64) - 1)
+        lib.pp_prof_enable(1)
+        for _ in range(2):
+            train_iteration(model, opt, batch, a, ep_main)
+        sync()
+        lib.pp_prof_enable(0)
+        prof_all = prof_collect()
+    if full and cli.prof_timed != 'matrix':   # families not timed inside the timed region: from the two untimed steps (per-step scale)
         for k in matrix_kinds:
             if not (timed_mask >> PROF_KINDS.index(k)) & 1:
                 v = prof_all[k]
@@ -423,7 +436,7 @@ def main():
     # family's time when it has the chip to itself (`single_stream` in the line; `roofline` itself stays the timed region's).
     from pacingpseudo_amd import engine as _engine
     prof_single = None
-    if _engine.WGRAD_STREAM:
+    if full and _engine.WGRAD_STREAM:
         _engine.WGRAD_STREAM = False
         try:
             train_iteration(model, opt, batch, a, ep_main)
@@ -446,7 +459,7 @@ def main():
     value = B * world * cli.steps / dt
 
     bn_eval = None
-    if not cli.no_bn_eval and not eval_main:
+    if legs and not eval_main:
         # The reference's steady state: BatchNorm with running statistics from epoch 1 on (train_chaos.py:370, never undone) --
         # 399 of its 400 epochs.  Timed like the headline (same batch, whole iteration), then two event-profiled steps for the
         # family times, and two more with the weight gradients back on the main stream (every family alone on the chip).
@@ -509,7 +522,7 @@ def main():
     # direct weight gradients).  Reported
     # beside the headline, never as `value`: it has no 1e-4 parity claim (tests/test_gpu_round3.py states its tolerance).
     mixed = None
-    if not cli.no_bn_eval:
+    if legs:
         model.train()
         lib.pp_set_matrix_products(1)
         try:
@@ -613,7 +626,7 @@ def main():
             del m16, o16
             torch.cuda.empty_cache()
 
-    if world == 1 and not cli.no_bn_eval and cli.session == 'Experiment':      # single process only: a second attached model is not part of the scaling runs
+    if world == 1 and legs and cli.session == 'Experiment':      # single process only: a second attached model is not part of the scaling runs
         storage16 = storage_leg('fp16')
         storage_bf16 = storage_leg('bf16', with_operands=False)
 
@@ -622,7 +635,7 @@ def main():
     # Python host is out of it.  Beside the headline, never `value` (the contract's per-launch HIP events cannot be recorded
     # inside a replayed graph).  Single process only.
     graphed = None
-    if world == 1 and not dist_on and not cli.no_bn_eval:
+    if world == 1 and not dist_on and legs:
         try:
             from pacingpseudo_amd.graph import GraphedStep
             model.train()
@@ -658,7 +671,7 @@ def main():
     # BASELINE.json configs[0] on the GPU: --session=Control (UNet + partial CE, one backbone pass), batch 8 -- the case the
     # cpu_baseline leg times as `control_batch8_images_per_sec`.  Single process only (it is the reference's CPU-runnable case).
     control = None
-    if world == 1 and cli.session == 'Experiment' and not cli.no_bn_eval:
+    if world == 1 and cli.session == 'Experiment' and legs:
         m_ctl = o_ctl = b_ctl = None
         try:                                   # an extra leg must never cost the headline line
             a_ctl = default_args()
@@ -686,7 +699,7 @@ def main():
 
     # the GPU input pipeline, timed on its own: NOT part of `value` (inputs are resident in HBM there)
     aug_rate = None
-    if rank == 0 and not cli.no_bn_eval:
+    if rank == 0 and legs:
         try:                                   # an extra leg must never cost the headline line
             from pacingpseudo_amd.augment import AugConfig, DeviceAugmenter
             aug = DeviceAugmenter(AugConfig(num_classes=a.num_classes, crop_size=(S, S)), device, seed=1)
@@ -721,16 +734,17 @@ def main():
                       'families': single, 'matrix_ms_per_step': round(sm, 3),
                       'matrix_pipe_utilisation_time_weighted': round(sum(r['frac'] * r['ms_per_step'] for r in single.values()) / sm, 4) if sm else None,
                       'all_families_ms_per_step': {k: round(v['ms'] / 2, 3) for k, v in prof_single.items() if v['launches']}}
-        # `roofline` describes the family that was event-timed INSIDE the timed region (the dominant one of the profiled warm-up step)
-        dom = next((r for r in table if r['family'] == dom_kind), table[0]) if cli.prof_timed == 'dominant' else table[0]
+        # `roofline` describes the family that was event-timed INSIDE the timed region (the dominant one of the profiled warm-up step);
+        # a plain run without such a family (--warmup 0, --prof-timed none) has none to describe
+        dom = (next((r for r in table if r['family'] == dom_kind), table[0]) if cli.prof_timed == 'dominant' else table[0]) if table else None
         mfma_ms = sum(r['ms_per_step'] for r in table)
         # time-weighted utilisation of the matrix pipes over all of these launches
         util = sum(r['frac'] * r['ms_per_step'] for r in table) / mfma_ms if mfma_ms > 0 else 0.0
-        # all families, from the two untimed steps that follow the timed region (every launch bracketed by events)
+        # all families, from the two untimed steps that follow the timed region (every launch bracketed by events; --full)
         kernels = {k: dict(launches_per_step=v['launches'] / 2, ms_per_step=round(v['ms'] / 2, 3),
                            tflops=round(v['flops'] / (v['ms'] * 1e-3) / 1e12, 2) if v['ms'] > 0 and v['flops'] else None,
                            alg_gbps=round(v['bytes'] / (v['ms'] * 1e-3) / 1e9, 1) if v['ms'] > 0 else None)
-                   for k, v in prof_all.items() if v['launches']}
+                   for k, v in prof_all.items() if v['launches']} if prof_all is not None else None
         line = {
             'metric': 'training images/sec (256x256, 5-class)', 'value': round(value, 2), 'unit': 'images/sec',
             'n_gpus': world, 'steps': cli.steps, 'warmup': cli.warmup, 'ms_per_step': round(ms_per_step, 3),
@@ -758,11 +772,12 @@ def main():
                 'matrix_pipe_utilisation_time_weighted': round(util, 4),
                 'timed_by_events_in_timed_region': ([dom_kind] if cli.prof_timed == 'dominant' and dom_kind else
                                                     (list(matrix_kinds) if cli.prof_timed == 'matrix' else [])),
-                'other_families_from': 'two untimed steps after the timed region (HIP events around every launch)',
+                'other_families_from': ('two untimed steps after the timed region (HIP events around every launch)' if full else
+                                        'not measured: a plain run lists the families timed inside the timed region (--full: all)'),
                 'streams': ('2: weight gradients run beside the data-gradient / BatchNorm chain, event times include the co-running '
-                            'kernels' if prof_single is not None else '1'),
+                            'kernels' if _engine.WGRAD_STREAM else '1'),
                 'single_stream': single,
-            },
+            } if dom else None,
             'whole_step': {'algorithmic_tflops': round(FLOP_PER_IMAGE_FULL * value / world / 1e12, 2) if a.do_aux_path else None,
                            'algorithmic_over_f32_peak': round(FLOP_PER_IMAGE_FULL * value / world / 1e12 / PEAK_F32_MFMA_TFLOPS, 4) if a.do_aux_path else None,
                            'frac_of_hbm_roofline': round(BYTES_PER_IMAGE_FULL * value / world / 8.0e12, 4) if a.do_aux_path else None},
@@ -788,7 +803,7 @@ def main():
         }
         if dumped:
             line['dump_outputs'] = dumped
-        if world == 1 and not cli.no_cpu_baseline:
+        if world == 1 and full and not cli.no_cpu_baseline:
             try:
                 line['cpu_baseline'] = cpu_baseline(a, cli.cpu_batch, S, cli.cpu_steps)
                 line['gpu_over_cpu'] = round(value / line['cpu_baseline']['value'], 1)

@@ -9,7 +9,7 @@ for r in $(seq 1 "$ROUNDS"); do
   for spec in "$@"; do
     label=${spec%%=*}; rest=${spec#*=}; dir=${rest%%:*}; envs=""
     [ "$rest" != "$dir" ] && envs=$(echo "${rest#*:}" | tr ',' ' ')
-    line=$(cd "$dir" && env $envs timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-bn-eval 2>/dev/null | grep '^{' | tail -1)
+    line=$(cd "$dir" && env $envs timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-bn-eval 2>/dev/null | grep '^{' | tail -1)
     echo "$line" | python3 -c '
 import sys, json
 d = json.loads(sys.stdin.read())

@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 for kv in "$@"; do export "$kv"; done
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt -- python3 $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-bn-eval > "$OUT/kt.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt -- python3 $ROOT/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-bn-eval > "$OUT/kt.log" 2>&1
 cp "$(find "$OUT/kt" -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_kernel_stats.csv"
 rm -rf "$OUT/kt"
 python3 - "$OUT/${TAG}_kernel_stats.csv" <<'P'

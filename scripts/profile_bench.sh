@@ -17,7 +17,7 @@ EXTRA="$*"
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/${TAG}_prof
 mkdir -p "$OUT"
-BENCH="$ROOT/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-bn-eval $EXTRA"
+BENCH="$ROOT/bench.py --steps 3 --warmup 2 --full --no-cpu-baseline --no-bn-eval $EXTRA"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt -- python3 $BENCH > "$OUT/kt.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o fetch -- python3 $BENCH > "$OUT/fetch.log" 2>&1

@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/${TAG}_one_stream
 mkdir -p "$OUT"
 export PP_WGRAD_STREAM=0 PP_AUX_SIDE=0
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt -- python3 "$ROOT/bench.py" --steps 3 --warmup 2 --no-cpu-baseline --no-bn-eval > "$OUT/kt.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt -- python3 "$ROOT/bench.py" --steps 3 --warmup 2 --full --no-cpu-baseline --no-bn-eval > "$OUT/kt.log" 2>&1
 cd "$ROOT"
 cp "$(find "$OUT/kt" -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_one_stream_kernel_stats.csv"
 grep -h '^{' "$OUT/kt.log" > "$OUT/${TAG}_one_stream_bench_line_under_rocprof.json" || true

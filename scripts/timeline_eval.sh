@@ -5,6 +5,6 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d "$OUT/kt" -o kt -- python3 $ROOT/bench.py --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/kt.log" 2>&1
+rocprofv3 --kernel-trace --output-format csv -d "$OUT/kt" -o kt -- python3 $ROOT/bench.py --steps 3 --warmup 2 --full --no-cpu-baseline > "$OUT/kt.log" 2>&1
 python3 $ROOT/scripts/timeline.py "$OUT/kt" "$OUT/timeline.tsv" $WHICH
 rm -rf "$OUT/kt"

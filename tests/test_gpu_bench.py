@@ -14,13 +14,19 @@ NAMES = {'segmentation_logits', 'loss_pce', 'loss_ent', 'loss_cr', 'segmentation
          'loss_memory', 'loss', 'parameters', 'gradients', 'buffers'}
 
 
-def _bench(out_dir, steps, warmup):
+def _line(*args):
+    """Run bench.py on one GPU at batch 2, 64x64 and return its JSON line."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'PP_FORCE_DIST', 'PP_SHARE_GPU')}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup),
-                        '--batch', '2', '--size', '64', '--no-cpu-baseline', '--no-bn-eval', '--dump-outputs', str(out_dir)],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--batch', '2', '--size', '64'] + list(args),
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def _bench(out_dir, steps, warmup):
+    return _line('--steps', str(steps), '--warmup', str(warmup), '--no-cpu-baseline', '--no-bn-eval', '--dump-outputs', str(out_dir))
 
 
 def test_bench_steps_and_dump_outputs(tmp_path):
@@ -38,3 +44,26 @@ def test_bench_steps_and_dump_outputs(tmp_path):
     loss = float(np.load(tmp_path / 'a' / 'loss.npy'))
     assert abs(loss - ja['final_loss']) <= 1e-5 * max(1.0, abs(loss))
     assert np.load(tmp_path / 'a' / 'segmentation_logits.npy').shape == (2, 5, 64, 64)
+
+
+LEGS = ('bn_eval', 'mixed_precision', 'storage_fp16', 'storage_bf16', 'graph_replay', 'control')
+
+
+def test_bench_plain_run_is_the_headline_and_full_adds_the_rest():
+    """A plain run times the same steps as --full and stops there: no untimed profile steps (`kernels`, single-stream table,
+    families outside the timed region), no extra legs, no CPU baseline.  --full still runs every leg."""
+    plain = _line('--steps', '2', '--warmup', '1')
+    full = _line('--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline')
+    for j in (plain, full):
+        assert j['metric'] == 'training images/sec (256x256, 5-class)' and j['unit'] == 'images/sec' and j['higher_is_better'] is True
+        assert j['value'] > 0 and j['ms_per_step'] > 0 and j['dtype'].startswith('f32') and len(j['step_ms']['all']) == 2
+    assert abs(plain['final_loss'] - full['final_loss']) <= 1e-5 * max(1.0, abs(full['final_loss']))
+    roof = plain['roofline']
+    assert [r['family'] for r in roof['matrix_families']] == roof['timed_by_events_in_timed_region'] and roof['achieved'] > 0
+    assert plain['kernels'] is None and roof['single_stream'] is None and 'cpu_baseline' not in plain
+    assert all(plain[k] is None for k in LEGS) and plain['input_pipeline_images_per_sec'] is None
+    assert full['kernels'] and full['roofline']['single_stream']
+    assert {r['family'] for r in roof['matrix_families']} <= {r['family'] for r in full['roofline']['matrix_families']}
+    for k in LEGS:
+        assert full[k] and 'error' not in full[k], (k, full[k])
+    assert full['input_pipeline_images_per_sec'] > 0 and 'cpu_baseline' not in full

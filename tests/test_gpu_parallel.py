@@ -198,6 +198,29 @@ def test_bench_contract_with_two_ranks(tmp_path):
     assert 'cpu_baseline' not in j                             # rank 0 at N = 1 only
 
 
+def test_bench_full_with_two_ranks():
+    """`--full` with two ranks: the profile steps and the legs with collectives (eval-mode BatchNorm, mixed precision) beside
+    the rank-0-only input-pipeline leg finish on every rank (the r02 hang was a collective inside a rank-0-only block); the
+    single-process legs stay out.  Same one-GPU rehearsal transport as above."""
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ, PP_DIST_BACKEND='gloo', PP_SHARE_GPU='1', PP_HANG_DUMP='240')
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
+                        '--master-addr', '127.0.0.1', '--master-port', str(_free_port()), os.path.join(root, 'bench.py'),
+                        '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2', '--size', '64', '--full'],
+                       env=env, cwd=root, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j['n_gpus'] == 2 and j['collective_backend'] == 'gloo' and j['kernels']
+    assert j['bn_eval']['images_per_sec'] > 0 and j['mixed_precision']['images_per_sec'] > 0
+    assert j['input_pipeline_images_per_sec'] > 0
+    assert j['storage_fp16'] is None and j['graph_replay'] is None and j['control'] is None and 'cpu_baseline' not in j
+
+
 def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with NO launcher around it (the way the driver calls `--gpus 1`): bench.py must start the
     two ranks itself (a torch.distributed.run child, before the parent touches the GPU), relay rank 0's single JSON line and

@@ -327,6 +327,18 @@ def test_bench_refuses_zero_steps():
     assert r.returncode == 2 and '--steps' in r.stderr and '{' not in r.stdout
 
 
+def test_bench_full_is_off_by_default(monkeypatch):
+    """A plain bench.py run leaves the profile steps, extra legs and CPU baseline out; --full asks for them."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1'])
+    cli = bench.parse()
+    assert cli.full is False and (cli.steps, cli.warmup) == (3, 1)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-cpu-baseline'])
+    cli = bench.parse()
+    assert cli.full is True and cli.no_cpu_baseline and not cli.no_bn_eval
+
+
 def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
     """bench.py --dump-outputs: one float32 (float64 kept) .npy per array; an array larger than DUMP_SAMPLE is cut to DUMP_SAMPLE
     elements at the same seeded positions in every run; more than DUMP_LIMIT bytes in all is refused."""

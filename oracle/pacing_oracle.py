@@ -240,6 +240,8 @@ def conv_layer(sd, prefix: str, x: Tensor, dil: int, training: bool, stride: int
     w = sd[prefix + '.conv.weight']
     if CONV_OPERAND_ROUND is not None:         # mixed-precision check: the device rounds both conv operands to fp16
         x, w = CONV_OPERAND_ROUND(x, prefix), CONV_OPERAND_ROUND(w, prefix)
+    if STORAGE is not None:
+        return _conv_layer_stored(sd, prefix, x, w, dil, training, stride)
     z = F.conv2d(x, w, sd[prefix + '.conv.bias'], stride, dil, dil)
     y = leaky_relu_choice(_bn(sd, prefix + '.norm_op', z, training), prefix)
     if TAP is not None and y.requires_grad:
@@ -250,6 +252,133 @@ def conv_layer(sd, prefix: str, x: Tensor, dil: int, training: bool, stride: int
 
 # hook for tests of the fp16-operand mode (`--precision fp16`): callable(tensor, layer prefix) -> tensor, or None
 CONV_OPERAND_ROUND = None
+# hook for tests of the 16-bit storage mode (`--storage fp16 | bf16`): a StorageRounding, or None (then every result is unchanged)
+STORAGE = None
+
+
+class _ValueRound(torch.autograd.Function):
+    """Forward: the value a 16-bit store leaves (round to nearest even from the fp32 value); backward: straight through."""
+    @staticmethod
+    def forward(ctx, x, dtype):
+        return x.float().to(dtype).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+class _GradRound(torch.autograd.Function):
+    """Forward: identity; backward: the gradient as a 16-bit store of the loss-scaled gradient leaves it (g * S rounded, / S)."""
+    @staticmethod
+    def forward(ctx, x, dtype, scale):
+        ctx.dtype, ctx.scale = dtype, scale
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g * ctx.scale).float().to(ctx.dtype).to(g.dtype) / ctx.scale, None, None
+
+
+class StorageRounding:
+    """Where the 16-bit storage mode rounds, restated for the oracle.  `sites` maps a site name to what the device stores there:
+
+      'input'                          'F' (the packed input images)
+      '<layer>:z', '<layer>:y'         'F' value stored (z: BatchNorm normalises the stored value; its statistics come from the
+                                       unrounded z, as the device takes them from the fp32 accumulators), 'B' gradient stored
+      '<layer>:split'                  input channels of the first split-K launch (its half-sum is stored before the second
+                                       launch adds to it), 0: none
+      'backbone.enc_block<k>.pooling'  'B' (the pooled tensor is exact: a maximum of stored values)
+      'backbone.dec_block<k>.up'       'F' / 'B' of the up-sampled half of the concatenation
+      'backbone.dec_block<k>.cat'      'B' (the concatenation's gradient is one stored tensor)
+      'backbone.enc_block<k>'          the uses of an encoder stage output in the order the engine adds their gradients into
+                                       one 16-bit buffer (names 'dec', 'aux', 'next'): the total is
+                                       round(...round(round(g_1) + g_2)... + g_n); 'fused': the uses' own stores are added in
+                                       fp32 and the sum is not stored
+
+    Values are rounded from fp32 (an fp64 oracle rounds fp64 -> fp32 -> 16 bits, never fp64 -> 16 bits directly); gradients
+    are multiplied by the power-of-two loss scale before and divided after the rounding (both exact).  A site the oracle
+    reaches without an entry raises KeyError, and `seen` lists the sites it reached."""
+
+    def __init__(self, dtype, loss_scale: float, sites: dict):
+        self.dtype, self.scale, self.sites = dtype, float(loss_scale), sites
+        self.seen = set()
+        self._chains = {}
+
+    def _flags(self, site):
+        if site not in self.sites:
+            raise KeyError(f'storage rounding: no entry for site {site!r}')
+        self.seen.add(site)
+        return self.sites[site]
+
+    def value(self, t: Tensor) -> Tensor:
+        return _ValueRound.apply(t, self.dtype)
+
+    def grad(self, t: Tensor) -> Tensor:
+        return _GradRound.apply(t, self.dtype, self.scale)
+
+    def act(self, t: Tensor, site: str) -> Tensor:
+        f = self._flags(site)
+        if 'F' in f:
+            t = self.value(t)
+        if 'B' in f:
+            t = self.grad(t)
+        return t
+
+    def z(self, z: Tensor, prefix: str):
+        """(z for the statistics, z the normalisation is applied to)."""
+        f = self._flags(prefix + ':z')
+        if 'B' in f:
+            z = self.grad(z)
+        return z, (self.value(z) if 'F' in f else z)
+
+    def split(self, prefix: str) -> int:
+        return int(self._flags(prefix + ':split'))
+
+    def use(self, t: Tensor, site: str, use: str) -> Tensor:
+        order = self._flags(site)
+        if order == 'fused':
+            return t
+        ch = self._chains.get(site)
+        if ch is None or ch[0] is not t:
+            nodes, cur = {}, t
+            for u in reversed(order):            # the use added last hangs off the outermost rounding
+                cur = self.grad(cur)
+                nodes[u] = cur
+            ch = self._chains[site] = (t, nodes)
+        return ch[1][use]
+
+
+def _bn_stored(sd, prefix: str, z: Tensor, za: Tensor, training: bool) -> Tensor:
+    """BatchNorm2d of the 16-bit storage mode: train-mode statistics (and the running-stat update) from z, normalisation
+    applied to za, the value the device stored."""
+    if not training:
+        return F.batch_norm(za, sd[prefix + '.running_mean'], sd[prefix + '.running_var'], sd[prefix + '.weight'],
+                            sd[prefix + '.bias'], False, BN_MOMENTUM, BN_EPS)
+    sd[prefix + '.num_batches_tracked'] += 1
+    mean, var = z.mean((0, 2, 3)), z.var((0, 2, 3), unbiased=False)
+    n = z.numel() // z.shape[1]
+    with torch.no_grad():
+        sd[prefix + '.running_mean'].mul_(1 - BN_MOMENTUM).add_(mean.detach(), alpha=BN_MOMENTUM)
+        sd[prefix + '.running_var'].mul_(1 - BN_MOMENTUM).add_(var.detach() * (n / max(n - 1, 1)), alpha=BN_MOMENTUM)
+    scale = sd[prefix + '.weight'] * torch.rsqrt(var + BN_EPS)
+    return (za - mean[None, :, None, None]) * scale[None, :, None, None] + sd[prefix + '.bias'][None, :, None, None]
+
+
+def _conv_layer_stored(sd, prefix: str, x: Tensor, w: Tensor, dil: int, training: bool, stride: int) -> Tensor:
+    """conv_layer under STORAGE: the split-K half-sum, z and y rounded where the device stores them."""
+    b = sd[prefix + '.conv.bias']
+    c1 = STORAGE.split(prefix)
+    if c1:
+        z = (STORAGE.value(F.conv2d(x[:, :c1], w[:, :c1], b, stride, dil, dil))
+             + F.conv2d(x[:, c1:], w[:, c1:], None, stride, dil, dil))
+    else:
+        z = F.conv2d(x, w, b, stride, dil, dil)
+    z, za = STORAGE.z(z, prefix)
+    y = STORAGE.act(leaky_relu_choice(_bn_stored(sd, prefix + '.norm_op', z, za, training), prefix), prefix + ':y')
+    if TAP is not None and y.requires_grad:
+        z.retain_grad(); y.retain_grad()
+        TAP.setdefault(prefix, []).append((z, y))
+    return y
 
 
 def double_conv(sd, prefix: str, x: Tensor, dil: int, training: bool, stride1: int = 1) -> Tensor:
@@ -261,14 +390,19 @@ def double_conv(sd, prefix: str, x: Tensor, dil: int, training: bool, stride1: i
 def unet_forward(sd, x: Tensor, args, training: bool) -> Dict[str, Tensor]:
     """UNet.forward (models/unet.py:62-98), max-pool / bilinear variant only."""
     plan = stage_plan(args)
+    st = STORAGE
     enc = []
-    h = x
+    h = x if st is None else st.act(x, 'input')
     for k, e in enumerate(plan['enc'], start=1):
+        if st is not None and k > 1:
+            h = st.use(h, f'backbone.enc_block{k - 1}', 'next')
         if e['pool']:
             h = max_pool_choice(h, f'backbone.enc_block{k}.pooling')    # models/unet.py:109,124-125
+            if st is not None:
+                h = st.act(h, f'backbone.enc_block{k}.pooling')
         h = double_conv(sd, f'backbone.enc_block{k}.conv_block', h, e['dil'], training, e['stride'])
         enc.append(h)
-    d = enc[5]
+    d = enc[5] if st is None else st.use(enc[5], 'backbone.enc_block6', 'dec')
     decs = {}
     for k in (5, 4, 3, 2, 1):
         up = plan['dec'][k]['up']
@@ -277,7 +411,12 @@ def unet_forward(sd, x: Tensor, args, training: bool) -> Dict[str, Tensor]:
             u = F.conv_transpose2d(d, sd[f'backbone.dec_block{k}.up_samp.weight'], None, up)
         else:
             u = F.interpolate(d, scale_factor=up, mode='bilinear', align_corners=True)
-        d = double_conv(sd, f'backbone.dec_block{k}.conv_block', torch.cat((u, enc[k - 1]), 1), 1, training)
+        if st is None:
+            cat = torch.cat((u, enc[k - 1]), 1)
+        else:
+            cat = st.act(torch.cat((st.act(u, f'backbone.dec_block{k}.up'), st.use(enc[k - 1], f'backbone.enc_block{k}', 'dec')), 1),
+                         f'backbone.dec_block{k}.cat')
+        d = double_conv(sd, f'backbone.dec_block{k}.conv_block', cat, 1, training)
         decs[k] = d
     logits = F.conv2d(d, sd['backbone.final_conv.weight'], sd['backbone.final_conv.bias'])   # :60,75
     ep = {f'encoder/stage{k}': enc[k - 1] for k in range(1, 7)}
@@ -337,10 +476,19 @@ def _dropout2d(x: Tensor, p: float, training: bool, key: str) -> Tensor:
 
 def aux_forward(sd, end_points, scribble: Tensor, step, args, training: bool) -> Dict[str, Tensor]:
     """AuxPath.forward (models/aux_path_memory.py:46-66)."""
-    feat = torch.cat([end_points[s] for s in args.feat_stage], 1)
+    st = STORAGE
+    if st is None:
+        feat = torch.cat([end_points[s] for s in args.feat_stage], 1)
+    else:
+        feat = torch.cat([st.use(end_points[s], 'backbone.enc_block' + s.rsplit('stage', 1)[1], 'aux') for s in args.feat_stage], 1)
     feat = _dropout2d(feat, args.aux_drop_prob, training, 'input')
     z = F.conv2d(feat, sd['aux_path.layer_bottleneck.1.weight'], sd['aux_path.layer_bottleneck.1.bias'], 1, 1)
-    aux_features = leaky_relu_choice(_bn(sd, 'aux_path.layer_bottleneck.2', z, training), 'aux_path.layer_bottleneck')
+    if st is None:
+        aux_features = leaky_relu_choice(_bn(sd, 'aux_path.layer_bottleneck.2', z, training), 'aux_path.layer_bottleneck')
+    else:
+        z, za = st.z(z, 'aux_path.layer_bottleneck')
+        aux_features = st.act(leaky_relu_choice(_bn_stored(sd, 'aux_path.layer_bottleneck.2', z, za, training),
+                                                'aux_path.layer_bottleneck'), 'aux_path.layer_bottleneck:y')
     lo = F.conv2d(_dropout2d(aux_features, args.aux_drop_prob, training, 'features'), sd['aux_path.fc_cls.1.weight'])
     logits_aux = F.interpolate(lo, size=scribble.shape[-2:], mode='bilinear', align_corners=True)
     out = {'logits_aux_cls': logits_aux, 'aux_targets': scribble.argmax(1).long(), 'aux_features': aux_features}

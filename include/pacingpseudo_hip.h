@@ -442,6 +442,7 @@ int pp_convtranspose_bwd_weight(const float* dout, int ld_dout, int Cout, const 
                                 int W, float* dw, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- 1x1 heads: final_conv (models/unet.py:60) and aux fc_cls (aux_path_memory.py:32), NHWC -> NCHW logits ---- */
+/* 1 <= K <= 32 classes (an argument error names the bound), C <= 128 and a multiple of 4 */
 int pp_conv1x1_nhwc_to_nchw_fwd(const float* x, int ld_x, int C, const float* w, const float* bias, float* logits,
                                 int K, int N, int HW, void* stream);
 /* ... with a lazy x (the features of dec_block1 kept as raw convolution output in train-mode BN) */
@@ -457,6 +458,7 @@ int pp_conv1x1_nchw_to_nhwc_bwd_lazy(const float* dlogits, const float* x, int l
                                 int accumulate_param_grads, void* workspace, size_t workspace_bytes, const pp_lazy_in* lazy_x, void* stream);
 
 /* ---- losses (losses/losses.py; models/consistency_reglur_memory.py:31-97) ------------------------------ */
+/* every loss entry point with a class count K takes 1 <= K <= 32 (pp_argmax_channels and pp_hd95_surface_distances: any K) */
 /* torch.argmax(x, dim=1) on (N,C,HW) fp32 -> int64, first maximum wins (bit-exact pseudo-label masks) */
 int pp_argmax_channels(const float* x, int N, int C, int HW, int64_t* out, void* stream);
 /* sums[6] (double): pCE sum, #labelled, entropy sum, entropy denominator, consistency sum, consistency denominator.

@@ -209,7 +209,7 @@ for _n in H16_ENTRIES:
 _H16_SET = frozenset(H16_ENTRIES) | {'pp_memory_update'}
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
-MIN_LIB_VERSION = 601      # include/pacingpseudo_hip.h with the GroupNorm entry points (pp_runtime.cpp: PP_VERSION)
+MIN_LIB_VERSION = 602      # include/pacingpseudo_hip.h with K <= 32 in the loss and head kernels (pp_runtime.cpp: PP_VERSION)
 PROF_KINDS = ('conv_igemm', 'conv_wgrad', 'bn', 'spatial', 'loss', 'optim', 'misc', 'wino_gemm', 'wino_wgrad',
               'wino_xform', 'conv_f16x3', 'wino_gemm_f16x3', 'wino_wgrad_f16x3', 'conv_wgrad_f16x3', 'conv_halo_f16x3')
 

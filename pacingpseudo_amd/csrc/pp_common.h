@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <string.h>
+#include <type_traits>
 #include "pacingpseudo_hip.h"      // the public C ABI: every extern "C" definition is checked against its declaration
 
 #define PP_WAVE 64
@@ -103,6 +104,19 @@ int pp_bn_apply_launch(const act_t* z, int ld_z, const float* scale, const float
 PP_NS_END
 
 static inline int pp_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// ---- class bound of the per-pixel loss and head kernels ----
+// Those kernels hold one pixel's K classes in arrays of a compile-time bound MK.  K <= 8 (the reference's data sets: 2, 4, 5)
+// runs the MK = 8 instantiations it always ran; 9 .. 16 and 17 .. 32 run instantiations at MK = 16 and 32, so the register
+// allocation and LDS of the K <= 8 kernels do not grow with the wider range.  f(std::integral_constant<int, MK>) launches.
+#define PP_MAXK_SMALL 8
+#define PP_MAXK 32
+template <class F>
+static inline void pp_by_class_bound(int K, F&& f) {
+  if (K <= PP_MAXK_SMALL) f(std::integral_constant<int, PP_MAXK_SMALL>());
+  else if (K <= 16) f(std::integral_constant<int, 16>());
+  else f(std::integral_constant<int, PP_MAXK>());
+}
 
 // ---- "lazy" activations: BatchNorm + LeakyReLU applied by the CONSUMER while it loads (round 4) ----
 // In train mode the batch statistics exist only after the whole convolution output z has been written, so the normalised

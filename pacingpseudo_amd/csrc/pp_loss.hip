@@ -1,4 +1,4 @@
-// Loss-side kernels of the PacingPseudo step (all HBM/latency-bound, NCHW logits with K <= 8 classes):
+// Loss-side kernels of the PacingPseudo step (all HBM/latency-bound, NCHW logits with K <= 32 classes):
 //   * channel arg-max (scribble one-hot -> int64 target, prediction masks)  consistency_reglur_memory.py:31
 //   * fused partial-CE + entropy-minimisation + decoder-consistency sums     losses/losses.py:9-116
 //   * their gradient wrt the weak and strong logits
@@ -8,10 +8,12 @@
 //                                                                            aux_path_memory.py:61,68-116
 //   * validation Dice counts                                                 utils/metrics.py:7-34
 // Reductions are two-stage (per-block partials, fixed-order double finalize): deterministic, no float atomics.
+// The per-pixel kernels are templates on the class bound MK (pp_by_class_bound, pp_common.h): K <= 8 runs the MK = LS_MAXK
+// instantiations (and the four-pixel v4 forms for K in {2, 4, 5}), 9 <= K <= 16 and 17 <= K <= 32 the MK = 16 and 32 ones.
 #include "pp_common.h"
 
 #define LS_THREADS 256
-#define LS_MAXK 8
+#define LS_MAXK PP_MAXK_SMALL    // class bound of the K <= 8 kernels; the wide instantiations go to PP_MAXK
 
 // ---------------------------------------------------------------- arg-max over channels (first maximum wins)
 __global__ void argmax_channels_kernel(const float* __restrict__ x, int N, int C, int HW, long long* __restrict__ out) {
@@ -43,36 +45,40 @@ extern "C" int pp_argmax_channels(const float* x, int N, int C, int HW, int64_t*
 }
 
 // ---------------------------------------------------------------- softmax helpers
-struct SM { float p[LS_MAXK]; float l[LS_MAXK]; };   // softmax and log-softmax of one pixel
+template <int MK>
+struct SM { float p[MK]; float l[MK]; };             // softmax and log-softmax of one pixel
 // softmax / log-softmax of one pixel from its K logits (the one expression every loss kernel uses: the scalar and the
 // four-pixels-per-thread forms of a kernel give the same bits)
-__device__ __forceinline__ void softmax_vals(const float (&v)[LS_MAXK], int K, SM& o) {
+template <int MK>
+__device__ __forceinline__ void softmax_vals(const float (&v)[MK], int K, SM<MK>& o) {
   float m = -INFINITY;
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k)
+  for (int k = 0; k < MK; ++k)
     if (k < K) m = fmaxf(m, v[k]);
   float s = 0.f;
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k)
+  for (int k = 0; k < MK; ++k)
     if (k < K) { o.p[k] = expf(v[k] - m); s += o.p[k]; }
   const float ls = logf(s), inv = 1.f / s;
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k)
+  for (int k = 0; k < MK; ++k)
     if (k < K) { o.l[k] = v[k] - m - ls; o.p[k] *= inv; }
 }
-__device__ __forceinline__ void pixel_softmax(const float* __restrict__ z, size_t stride, int K, SM& o) {
-  float v[LS_MAXK];
+template <int MK>
+__device__ __forceinline__ void pixel_softmax(const float* __restrict__ z, size_t stride, int K, SM<MK>& o) {
+  float v[MK];
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k)
+  for (int k = 0; k < MK; ++k)
     if (k < K) v[k] = z[(size_t)k * stride];
   softmax_vals(v, K, o);
 }
 
 // consistency variants (train_chaos.py:138): 0 none, 1 ce_loss, 2 l1_loss, 3 l2_loss, 4 kl_loss
-__device__ __forceinline__ float cr_value(const SM& w, const SM& s, int K, int variant) {
+template <int MK>
+__device__ __forceinline__ float cr_value(const SM<MK>& w, const SM<MK>& s, int K, int variant) {
   float L = 0.f;
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k)
+  for (int k = 0; k < MK; ++k)
     if (k < K) {
       if (variant == 1) L -= w.p[k] * s.l[k];
       else if (variant == 2) L += fabsf(s.p[k] - w.p[k]);
@@ -84,14 +90,15 @@ __device__ __forceinline__ float cr_value(const SM& w, const SM& s, int K, int v
 
 // sums[0]=pce_sum [1]=n_labelled [2]=ent_sum [3]=ent_den [4]=cr_sum [5]=cr_den   (double)
 struct SegAcc { float pce, n, ent, cr, m; };
-__device__ __forceinline__ void seg_fwd_pixel(const float (&vw)[LS_MAXK], const float (&vs)[LS_MAXK], long long t, float m, int K,
+template <int MK>
+__device__ __forceinline__ void seg_fwd_pixel(const float (&vw)[MK], const float (&vs)[MK], long long t, float m, int K,
                                               int ignore_index, int do_ent, int variant, SegAcc& a) {
-  SM w;
+  SM<MK> w;
   softmax_vals(vw, K, w);
   if (t != ignore_index && t >= 0 && t < K) {
     float lt = 0.f;
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k) if (k == (int)t) lt = w.l[k];
+    for (int k = 0; k < MK; ++k) if (k == (int)t) lt = w.l[k];
     a.pce -= lt;
     a.n += 1.f;
   }
@@ -99,11 +106,11 @@ __device__ __forceinline__ void seg_fwd_pixel(const float (&vw)[LS_MAXK], const 
   if (do_ent) {
     float h = 0.f;
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k) if (k < K) h -= w.p[k] * w.l[k];
+    for (int k = 0; k < MK; ++k) if (k < K) h -= w.p[k] * w.l[k];
     a.ent += h * m;
   }
   if (variant) {
-    SM s;
+    SM<MK> s;
     softmax_vals(vs, K, s);
     a.cr += cr_value(w, s, K, variant) * m;
   }
@@ -118,6 +125,7 @@ __device__ __forceinline__ void seg_acc_store(const SegAcc& a, float* sh, double
   }
 }
 
+template <int MK>
 __global__ __launch_bounds__(LS_THREADS) void seg_losses_partial_kernel(
     const float* __restrict__ zw, const float* __restrict__ zs, const long long* __restrict__ target,
     const float* __restrict__ mask, int N, int K, int HW, int ignore_index, int do_ent, int variant,
@@ -129,9 +137,9 @@ __global__ __launch_bounds__(LS_THREADS) void seg_losses_partial_kernel(
     // (32-bit division where the pixel index fits: the 64-bit form is ~150 VALU instructions of these kernels' ~870 per pixel)
     const int n = p < 0x7fffffffLL ? (int)((unsigned)p / (unsigned)HW) : (int)(p / HW), hw = (int)(p - (long long)n * HW);
     const size_t off = (size_t)n * K * HW + hw;
-    float vw[LS_MAXK], vs[LS_MAXK];
+    float vw[MK], vs[MK];
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k) {
+    for (int k = 0; k < MK; ++k) {
       vw[k] = k < K ? zw[off + (size_t)k * HW] : 0.f;
       vs[k] = (k < K && variant) ? zs[off + (size_t)k * HW] : 0.f;
     }
@@ -224,7 +232,7 @@ extern "C" int pp_seg_losses_fwd(const float* logits_w, const float* logits_s, c
                                  void* stream) {
   hipStream_t s = (hipStream_t)stream;
   PP_CHECK_ARG(logits_w && target && sums && workspace, "seg_losses_fwd: null pointer");
-  PP_CHECK_ARG(K >= 1 && K <= LS_MAXK && cr_variant >= 0 && cr_variant <= 4, "seg_losses_fwd: K=%d variant=%d", K, cr_variant);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && cr_variant >= 0 && cr_variant <= 4, "seg_losses_fwd: K=%d (1..%d) variant=%d", K, PP_MAXK, cr_variant);
   PP_CHECK_ARG(cr_variant == 0 || logits_s, "seg_losses_fwd: consistency loss needs the strong logits");
   if (workspace_bytes < pp_seg_losses_workspace(N, HW)) {
     pp_set_error("seg_losses_fwd: workspace too small");
@@ -242,8 +250,10 @@ extern "C" int pp_seg_losses_fwd(const float* logits_w, const float* logits_s, c
   else if (v4 && K == 4) SEG_FWD_V4(4);
   else if (v4 && K == 2) SEG_FWD_V4(2);
   else
-    hipLaunchKernelGGL(seg_losses_partial_kernel, dim3(blocks), dim3(LS_THREADS), 0, s, logits_w, logits_s,
-                       (const long long*)target, valid_mask, N, K, HW, ignore_index, do_ent, cr_variant, (double*)workspace);
+    pp_by_class_bound(K, [&](auto mk) {
+      hipLaunchKernelGGL(seg_losses_partial_kernel<decltype(mk)::value>, dim3(blocks), dim3(LS_THREADS), 0, s, logits_w, logits_s,
+                         (const long long*)target, valid_mask, N, K, HW, ignore_index, do_ent, cr_variant, (double*)workspace);
+    });
 #undef SEG_FWD_V4
   hipLaunchKernelGGL(seg_losses_reduce_kernel, dim3(1), dim3(64), 0, s, (const double*)workspace, blocks,
                      valid_mask ? 1 : 0, cr_variant, den_ent, den_cr, sums);
@@ -272,33 +282,34 @@ __device__ __forceinline__ SegG seg_bwd_scales(const double* __restrict__ sums, 
   g.gc = (variant && g_cr) ? (float)((double)(*g_cr * grad_scale) / dc) : 0.f;
   return g;
 }
-__device__ __forceinline__ void seg_bwd_pixel(const float (&vw)[LS_MAXK], const float (&vs)[LS_MAXK], long long t, float m, int K,
+template <int MK>
+__device__ __forceinline__ void seg_bwd_pixel(const float (&vw)[MK], const float (&vs)[MK], long long t, float m, int K,
                                               int ignore_index, int do_ent, int variant, int detach_weak, const SegG& g,
-                                              float (&dw)[LS_MAXK], float (&ds)[LS_MAXK]) {
-  SM w;
+                                              float (&dw)[MK], float (&ds)[MK]) {
+  SM<MK> w;
   softmax_vals(vw, K, w);
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k) { dw[k] = 0.f; ds[k] = 0.f; }
+  for (int k = 0; k < MK; ++k) { dw[k] = 0.f; ds[k] = 0.f; }
   if (t != ignore_index && t >= 0 && t < K) {
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k)
+    for (int k = 0; k < MK; ++k)
       if (k < K) dw[k] = g.gp * (w.p[k] - (k == (int)t ? 1.f : 0.f));
   }
   if (do_ent) {
     float h = 0.f;
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k) if (k < K) h -= w.p[k] * w.l[k];
+    for (int k = 0; k < MK; ++k) if (k < K) h -= w.p[k] * w.l[k];
     const float f = g.ge * m;
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k) if (k < K) dw[k] -= f * w.p[k] * (w.l[k] + h);
+    for (int k = 0; k < MK; ++k) if (k < K) dw[k] -= f * w.p[k] * (w.l[k] + h);
   }
   if (variant) {
-    SM s;
+    SM<MK> s;
     softmax_vals(vs, K, s);
-    float u[LS_MAXK], v[LS_MAXK];
+    float u[MK], v[MK];
     float qu = 0.f, sv = 0.f;
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k)
+    for (int k = 0; k < MK; ++k)
       if (k < K) {
         if (variant == 1) { u[k] = -s.l[k]; v[k] = 0.f; }
         else if (variant == 2) {
@@ -318,7 +329,7 @@ __device__ __forceinline__ void seg_bwd_pixel(const float (&vw)[LS_MAXK], const 
     // (the reference, losses/losses.py:54-59) is the closed form too.
     const bool closed = variant == 1 || variant == 4;
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k)
+    for (int k = 0; k < MK; ++k)
       if (k < K) {
         if (weak_grad) dw[k] += f * w.p[k] * (u[k] - qu);
         ds[k] = closed ? f * (s.p[k] - w.p[k]) : f * s.p[k] * (v[k] - sv);
@@ -326,6 +337,7 @@ __device__ __forceinline__ void seg_bwd_pixel(const float (&vw)[LS_MAXK], const 
   }
 }
 
+template <int MK>
 __global__ __launch_bounds__(LS_THREADS) void seg_losses_bwd_kernel(
     const float* __restrict__ zw, const float* __restrict__ zs, const long long* __restrict__ target,
     const float* __restrict__ mask, int N, int K, int HW, int ignore_index, int do_ent, int variant, int detach_weak,
@@ -337,15 +349,15 @@ __global__ __launch_bounds__(LS_THREADS) void seg_losses_bwd_kernel(
     // (32-bit division where the pixel index fits: the 64-bit form is ~150 VALU instructions of these kernels' ~870 per pixel)
     const int n = p < 0x7fffffffLL ? (int)((unsigned)p / (unsigned)HW) : (int)(p / HW), hw = (int)(p - (long long)n * HW);
     const size_t off = (size_t)n * K * HW + hw;
-    float vw[LS_MAXK], vs[LS_MAXK], dw[LS_MAXK], ds[LS_MAXK];
+    float vw[MK], vs[MK], dw[MK], ds[MK];
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k) {
+    for (int k = 0; k < MK; ++k) {
       vw[k] = k < K ? zw[off + (size_t)k * HW] : 0.f;
       vs[k] = (k < K && variant) ? zs[off + (size_t)k * HW] : 0.f;
     }
     seg_bwd_pixel(vw, vs, target[p], mask ? mask[p] : 1.f, K, ignore_index, do_ent, variant, detach_weak, g, dw, ds);
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k)
+    for (int k = 0; k < MK; ++k)
       if (k < K) {
         if (variant) dzs[off + (size_t)k * HW] = ds[k];
         dzw[off + (size_t)k * HW] = dw[k];
@@ -401,7 +413,7 @@ extern "C" int pp_seg_losses_bwd(const float* logits_w, const float* logits_s, c
                                  float* dlogits_s, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   PP_CHECK_ARG(logits_w && target && sums && dlogits_w, "seg_losses_bwd: null pointer");
-  PP_CHECK_ARG(K >= 1 && K <= LS_MAXK && cr_variant >= 0 && cr_variant <= 4, "seg_losses_bwd: K=%d variant=%d", K, cr_variant);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && cr_variant >= 0 && cr_variant <= 4, "seg_losses_bwd: K=%d (1..%d) variant=%d", K, PP_MAXK, cr_variant);
   PP_CHECK_ARG(cr_variant == 0 || (logits_s && dlogits_s), "seg_losses_bwd: consistency loss needs the strong logits");
   const double P = (double)N * HW;
   pp_prof_begin(PP_K_LOSS, 0.0, P * (16.0 * K + 12.0), s);
@@ -413,9 +425,11 @@ extern "C" int pp_seg_losses_bwd(const float* logits_w, const float* logits_s, c
   else if (v4 && K == 4) SEG_BWD_V4(4);
   else if (v4 && K == 2) SEG_BWD_V4(2);
   else
-    hipLaunchKernelGGL(seg_losses_bwd_kernel, dim3(ls_blocks((long long)N * HW)), dim3(LS_THREADS), 0, s, logits_w,
-                       logits_s, (const long long*)target, valid_mask, N, K, HW, ignore_index, do_ent, cr_variant,
-                       detach_weak, sums, valid_mask ? 1 : 0, g_pce, g_ent, g_cr, grad_scale, dlogits_w, dlogits_s);
+    pp_by_class_bound(K, [&](auto mk) {
+      hipLaunchKernelGGL(seg_losses_bwd_kernel<decltype(mk)::value>, dim3(ls_blocks((long long)N * HW)), dim3(LS_THREADS), 0, s, logits_w,
+                         logits_s, (const long long*)target, valid_mask, N, K, HW, ignore_index, do_ent, cr_variant,
+                         detach_weak, sums, valid_mask ? 1 : 0, g_pce, g_ent, g_cr, grad_scale, dlogits_w, dlogits_s);
+    });
 #undef SEG_BWD_V4
   pp_prof_end(s);
   return pp_launch_status("seg_losses_bwd");
@@ -434,6 +448,7 @@ static inline float lin_scale_l(int in_size, int out_size) {
   return out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
 }
 
+template <int MK>
 __global__ __launch_bounds__(LS_THREADS) void aux_pce_fwd_kernel(const float* __restrict__ lo, int N, int K, int h,
                                                                  int w, int H, int W, float sy, float sx,
                                                                  const long long* __restrict__ target,
@@ -450,10 +465,10 @@ __global__ __launch_bounds__(LS_THREADS) void aux_pce_fwd_kernel(const float* __
     float wy0, wy1, wx0, wx1;
     lin_coeff_l(y, sy, h, y0, y1, wy0, wy1);
     lin_coeff_l(x, sx, w, x0, x1, wx0, wx1);
-    float v[LS_MAXK];
+    float v[MK];
     float m = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k)
+    for (int k = 0; k < MK; ++k)
       if (k < K) {
         const float* b = lo + ((size_t)n * K + k) * hw_lo;
         v[k] = wy0 * (wx0 * b[y0 * w + x0] + wx1 * b[y0 * w + x1]) + wy1 * (wx0 * b[y1 * w + x0] + wx1 * b[y1 * w + x1]);
@@ -464,7 +479,7 @@ __global__ __launch_bounds__(LS_THREADS) void aux_pce_fwd_kernel(const float* __
     if (t != ignore_index && t >= 0 && t < K) {
       float s = 0.f, vt = 0.f;
 #pragma unroll
-      for (int k = 0; k < LS_MAXK; ++k)
+      for (int k = 0; k < MK; ++k)
         if (k < K) { s += expf(v[k] - m); if (k == (int)t) vt = v[k]; }
       a_pce -= vt - m - logf(s);
       a_n += 1.f;
@@ -488,15 +503,17 @@ extern "C" int pp_aux_pce_fwd(const float* lo, int N, int K, int h, int w, int H
                               size_t workspace_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   PP_CHECK_ARG(lo && target && logits_up && sums && workspace, "aux_pce_fwd: null pointer");
-  PP_CHECK_ARG(K >= 1 && K <= LS_MAXK, "aux_pce_fwd: K=%d", K);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK, "aux_pce_fwd: K=%d (1..%d)", K, PP_MAXK);
   const int blocks = ls_blocks((long long)N * H * W, 1024);
   if (workspace_bytes < (size_t)blocks * 2 * sizeof(double)) {
     pp_set_error("aux_pce_fwd: workspace too small");
     return PP_ERR_WORKSPACE;
   }
   pp_prof_begin(PP_K_LOSS, 0.0, (double)N * H * W * (4.0 * K + 8.0), s);
-  hipLaunchKernelGGL(aux_pce_fwd_kernel, dim3(blocks), dim3(LS_THREADS), 0, s, lo, N, K, h, w, H, W, lin_scale_l(h, H),
-                     lin_scale_l(w, W), (const long long*)target, ignore_index, logits_up, (double*)workspace);
+  pp_by_class_bound(K, [&](auto mk) {
+    hipLaunchKernelGGL(aux_pce_fwd_kernel<decltype(mk)::value>, dim3(blocks), dim3(LS_THREADS), 0, s, lo, N, K, h, w, H, W, lin_scale_l(h, H),
+                       lin_scale_l(w, W), (const long long*)target, ignore_index, logits_up, (double*)workspace);
+  });
   hipLaunchKernelGGL(pair_reduce_kernel, dim3(1), dim3(64), 0, s, (const double*)workspace, blocks, sums);
   pp_prof_end(s);
   return pp_launch_status("aux_pce_fwd");
@@ -520,6 +537,7 @@ __device__ __forceinline__ void touch_range_l(int i, float scale, int out_size, 
 // the xor butterfly: a fixed order.
 #define AUXB_SLOTS 8
 #define AUXB_LIST (64 * AUXB_SLOTS)        // labelled positions of one phase-1 round: at most every slot of every lane
+template <int MK>
 __global__ __launch_bounds__(256) void aux_pce_bwd_kernel(const float* __restrict__ up, const long long* __restrict__ target,
                                                           int ignore_index, const float* __restrict__ g_aux,
                                                           float grad_scale, const double* __restrict__ sums,
@@ -540,9 +558,9 @@ __global__ __launch_bounds__(256) void aux_pce_bwd_kernel(const float* __restric
   const int wx = xhi - xlo + 1, cnt = (yhi - ylo + 1) * wx;
   const long long* tgt = target + (size_t)n * HW;
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
-  float acc[LS_MAXK];
+  float acc[MK];
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k) acc[k] = 0.f;
+  for (int k = 0; k < MK; ++k) acc[k] = 0.f;
   for (int base = 0; base < cnt; base += 64 * AUXB_SLOTS) {
     long long t[AUXB_SLOTS];
     int pos[AUXB_SLOTS];
@@ -577,15 +595,15 @@ __global__ __launch_bounds__(256) void aux_pce_bwd_kernel(const float* __restric
       lin_coeff_l(x, sx, w, x0, x1, wx0, wx1);
       const float wgt = ((y0 == yl ? wy0 : 0.f) + (y1 == yl ? wy1 : 0.f)) * ((x0 == xl ? wx0 : 0.f) + (x1 == xl ? wx1 : 0.f));
       if (wgt == 0.f) continue;
-      SM sm;
+      SM<MK> sm;
       pixel_softmax(up + (size_t)n * K * HW + p, HW, K, sm);
 #pragma unroll
-      for (int k = 0; k < LS_MAXK; ++k)
+      for (int k = 0; k < MK; ++k)
         if (k < K) acc[k] += wgt * (sm.p[k] - (k == tt ? 1.f : 0.f));
     }
   }
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k)
+  for (int k = 0; k < MK; ++k)
     if (k < K) {
       const float v = pp_wave_sum(acc[k]);
       if (lane == 0) dlo[((size_t)n * K + k) * h * w + yl * w + xl] = v * gs;
@@ -597,11 +615,13 @@ extern "C" int pp_aux_pce_bwd(const float* logits_up, const int64_t* target, int
                               int W, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   PP_CHECK_ARG(logits_up && target && sums && dlo, "aux_pce_bwd: null pointer");
-  PP_CHECK_ARG(K >= 1 && K <= LS_MAXK, "aux_pce_bwd: K=%d", K);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK, "aux_pce_bwd: K=%d (1..%d)", K, PP_MAXK);
   pp_prof_begin(PP_K_LOSS, 0.0, (double)N * H * W * 8.0, s);
-  hipLaunchKernelGGL(aux_pce_bwd_kernel, dim3(pp_cdiv((long long)N * h * w * 64, 256)), dim3(256), 0, s, logits_up,
-                     (const long long*)target, ignore_index, g_aux, grad_scale, sums, dlo, N, K, h, w, H, W,
-                     lin_scale_l(h, H), lin_scale_l(w, W));
+  pp_by_class_bound(K, [&](auto mk) {
+    hipLaunchKernelGGL(aux_pce_bwd_kernel<decltype(mk)::value>, dim3(pp_cdiv((long long)N * h * w * 64, 256)), dim3(256), 0, s, logits_up,
+                       (const long long*)target, ignore_index, g_aux, grad_scale, sums, dlo, N, K, h, w, H, W,
+                       lin_scale_l(h, H), lin_scale_l(w, W));
+  });
   pp_prof_end(s);
   return pp_launch_status("aux_pce_bwd");
 }
@@ -814,11 +834,12 @@ extern "C" int pp_memory_update_bf16(const void* feat0, int ld, int hid, int h, 
 
 // bank classification: logits[r][k] = <bank[r], wfc[k]>, loss = mean_r CE(logits[r], r)   (aux_path_memory.py:61,
 // consistency_reglur_memory.py:94-97).  mode 0: write loss;  mode 1: dwfc (+)= g * dloss/dwfc.
+template <int MK>
 __global__ __launch_bounds__(64) void memory_ce_kernel(const float* __restrict__ bank, const float* __restrict__ wfc,
                                                        int K, int hid, float* loss, const float* g, float grad_scale,
                                                        float* dwfc, int accumulate, int mode) {
-  __shared__ float lg[LS_MAXK][LS_MAXK];
-  __shared__ float dl[LS_MAXK][LS_MAXK];
+  __shared__ float lg[MK][MK];
+  __shared__ float dl[MK][MK];
   const int lane = threadIdx.x;
   for (int r = 0; r < K; ++r)
     for (int k = 0; k < K; ++k) {
@@ -853,30 +874,37 @@ __global__ __launch_bounds__(64) void memory_ce_kernel(const float* __restrict__
 }
 
 extern "C" int pp_memory_ce_fwd(const float* bank, const float* wfc, int K, int hid, float* loss, void* stream) {
-  PP_CHECK_ARG(bank && wfc && loss && K >= 1 && K <= LS_MAXK, "memory_ce_fwd: bad arguments");
-  hipLaunchKernelGGL(memory_ce_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, bank, wfc, K, hid, loss, nullptr, 0.f,
-                     nullptr, 0, 0);
+  PP_CHECK_ARG(bank && wfc && loss, "memory_ce_fwd: bad arguments");
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK, "memory_ce_fwd: K=%d (1..%d)", K, PP_MAXK);
+  pp_by_class_bound(K, [&](auto mk) {
+    hipLaunchKernelGGL(memory_ce_kernel<decltype(mk)::value>, dim3(1), dim3(64), 0, (hipStream_t)stream, bank, wfc, K, hid, loss, nullptr,
+                       0.f, nullptr, 0, 0);
+  });
   return pp_launch_status("memory_ce_fwd");
 }
 
 extern "C" int pp_memory_ce_bwd(const float* bank, const float* wfc, int K, int hid, const float* g, float grad_scale,
                                 float* dwfc, int accumulate, void* stream) {
-  PP_CHECK_ARG(bank && wfc && dwfc && K >= 1 && K <= LS_MAXK, "memory_ce_bwd: bad arguments");
-  hipLaunchKernelGGL(memory_ce_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, bank, wfc, K, hid, nullptr, g,
-                     grad_scale, dwfc, accumulate, 1);
+  PP_CHECK_ARG(bank && wfc && dwfc, "memory_ce_bwd: bad arguments");
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK, "memory_ce_bwd: K=%d (1..%d)", K, PP_MAXK);
+  pp_by_class_bound(K, [&](auto mk) {
+    hipLaunchKernelGGL(memory_ce_kernel<decltype(mk)::value>, dim3(1), dim3(64), 0, (hipStream_t)stream, bank, wfc, K, hid, nullptr, g,
+                       grad_scale, dwfc, accumulate, 1);
+  });
   return pp_launch_status("memory_ce_bwd");
 }
 
 // ---------------------------------------------------------------- validation Dice counts (utils/metrics.py:7-34)
 // counts[n][k] = { sum pred_k * target_k, sum pred_k, sum target_k } with pred = one-hot(argmax_k logits)
+template <int MK>
 __global__ __launch_bounds__(LS_THREADS) void dice_counts_kernel(const float* __restrict__ logits,
                                                                  const float* __restrict__ label, int K, int HW,
                                                                  float* __restrict__ counts) {
   __shared__ float sh[16];
   const int n = blockIdx.x;
-  float inter[LS_MAXK], ps[LS_MAXK], ts[LS_MAXK];
+  float inter[MK], ps[MK], ts[MK];
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k) inter[k] = ps[k] = ts[k] = 0.f;
+  for (int k = 0; k < MK; ++k) inter[k] = ps[k] = ts[k] = 0.f;
   const float* lz = logits + (size_t)n * K * HW;
   const float* lb = label + (size_t)n * K * HW;
   for (int p = threadIdx.x; p < HW; p += blockDim.x) {
@@ -884,7 +912,7 @@ __global__ __launch_bounds__(LS_THREADS) void dice_counts_kernel(const float* __
     int a = 0;
     for (int k = 1; k < K; ++k) { const float v = lz[(size_t)k * HW + p]; if (v > m) { m = v; a = k; } }
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k)
+    for (int k = 0; k < MK; ++k)
       if (k < K) {
         const float t = lb[(size_t)k * HW + p];
         const float pr = (k == a) ? 1.f : 0.f;
@@ -892,7 +920,7 @@ __global__ __launch_bounds__(LS_THREADS) void dice_counts_kernel(const float* __
       }
   }
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k)
+  for (int k = 0; k < MK; ++k)
     if (k < K) {
       const float a = pp_block_sum(inter[k], sh), b = pp_block_sum(ps[k], sh), c = pp_block_sum(ts[k], sh);
       if (threadIdx.x == 0) {
@@ -904,9 +932,12 @@ __global__ __launch_bounds__(LS_THREADS) void dice_counts_kernel(const float* __
 
 extern "C" int pp_dice_counts(const float* logits, const float* label_onehot, int N, int K, int HW, float* counts,
                               void* stream) {
-  PP_CHECK_ARG(logits && label_onehot && counts && K >= 1 && K <= LS_MAXK, "dice_counts: bad arguments");
-  hipLaunchKernelGGL(dice_counts_kernel, dim3(N), dim3(LS_THREADS), 0, (hipStream_t)stream, logits, label_onehot, K, HW,
-                     counts);
+  PP_CHECK_ARG(logits && label_onehot && counts && K >= 1, "dice_counts: bad arguments");
+  PP_CHECK_ARG(K <= PP_MAXK, "dice_counts: K=%d (1..%d)", K, PP_MAXK);
+  pp_by_class_bound(K, [&](auto mk) {
+    hipLaunchKernelGGL(dice_counts_kernel<decltype(mk)::value>, dim3(N), dim3(LS_THREADS), 0, (hipStream_t)stream, logits, label_onehot,
+                       K, HW, counts);
+  });
   return pp_launch_status("dice_counts");
 }
 
@@ -916,28 +947,29 @@ extern "C" int pp_dice_counts(const float* logits, const float* label_onehot, in
 // the partials into sums[n][K][3] = {sum p t, sum p, sum t} and writes the loss.
 // Backward: dL/dp_k = -g/(N K) * (2 t_k down - up) / down^2 per pixel, then through the soft-max.
 #define DICE_BLOCKS 64
+template <int MK>
 __global__ __launch_bounds__(LS_THREADS) void dice_loss_partial_kernel(const float* __restrict__ logits,
                                                                        const float* __restrict__ label, int K, int HW,
                                                                        double* __restrict__ partial) {
   __shared__ float sh[16];
   const int n = blockIdx.y;
-  float inter[LS_MAXK], ps[LS_MAXK], ts[LS_MAXK];
+  float inter[MK], ps[MK], ts[MK];
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k) inter[k] = ps[k] = ts[k] = 0.f;
+  for (int k = 0; k < MK; ++k) inter[k] = ps[k] = ts[k] = 0.f;
   const float* lz = logits + (size_t)n * K * HW;
   const float* lb = label + (size_t)n * K * HW;
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-    SM w;
+    SM<MK> w;
     pixel_softmax(lz + p, HW, K, w);
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k)
+    for (int k = 0; k < MK; ++k)
       if (k < K) {
         const float t = lb[(size_t)k * HW + p];
         inter[k] += w.p[k] * t; ps[k] += w.p[k]; ts[k] += t;
       }
   }
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k)
+  for (int k = 0; k < MK; ++k)
     if (k < K) {
       const float a = pp_block_sum(inter[k], sh), b = pp_block_sum(ps[k], sh), c = pp_block_sum(ts[k], sh);
       if (threadIdx.x == 0) {
@@ -972,6 +1004,7 @@ __global__ __launch_bounds__(64) void dice_loss_finalize_kernel(const double* __
   }
 }
 
+template <int MK>
 __global__ __launch_bounds__(LS_THREADS) void dice_loss_bwd_kernel(const float* __restrict__ logits,
                                                                    const float* __restrict__ label, int N, int K, int HW,
                                                                    const double* __restrict__ sums, const float* __restrict__ g,
@@ -979,29 +1012,43 @@ __global__ __launch_bounds__(LS_THREADS) void dice_loss_bwd_kernel(const float* 
                                                                    int accumulate) {
   const int n = blockIdx.y;
   const float gs = (g ? *g : 1.f) * grad_scale / (float)(N * K);
-  float A[LS_MAXK], B[LS_MAXK];                  // dL/dp_k = A_k t_k + B_k
+  // dL/dp_k = A_k t_k + B_k.  The wide forms (MK > LS_MAXK) keep A and B in LDS: in registers they took the MK = 32 form to
+  // 228 VGPRs + 32 AGPRs, one wave per SIMD.  Same values either way.
+  constexpr bool ab_lds = MK > LS_MAXK;
+  __shared__ float ab_sh[ab_lds ? 2 * MK : 1];
+  float A[ab_lds ? 1 : MK], B[ab_lds ? 1 : MK];
 #pragma unroll
-  for (int k = 0; k < LS_MAXK; ++k) {
-    A[k] = 0.f; B[k] = 0.f;
+  for (int k = 0; k < MK; ++k) {
+    float a = 0.f, b = 0.f;
     if (k < K) {
       const double* s = sums + ((size_t)n * K + k) * 3;
       const double up = 2.0 * s[0], down = s[1] + s[2] + 1e-5;
-      A[k] = (float)(-2.0 * gs / down);
-      B[k] = (float)(gs * up / (down * down));
+      a = (float)(-2.0 * gs / down);
+      b = (float)(gs * up / (down * down));
+    }
+    if constexpr (ab_lds) {
+      if (threadIdx.x == 0) { ab_sh[k] = a; ab_sh[MK + k] = b; }
+    } else {
+      A[k] = a; B[k] = b;
     }
   }
+  if constexpr (ab_lds) __syncthreads();
   const float* lz = logits + (size_t)n * K * HW;
   const float* lb = label + (size_t)n * K * HW;
   float* dz = dlogits + (size_t)n * K * HW;
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-    SM w;
+    SM<MK> w;
     pixel_softmax(lz + p, HW, K, w);
-    float u[LS_MAXK], pu = 0.f;
+    float u[MK], pu = 0.f;
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k)
-      if (k < K) { u[k] = A[k] * lb[(size_t)k * HW + p] + B[k]; pu += w.p[k] * u[k]; }
+    for (int k = 0; k < MK; ++k)
+      if (k < K) {
+        const float ak = ab_lds ? ab_sh[k] : A[ab_lds ? 0 : k], bk = ab_lds ? ab_sh[MK + k] : B[ab_lds ? 0 : k];
+        u[k] = ak * lb[(size_t)k * HW + p] + bk;
+        pu += w.p[k] * u[k];
+      }
 #pragma unroll
-    for (int k = 0; k < LS_MAXK; ++k)
+    for (int k = 0; k < MK; ++k)
       if (k < K) {
         const float v = w.p[k] * (u[k] - pu);
         float* o = dz + (size_t)k * HW + p;
@@ -1015,8 +1062,9 @@ extern "C" size_t pp_dice_loss_workspace(int N, int K) { return (size_t)N * DICE
 extern "C" int pp_dice_loss_fwd(const float* logits, const float* label_onehot, int N, int K, int HW, double* sums,
                                 float* loss, void* workspace, size_t workspace_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  PP_CHECK_ARG(logits && label_onehot && sums && loss && workspace && N >= 1 && K >= 1 && K <= LS_MAXK && HW >= 1,
+  PP_CHECK_ARG(logits && label_onehot && sums && loss && workspace && N >= 1 && K >= 1 && HW >= 1,
                "dice_loss_fwd: bad arguments");
+  PP_CHECK_ARG(K <= PP_MAXK, "dice_loss_fwd: K=%d (1..%d)", K, PP_MAXK);
   if (workspace_bytes < pp_dice_loss_workspace(N, K)) {
     pp_set_error("dice_loss_fwd: workspace too small");
     return PP_ERR_WORKSPACE;
@@ -1025,7 +1073,10 @@ extern "C" int pp_dice_loss_fwd(const float* logits, const float* label_onehot, 
   int bx = pp_cdiv(HW, LS_THREADS);
   if (bx > DICE_BLOCKS) bx = DICE_BLOCKS;
   pp_prof_begin(PP_K_LOSS, 0.0, 8.0 * (double)N * K * HW, s);
-  hipLaunchKernelGGL(dice_loss_partial_kernel, dim3(bx, N), dim3(LS_THREADS), 0, s, logits, label_onehot, K, HW, partial);
+  pp_by_class_bound(K, [&](auto mk) {
+    hipLaunchKernelGGL(dice_loss_partial_kernel<decltype(mk)::value>, dim3(bx, N), dim3(LS_THREADS), 0, s, logits, label_onehot, K, HW,
+                       partial);
+  });
   hipLaunchKernelGGL(dice_loss_finalize_kernel, dim3(1), dim3(64), 0, s, partial, bx, N, K, sums, loss);
   pp_prof_end(s);
   return pp_launch_status("dice_loss_fwd");
@@ -1034,12 +1085,15 @@ extern "C" int pp_dice_loss_fwd(const float* logits, const float* label_onehot, 
 extern "C" int pp_dice_loss_bwd(const float* logits, const float* label_onehot, int N, int K, int HW, const double* sums,
                                 const float* g, float grad_scale, float* dlogits, int accumulate, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  PP_CHECK_ARG(logits && label_onehot && sums && dlogits && N >= 1 && K >= 1 && K <= LS_MAXK, "dice_loss_bwd: bad arguments");
+  PP_CHECK_ARG(logits && label_onehot && sums && dlogits && N >= 1 && K >= 1, "dice_loss_bwd: bad arguments");
+  PP_CHECK_ARG(K <= PP_MAXK, "dice_loss_bwd: K=%d (1..%d)", K, PP_MAXK);
   int bx = pp_cdiv(HW, LS_THREADS);
   if (bx > 256) bx = 256;
   pp_prof_begin(PP_K_LOSS, 0.0, 12.0 * (double)N * K * HW, s);
-  hipLaunchKernelGGL(dice_loss_bwd_kernel, dim3(bx, N), dim3(LS_THREADS), 0, s, logits, label_onehot, N, K, HW, sums, g,
-                     grad_scale, dlogits, accumulate);
+  pp_by_class_bound(K, [&](auto mk) {
+    hipLaunchKernelGGL(dice_loss_bwd_kernel<decltype(mk)::value>, dim3(bx, N), dim3(LS_THREADS), 0, s, logits, label_onehot, N, K, HW,
+                       sums, g, grad_scale, dlogits, accumulate);
+  });
   pp_prof_end(s);
   return pp_launch_status("dice_loss_bwd");
 }

@@ -498,21 +498,21 @@ extern "C" int PP_FN(pp_channel_scale)(const pp_act* x, int ld_x, pp_act* y, int
 }
 
 // ---------------------------------------------------------------- 1x1 head: NHWC features -> NCHW logits
-#define HEAD_MAXK 8
-#define HEAD_MAXC 128
+#define HEAD_MAXK PP_MAXK_SMALL   // class bound of the K <= 8 head kernels; 9 <= K <= 32 run the MK = 16 / 32 instantiations
+#define HEAD_MAXC 128             //   (pp_by_class_bound, pp_common.h)
 // A block stages a tile of TP pixels x C channels in LDS with coalesced float4 loads (a pixel's channels are
 // contiguous), then every thread reduces one pixel's row against the K weight rows (row stride C + 1 floats: the
 // threads of a wave walk different banks) and writes its K logits to the NCHW planes (coalesced across pixels).
 // The first version had each thread stream its own pixel straight from global memory: lanes 128 B apart, 2.7x the
 // algorithmic HBM traffic (r01 PMC profile).
-template <int TP, bool LAZY>
+template <int TP, bool LAZY, int MK>
 __global__ __launch_bounds__(TP) void conv1x1_fwd_kernel(const act_t* __restrict__ x, int ld_x, int C,
                                                          const float* __restrict__ w, const float* __restrict__ bias,
                                                          float* __restrict__ logits, int K, int N, int HW, PpLazy lz) {
   extern __shared__ float sm[];
   float* ws = sm;                          // [K][C]
   float* bs = ws + K * C;                  // [K]
-  float* xs = bs + HEAD_MAXK;              // [TP][C + 1]
+  float* xs = bs + MK;              // [TP][C + 1]
   for (int i = threadIdx.x; i < K * C; i += TP) ws[i] = w[i];
   if (threadIdx.x < K) bs[threadIdx.x] = bias ? bias[threadIdx.x] : 0.f;
   const long long P = (long long)N * HW;
@@ -534,19 +534,19 @@ __global__ __launch_bounds__(TP) void conv1x1_fwd_kernel(const act_t* __restrict
     __syncthreads();
     const long long p = p0 + threadIdx.x;
     if (p < P) {
-      float acc[HEAD_MAXK];
+      float acc[MK];
 #pragma unroll
-      for (int k = 0; k < HEAD_MAXK; ++k) acc[k] = 0.f;
+      for (int k = 0; k < MK; ++k) acc[k] = 0.f;
       const float* xp = xs + threadIdx.x * ldx;
       for (int c = 0; c < C; ++c) {
         const float v = xp[c];
 #pragma unroll
-        for (int k = 0; k < HEAD_MAXK; ++k)
+        for (int k = 0; k < MK; ++k)
           if (k < K) acc[k] += v * ws[k * C + c];
       }
       const int n = (int)(p / HW), hw = (int)(p % HW);
 #pragma unroll
-      for (int k = 0; k < HEAD_MAXK; ++k)
+      for (int k = 0; k < MK; ++k)
         if (k < K) logits[((size_t)n * K + k) * HW + hw] = acc[k] + bs[k];
     }
   }
@@ -556,7 +556,7 @@ __global__ __launch_bounds__(TP) void conv1x1_fwd_kernel(const act_t* __restrict
 // per pixel, the K partial dot products are summed over the quad lanes of the pixel by a butterfly, and lane `quad == k`
 // stores class k (a wave stores all K planes of its 64 / c4n pixels with one instruction).  No LDS tile, no barrier.
 // The LDS-tiled kernel above ran the 32 -> 5 head at 256^2 x 64 images at 2.4 TB/s of its 0.62 GB.
-template <bool LAZY>
+template <bool LAZY, int MK>
 __global__ __launch_bounds__(SP_THREADS) void conv1x1_fwd_stream_kernel(const act_t* __restrict__ x, int ld_x, int C,
                                                                         const float* __restrict__ w, const float* __restrict__ bias,
                                                                         float* __restrict__ logits, int K, int N, int HW,
@@ -566,9 +566,9 @@ __global__ __launch_bounds__(SP_THREADS) void conv1x1_fwd_stream_kernel(const ac
   const int P = N * HW;
   const int p_lo = blockIdx.x * pix_per_block;
   const int p_hi = min(P, p_lo + pix_per_block);
-  float wr[HEAD_MAXK][4];
+  float wr[MK][4];
 #pragma unroll
-  for (int k = 0; k < HEAD_MAXK; ++k)
+  for (int k = 0; k < MK; ++k)
 #pragma unroll
     for (int j = 0; j < 4; ++j) wr[k][j] = k < K ? w[k * C + cq * 4 + j] : 0.f;
   const float bv = (bias && cq < K) ? bias[cq] : 0.f;
@@ -578,7 +578,7 @@ __global__ __launch_bounds__(SP_THREADS) void conv1x1_fwd_stream_kernel(const ac
     const float4 xv = xv1[0];
     float mine = 0.f;
 #pragma unroll
-    for (int k = 0; k < HEAD_MAXK; ++k)
+    for (int k = 0; k < MK; ++k)
       if (k < K) {
         float t = xv.x * wr[k][0] + xv.y * wr[k][1] + xv.z * wr[k][2] + xv.w * wr[k][3];
         t = pp_group_sum(t, c4n);
@@ -605,38 +605,41 @@ __global__ __launch_bounds__(SP_THREADS) void conv1x1_fwd_stream_kernel(const ac
 static int conv1x1_fwd_impl(const pp_act* x, int ld_x, int C, const float* w, const float* bias,
                             float* logits, int K, int N, int HW, PpLazy lz, hipStream_t s) {
   PP_CHECK_ARG(x && w && logits, "conv1x1_fwd: null pointer");
-  PP_CHECK_ARG(K >= 1 && K <= HEAD_MAXK && C % 4 == 0 && C <= HEAD_MAXC && ld_x % 4 == 0 && ld_x >= C,
-               "conv1x1_fwd: K=%d (<=8) C=%d (<=128, %%4) ld=%d", K, C, ld_x);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && C % 4 == 0 && C <= HEAD_MAXC && ld_x % 4 == 0 && ld_x >= C,
+               "conv1x1_fwd: K=%d (1..%d) C=%d (<=128, %%4) ld=%d", K, PP_MAXK, C, ld_x);
   PP_CHECK_ARG(((uintptr_t)x & PP_ACT_ALIGN) == 0, "conv1x1_fwd: x must be 16-byte aligned");
   const long long P = (long long)N * HW;
   pp_prof_begin(PP_K_SPATIAL, 2.0 * P * K * C, 4.0 * P * (C + K), s);
   const int tp = C > 64 ? 128 : 256;
-  const size_t lds = (size_t)(K * C + HEAD_MAXK + tp * (C + 1)) * sizeof(float);
   int blocks = pp_cdiv(P, tp);
   if (blocks > SP_MAX_BLOCKS) blocks = SP_MAX_BLOCKS;
-  {   // once per (kernel, device): pp_max_lds
-    pp_max_lds(reinterpret_cast<const void*>(conv1x1_fwd_kernel<128, false>), (int)((HEAD_MAXK * HEAD_MAXC + HEAD_MAXK + 128 * (HEAD_MAXC + 1)) * sizeof(float)));
-    pp_max_lds(reinterpret_cast<const void*>(conv1x1_fwd_kernel<256, false>), (int)((HEAD_MAXK * 64 + HEAD_MAXK + 256 * 65) * sizeof(float)));
-    pp_max_lds(reinterpret_cast<const void*>(conv1x1_fwd_kernel<128, true>), (int)((HEAD_MAXK * HEAD_MAXC + HEAD_MAXK + 128 * (HEAD_MAXC + 1)) * sizeof(float)));
-    pp_max_lds(reinterpret_cast<const void*>(conv1x1_fwd_kernel<256, true>), (int)((HEAD_MAXK * 64 + HEAD_MAXK + 256 * 65) * sizeof(float)));
-  }
-  const int c4n = C / 4;
-  if ((c4n & (c4n - 1)) == 0 && c4n >= K && P < 0x7fffffffLL) {
-    int ppb = (int)pp_cdiv(P, 2048);                                   // <= 2048 blocks, whole pixel-lane groups per block
-    if (ppb < 1024) ppb = 1024;
-    ppb = pp_cdiv(ppb, SP_THREADS) * SP_THREADS;
-    if (lz.coef) hipLaunchKernelGGL(conv1x1_fwd_stream_kernel<true>, dim3(pp_cdiv(P, ppb)), dim3(SP_THREADS), 0, s, x, ld_x, C, w, bias, logits, K, N, HW, ppb, lz);
-    else hipLaunchKernelGGL(conv1x1_fwd_stream_kernel<false>, dim3(pp_cdiv(P, ppb)), dim3(SP_THREADS), 0, s, x, ld_x, C, w, bias, logits, K, N, HW, ppb, lz);
-  } else if (tp == 128)
-  {
-    if (lz.coef) hipLaunchKernelGGL((conv1x1_fwd_kernel<128, true>), dim3(blocks), dim3(128), lds, s, x, ld_x, C, w, bias, logits, K, N, HW, lz);
-    else hipLaunchKernelGGL((conv1x1_fwd_kernel<128, false>), dim3(blocks), dim3(128), lds, s, x, ld_x, C, w, bias, logits, K, N, HW, lz);
-  }
-  else
-  {
-    if (lz.coef) hipLaunchKernelGGL((conv1x1_fwd_kernel<256, true>), dim3(blocks), dim3(256), lds, s, x, ld_x, C, w, bias, logits, K, N, HW, lz);
-    else hipLaunchKernelGGL((conv1x1_fwd_kernel<256, false>), dim3(blocks), dim3(256), lds, s, x, ld_x, C, w, bias, logits, K, N, HW, lz);
-  }
+  pp_by_class_bound(K, [&](auto mk) {
+    constexpr int MK = decltype(mk)::value;
+    const size_t lds = (size_t)(K * C + MK + tp * (C + 1)) * sizeof(float);
+    {   // once per (kernel, device): pp_max_lds
+      pp_max_lds(reinterpret_cast<const void*>(conv1x1_fwd_kernel<128, false, MK>), (int)((MK * HEAD_MAXC + MK + 128 * (HEAD_MAXC + 1)) * sizeof(float)));
+      pp_max_lds(reinterpret_cast<const void*>(conv1x1_fwd_kernel<256, false, MK>), (int)((MK * 64 + MK + 256 * 65) * sizeof(float)));
+      pp_max_lds(reinterpret_cast<const void*>(conv1x1_fwd_kernel<128, true, MK>), (int)((MK * HEAD_MAXC + MK + 128 * (HEAD_MAXC + 1)) * sizeof(float)));
+      pp_max_lds(reinterpret_cast<const void*>(conv1x1_fwd_kernel<256, true, MK>), (int)((MK * 64 + MK + 256 * 65) * sizeof(float)));
+    }
+    const int c4n = C / 4;
+    if ((c4n & (c4n - 1)) == 0 && c4n >= K && P < 0x7fffffffLL) {
+      int ppb = (int)pp_cdiv(P, 2048);                                   // <= 2048 blocks, whole pixel-lane groups per block
+      if (ppb < 1024) ppb = 1024;
+      ppb = pp_cdiv(ppb, SP_THREADS) * SP_THREADS;
+      if (lz.coef) hipLaunchKernelGGL((conv1x1_fwd_stream_kernel<true, MK>), dim3(pp_cdiv(P, ppb)), dim3(SP_THREADS), 0, s, x, ld_x, C, w, bias, logits, K, N, HW, ppb, lz);
+      else hipLaunchKernelGGL((conv1x1_fwd_stream_kernel<false, MK>), dim3(pp_cdiv(P, ppb)), dim3(SP_THREADS), 0, s, x, ld_x, C, w, bias, logits, K, N, HW, ppb, lz);
+    } else if (tp == 128)
+    {
+      if (lz.coef) hipLaunchKernelGGL((conv1x1_fwd_kernel<128, true, MK>), dim3(blocks), dim3(128), lds, s, x, ld_x, C, w, bias, logits, K, N, HW, lz);
+      else hipLaunchKernelGGL((conv1x1_fwd_kernel<128, false, MK>), dim3(blocks), dim3(128), lds, s, x, ld_x, C, w, bias, logits, K, N, HW, lz);
+    }
+    else
+    {
+      if (lz.coef) hipLaunchKernelGGL((conv1x1_fwd_kernel<256, true, MK>), dim3(blocks), dim3(256), lds, s, x, ld_x, C, w, bias, logits, K, N, HW, lz);
+      else hipLaunchKernelGGL((conv1x1_fwd_kernel<256, false, MK>), dim3(blocks), dim3(256), lds, s, x, ld_x, C, w, bias, logits, K, N, HW, lz);
+    }
+  });
   pp_prof_end(s);
   return pp_launch_status("conv1x1_fwd");
 }
@@ -657,15 +660,15 @@ extern "C" int PP_FN(pp_conv1x1_nhwc_to_nchw_fwd_lazy)(const pp_act* x, int ld_x
 // dw/db: per-block partial sums (each thread owns a set of (k,c) outputs and walks the block's pixel range
 // through LDS tiles), then a fixed-order finalize.
 #define HEAD_TP 64       // pixels per LDS tile
-template <bool LAZY>
+template <bool LAZY, int MK>
 __global__ __launch_bounds__(SP_THREADS) void conv1x1_bwd_kernel(const float* __restrict__ dl, const act_t* __restrict__ x,
                                                                  int ld_x, int C, const float* __restrict__ w,
                                                                  act_t* __restrict__ dx, int ld_dx, int K, int N, int HW,
                                                                  int pix_per_block, int accumulate_dx,
                                                                  float* __restrict__ partial /*[blocks][K*(C+1)]*/, PpLazy lz) {
-  __shared__ float ws[HEAD_MAXK * HEAD_MAXC];
+  __shared__ float ws[MK * HEAD_MAXC];
   __shared__ float xs[HEAD_TP * (HEAD_MAXC + 1)];
-  __shared__ float ds[HEAD_TP * HEAD_MAXK];
+  __shared__ float ds[HEAD_TP * MK];
   for (int i = threadIdx.x; i < K * C; i += blockDim.x) ws[i] = w[i];
   const long long P = (long long)N * HW;
   const long long p_lo = (long long)blockIdx.x * pix_per_block;
@@ -673,7 +676,7 @@ __global__ __launch_bounds__(SP_THREADS) void conv1x1_bwd_kernel(const float* __
   if (p_hi > P) p_hi = P;
   const int nout = K * (C + 1);              // (k, c) pairs plus the bias column c == C
   // each thread accumulates up to ceil(nout / 256) outputs
-  constexpr int NACC = (HEAD_MAXK * (HEAD_MAXC + 1) + SP_THREADS - 1) / SP_THREADS;
+  constexpr int NACC = (MK * (HEAD_MAXC + 1) + SP_THREADS - 1) / SP_THREADS;
   double acc[NACC];      // across-tile accumulation in double: the bias gradient is a sum of N*H*W terms that largely cancel
 #pragma unroll
   for (int j = 0; j < NACC; ++j) acc[j] = 0.0;
@@ -690,7 +693,7 @@ __global__ __launch_bounds__(SP_THREADS) void conv1x1_bwd_kernel(const float* __
         const int n = (int)(p / HW), hw = (int)(p % HW);
         v = dl[((size_t)n * K + k) * HW + hw];
       }
-      ds[pp * HEAD_MAXK + k] = v;
+      ds[pp * MK + k] = v;
     }
     for (int i = threadIdx.x; i < HEAD_TP * c4n; i += blockDim.x) {
       const int cq = i % c4n, pp = i / c4n;
@@ -710,7 +713,7 @@ __global__ __launch_bounds__(SP_THREADS) void conv1x1_bwd_kernel(const float* __
         const int cq = i % c4n, pp = i / c4n;
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int k = 0; k < K; ++k) {
-          const float g = ds[pp * HEAD_MAXK + k];
+          const float g = ds[pp * MK + k];
           const float* wk = ws + k * C + cq * 4;
           o.x += g * wk[0]; o.y += g * wk[1]; o.z += g * wk[2]; o.w += g * wk[3];
         }
@@ -726,8 +729,8 @@ __global__ __launch_bounds__(SP_THREADS) void conv1x1_bwd_kernel(const float* __
       if (o < nout) {
         const int k = o / (C + 1), c = o % (C + 1);
         float s = 0.f;
-        if (c < C) for (int pp = 0; pp < np; ++pp) s += ds[pp * HEAD_MAXK + k] * xs[pp * (HEAD_MAXC + 1) + c];
-        else       for (int pp = 0; pp < np; ++pp) s += ds[pp * HEAD_MAXK + k];
+        if (c < C) for (int pp = 0; pp < np; ++pp) s += ds[pp * MK + k] * xs[pp * (HEAD_MAXC + 1) + c];
+        else       for (int pp = 0; pp < np; ++pp) s += ds[pp * MK + k];
         acc[j] += (double)s;
       }
     }
@@ -745,21 +748,21 @@ __global__ __launch_bounds__(SP_THREADS) void conv1x1_bwd_kernel(const float* __
 // barrier inside the loop.  The LDS-tiled kernel above ran the 32 -> 5 head at 256^2 x 64 images at 2.4 TB/s of its
 // 1.16 GB (three barriers per 64-pixel tile, 165 of 256 threads busy in the dw phase).  Per-thread fp32 sums over its
 // <= 64 pixels, fp32 across the lanes of a wave, double across waves and blocks (fixed order: deterministic).
-template <bool LAZY>
+template <bool LAZY, int MK>
 __global__ __launch_bounds__(SP_THREADS) void conv1x1_bwd_stream_kernel(const float* __restrict__ dl, const act_t* __restrict__ x,
                                                                         int ld_x, int C, const float* __restrict__ w,
                                                                         act_t* __restrict__ dx, int ld_dx, int K, int N, int HW,
                                                                         int pix_per_block, int accumulate_dx,
                                                                         float* __restrict__ partial /*[blocks][K*(C+1)]*/, PpLazy lz) {
-  __shared__ float red[SP_THREADS / 64][HEAD_MAXK][HEAD_MAXC + 4];
+  __shared__ float red[SP_THREADS / 64][MK][HEAD_MAXC + 4];
   const int c4n = C >> 2, ppl = SP_THREADS / c4n;
   const int cq = threadIdx.x % c4n, pl = threadIdx.x / c4n;
   const int P = N * HW;
   const int p_lo = blockIdx.x * pix_per_block;
   const int p_hi = min(P, p_lo + pix_per_block);
-  float wr[HEAD_MAXK][4], acc[HEAD_MAXK][4], accb[HEAD_MAXK];
+  float wr[MK][4], acc[MK][4], accb[MK];
 #pragma unroll
-  for (int k = 0; k < HEAD_MAXK; ++k) {
+  for (int k = 0; k < MK; ++k) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) wr[k][j] = k < K ? w[k * C + cq * 4 + j] : 0.f;     // w sits in the flat parameter slab: 4-byte aligned only
     acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0.f;
@@ -769,12 +772,12 @@ __global__ __launch_bounds__(SP_THREADS) void conv1x1_bwd_stream_kernel(const fl
     float4 xv1[1] = {act_ld4f(x + (size_t)p * ld_x + cq * 4)};
     SP_LAZY4(xv1, n_img)
     const float4 xv = xv1[0];
-    float g[HEAD_MAXK];
+    float g[MK];
 #pragma unroll
-    for (int k = 0; k < HEAD_MAXK; ++k) g[k] = k < K ? dp[(size_t)k * HW] : 0.f;
+    for (int k = 0; k < MK; ++k) g[k] = k < K ? dp[(size_t)k * HW] : 0.f;
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-    for (int k = 0; k < HEAD_MAXK; ++k)
+    for (int k = 0; k < MK; ++k)
       if (k < K) {
         o.x += g[k] * wr[k][0]; o.y += g[k] * wr[k][1]; o.z += g[k] * wr[k][2]; o.w += g[k] * wr[k][3];
         acc[k][0] += g[k] * xv.x; acc[k][1] += g[k] * xv.y; acc[k][2] += g[k] * xv.z; acc[k][3] += g[k] * xv.w;
@@ -802,7 +805,7 @@ __global__ __launch_bounds__(SP_THREADS) void conv1x1_bwd_stream_kernel(const fl
   // lanes of a wave that share the channel quad (lane = pixel lane * c4n + quad): butterfly over the pixel-lane bits
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
-  for (int k = 0; k < HEAD_MAXK; ++k)
+  for (int k = 0; k < MK; ++k)
     if (k < K) {
       for (int d = c4n; d < 64; d <<= 1) {
 #pragma unroll
@@ -881,8 +884,8 @@ static int conv1x1_bwd_impl(const float* dlogits, const pp_act* x, int ld_x, int
                             int accumulate_dx, int accumulate_param_grads, void* workspace,
                             size_t workspace_bytes, PpLazy lz, hipStream_t s) {
   PP_CHECK_ARG(dlogits && x && w && workspace, "conv1x1_bwd: null pointer");
-  PP_CHECK_ARG(K >= 1 && K <= HEAD_MAXK && C % 4 == 0 && C <= HEAD_MAXC && ld_x % 4 == 0 && ld_x >= C,
-               "conv1x1_bwd: K=%d (<=8) C=%d (<=128, %%4) ld=%d", K, C, ld_x);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && C % 4 == 0 && C <= HEAD_MAXC && ld_x % 4 == 0 && ld_x >= C,
+               "conv1x1_bwd: K=%d (1..%d) C=%d (<=128, %%4) ld=%d", K, PP_MAXK, C, ld_x);
   PP_CHECK_ARG(!dx || (ld_dx % 4 == 0 && ld_dx >= C && ((uintptr_t)dx & PP_ACT_ALIGN) == 0), "conv1x1_bwd: bad dx");
   PP_CHECK_ARG(((uintptr_t)x & PP_ACT_ALIGN) == 0, "conv1x1_bwd: x must be 16-byte aligned");
   if (workspace_bytes < pp_conv1x1_bwd_workspace(K, C, N, HW)) {
@@ -894,20 +897,26 @@ static int conv1x1_bwd_impl(const float* dlogits, const pp_act* x, int ld_x, int
   const int blocks = head_blocks(P, &ppb);
   pp_prof_begin(PP_K_SPATIAL, 4.0 * P * K * C, 4.0 * P * (2.0 * C + K), s);
   const int c4n = C / 4;
-  if ((c4n & (c4n - 1)) == 0 && P < 0x7fffffffLL)
-  {
-    if (lz.coef) hipLaunchKernelGGL(conv1x1_bwd_stream_kernel<true>, dim3(blocks), dim3(SP_THREADS), 0, s, dlogits, x, ld_x, C, w, dx, ld_dx, K, N,
-                       HW, ppb, accumulate_dx, (float*)workspace, lz);
-    else hipLaunchKernelGGL(conv1x1_bwd_stream_kernel<false>, dim3(blocks), dim3(SP_THREADS), 0, s, dlogits, x, ld_x, C, w, dx, ld_dx, K, N,
-                       HW, ppb, accumulate_dx, (float*)workspace, lz);
-  }
-  else
-  {
-    if (lz.coef) hipLaunchKernelGGL(conv1x1_bwd_kernel<true>, dim3(blocks), dim3(SP_THREADS), 0, s, dlogits, x, ld_x, C, w, dx, ld_dx, K, N,
-                       HW, ppb, accumulate_dx, (float*)workspace, lz);
-    else hipLaunchKernelGGL(conv1x1_bwd_kernel<false>, dim3(blocks), dim3(SP_THREADS), 0, s, dlogits, x, ld_x, C, w, dx, ld_dx, K, N,
-                       HW, ppb, accumulate_dx, (float*)workspace, lz);
-  }
+  pp_by_class_bound(K, [&](auto mk) {
+    constexpr int MK = decltype(mk)::value;
+    // the streaming form holds 10 MK floats per thread: at MK = 32 it needs 256 VGPRs + ~190 AGPRs (one wave per SIMD), so K > 8
+    // runs the LDS-tiled form, whose per-thread state is the ceil(MK (C + 1) / 256) double accumulators
+    if constexpr (MK == HEAD_MAXK) {
+      if ((c4n & (c4n - 1)) == 0 && P < 0x7fffffffLL) {
+        if (lz.coef) hipLaunchKernelGGL((conv1x1_bwd_stream_kernel<true, MK>), dim3(blocks), dim3(SP_THREADS), 0, s, dlogits, x, ld_x, C, w, dx, ld_dx, K, N,
+                           HW, ppb, accumulate_dx, (float*)workspace, lz);
+        else hipLaunchKernelGGL((conv1x1_bwd_stream_kernel<false, MK>), dim3(blocks), dim3(SP_THREADS), 0, s, dlogits, x, ld_x, C, w, dx, ld_dx, K, N,
+                           HW, ppb, accumulate_dx, (float*)workspace, lz);
+        return;
+      }
+    }
+    {
+      if (lz.coef) hipLaunchKernelGGL((conv1x1_bwd_kernel<true, MK>), dim3(blocks), dim3(SP_THREADS), 0, s, dlogits, x, ld_x, C, w, dx, ld_dx, K, N,
+                         HW, ppb, accumulate_dx, (float*)workspace, lz);
+      else hipLaunchKernelGGL((conv1x1_bwd_kernel<false, MK>), dim3(blocks), dim3(SP_THREADS), 0, s, dlogits, x, ld_x, C, w, dx, ld_dx, K, N,
+                         HW, ppb, accumulate_dx, (float*)workspace, lz);
+    }
+  });
   hipLaunchKernelGGL(conv1x1_bwd_finalize_kernel, dim3(pp_cdiv(K * (C + 1), 16)), dim3(256), 0, s, (const float*)workspace,
                      blocks, K, C, dw, dbias, accumulate_param_grads);
   pp_prof_end(s);

@@ -39,6 +39,8 @@ parser.add_argument('--checkpoint_file', type=str, required=True,
                     help='run directory of a training session (ckps/ckp_399.pth, or ckp_39.pth for lvsc, is taken) or a .pth file')
 parser.add_argument('--best_ckp', action='store_true', default=False, help='take best_ckp.pth of the run directory instead')
 parser.add_argument('--dataset', type=str, default='acdc', choices=['acdc', 'chaost1', 'chaost2', 'lvsc'])
+parser.add_argument('--num_classes', type=int, default=None,
+                    help='segmentation classes incl. background the checkpoint was trained with, 1 .. 32 (default: the --dataset preset)')
 parser.add_argument('--num_workers', type=int, default=4)
 parser.add_argument('--batch_size', type=int, default=1, help='slices per forward pass (metrics stay per slice)')
 parser.add_argument('--input_ch', type=int, default=1)
@@ -61,6 +63,10 @@ def load_backbone(model, state_dict):
     """inference.py:138-146: a full-model checkpoint is reduced to its `backbone.` entries."""
     from .models.unet import check_checkpoint_norm
     check_checkpoint_norm(model, state_dict)
+    head = [v for k, v in state_dict.items() if k in ('final_conv.weight', 'backbone.final_conv.weight')]
+    if head and head[0].shape[0] != model.num_classes:
+        raise ValueError(f'the checkpoint\'s head has {head[0].shape[0]} classes, the model was built with {model.num_classes}: '
+                         f'pass --num_classes {head[0].shape[0]}')
     try:
         model.load_state_dict(state_dict)
     except RuntimeError:
@@ -96,7 +102,8 @@ def main_interface(args):
     from .models import UNet
     from .models.unet import norm_kwargs
     from .utils import AvgMeter
-    num_classes, spacing = CLASSES[args.dataset], SPACING[args.dataset]
+    num_classes = args.num_classes if args.num_classes is not None else CLASSES[args.dataset]
+    spacing = SPACING[args.dataset]
     size = args.image_size or CROP[args.dataset]          # only the size of --synthetic phantoms; real slices keep theirs
     logging.info(f'Number of classes: {num_classes}')
     logging.info(f'Spacing: {spacing}')

@@ -11,6 +11,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from .unet import check_num_classes
+
 
 def _ramp_up_mo(step, max_step, base_mo=0.9, gamma=0.9):
     """Momentum of the *new* prototype estimate, decaying from ``base_mo`` (aux_path_memory.py:118-120)."""
@@ -21,6 +23,7 @@ class AuxPath(nn.Module):
     def __init__(self, **kwargs):
         super().__init__()
         self.num_classes = kwargs['num_classes']
+        check_num_classes(self.num_classes, 'AuxPath')
         self.feat_stage = list(kwargs['feat_stage'])
         self.feat_ch = list(kwargs['feat_ch'])
         self.hid_ch = kwargs['hid_ch']

@@ -130,6 +130,18 @@ class DecBlock(nn.Module):
         raise RuntimeError('DecBlock holds parameters only')
 
 
+MAX_CLASSES = 32     # class bound of the loss and head kernels (pp_common.h: PP_MAXK)
+
+
+def check_num_classes(num_classes, where):
+    """Refuse a class count the HIP kernels do not serve, before any module or GPU buffer exists."""
+    if num_classes < 1:
+        raise ValueError(f'{where}: num_classes must be >= 1 (got {num_classes!r})')
+    if num_classes > MAX_CLASSES:
+        raise NotImplementedError(f'{where}: num_classes={num_classes}, the HIP loss and head kernels serve at most '
+                                  f'{MAX_CLASSES} classes (--num_classes <= {MAX_CLASSES})')
+
+
 class UNet(nn.Module):
     """Six encoder stages, five decoder stages, 1x1 head (reference: models/unet.py:10-98).  norm_op: 'batch' (nn.BatchNorm2d, the
     reference's blocks) or 'group' (nn.GroupNorm(norm_groups, C) in every block; norm_groups must divide every block width)."""
@@ -137,6 +149,7 @@ class UNet(nn.Module):
     def __init__(self, input_ch=1, init_ch=32, max_ch=512, num_classes=4, output_stride=32,
                  is_stride_conv=False, is_trans_conv=False, elab_end_points=False, norm_op='batch', norm_groups=8):
         super().__init__()
+        check_num_classes(num_classes, 'UNet')
         assert is_trans_conv == is_stride_conv, \
             "Only combo of stride_conv and trans_conv or maxpool and upsample is allowed."
         assert output_stride in [8, 16, 32]

@@ -53,6 +53,10 @@ CONV_CASES = [   # B, H, W, Cin, Cout, dil -- the kernel each shape selects at t
     (2, 16, 16, 256, 256, 1),     # Winograd F(4x4), pre-split GEMM 128 x 256
     (1, 16, 16, 512, 128, 2),     # Winograd, dilation 2, 256 x 128 tiles
     (1, 12, 20, 64, 40, 1),       # ragged: fallback kernels
+    (2, 28, 28, 256, 512, 2),     # Winograd F(2x2) (fp32 GEMMs): enc_block5 at a 224 crop
+    (3, 6, 10, 256, 128, 1),      # ... odd tile counts
+    (1, 24, 8, 256, 72, 4),       # ... dilation 4, ragged N
+    (4, 28, 28, 256, 128, 2),     # ... weight gradient in two splits
 ]
 
 
@@ -67,8 +71,31 @@ def test_convolution_family_stays_inside_its_buffers(B, H, W, Cin, Cout, dil):
     dzs = (torch.randn(P * Cout, generator=g) * 1e-3).cuda()
     amax = dzs.abs().max().reshape(1).contiguous()
     wino = Cin >= 256 and H % (4 * dil) == 0 and W % (4 * dil) == 0
+    wino2 = Cin >= 256 and not wino
     out, dx, dw = Guarded(P * Cout), Guarded(P * Cin), Guarded(Cout * Cin * 9)
-    if wino:
+    if wino2:
+        # F(2x2,3x3): 16 planes; every workspace exactly the size its query reports, each call behind its own sentinel band
+        assert lib.pp_conv3x3_wino_tile(H, W, dil) == 2
+        Uf, Ub = torch.empty(16, Cout, Cin, device='cuda'), torch.empty(16, Cin, Cout, device='cuda')
+        lib.pp_wino_pack_weights(w.data_ptr(), Cout, Cin, 2, Uf.data_ptr(), Ub.data_ptr(), st)
+        nf, nd = lib.pp_conv3x3_wino_workspace(Cin, Cout, B, H, W, dil), lib.pp_conv3x3_wino_workspace(Cout, Cin, B, H, W, dil)
+        nwg = lib.pp_conv3x3_wino_bwd_weight_workspace(Cout, Cin, B, H, W, dil)
+        wsf, wsd, ws, ws2 = GuardedWs(nf), GuardedWs(nd), GuardedWs(nwg), GuardedWs(nwg)
+        vk = Guarded(lib.pp_conv3x3_wino_vkeep_elems(Cin, B, H, W, dil))
+        dw2 = Guarded(Cout * Cin * 9)
+        lib.pp_conv3x3_wino_fwd(x.data_ptr(), Cin, Cin, Uf.data_ptr(), bias.data_ptr(), out.t.data_ptr(), Cout, Cout, B, H, W, dil, 0,
+                                vk.t.data_ptr(), wsf.ptr(), nf, st)
+        lib.pp_conv3x3_wino_bwd_data(dzs.data_ptr(), Cout, Cout, Ub.data_ptr(), dx.t.data_ptr(), Cin, Cin, B, H, W, dil, 0,
+                                     wsd.ptr(), nd, st)
+        lib.pp_conv3x3_wino_bwd_weight(dzs.data_ptr(), Cout, Cout, x.data_ptr(), Cin, Cin, B, H, W, dil, dw.t.data_ptr(), 0,
+                                       vk.t.data_ptr(), ws.ptr(), nwg, st)
+        lib.pp_conv3x3_wino_bwd_weight(dzs.data_ptr(), Cout, Cout, x.data_ptr(), Cin, Cin, B, H, W, dil, dw2.t.data_ptr(), 0,
+                                       None, ws2.ptr(), nwg, st)                  # own input transform: the whole workspace
+        torch.cuda.synchronize()
+        assert vk.ok(), 'kept transformed input'
+        assert wsf.ok() and wsd.ok() and ws2.ok(), 'forward / data-gradient / weight-gradient workspace'
+        assert dw2.ok(), 'weight gradient (own input transform)'
+    elif wino:
         Uf, Ub = torch.empty(36, Cout, Cin, device='cuda'), torch.empty(36, Cin, Cout, device='cuda')
         lib.pp_wino_pack_weights_f16x3(w.data_ptr(), Cout, Cin, 4, Uf.data_ptr(), Ub.data_ptr(), st)
         nws = max(lib.pp_conv3x3_wino_workspace(Cin, Cout, B, H, W, dil), lib.pp_conv3x3_wino_workspace(Cout, Cin, B, H, W, dil),

@@ -571,7 +571,8 @@ WINO_CASES = [
 
 @pytest.mark.parametrize('B,H,W,Cin,Cout,dil', WINO_CASES)
 def test_winograd_conv(B, H, W, Cin, Cout, dil):
-    """Winograd F(2x2,3x3) path against nn.Conv2d / its autograd (fp64 reference)."""
+    """Winograd path against nn.Conv2d / its autograd (fp64 reference).  Every case here resolves to the F(4x4,3x3) tile;
+    the F(2x2,3x3) kernels have their own cases (WINO2_CASES)."""
     lib, st = _lib()
     g = torch.Generator().manual_seed(B * 100 + Cin + Cout + dil)
     x = torch.randn(B, Cin, H, W, generator=g)
@@ -643,6 +644,181 @@ def test_winograd_conv(B, H, W, Cin, Cout, dil):
         lib.pp_conv3x3_wino_bwd_weight_f16x3(dz_small.data_ptr(), ld_out, Cout, xin.data_ptr(), ld_in, Cin, B, H, W, dil,
                                              dw.data_ptr(), 1, vk.data_ptr(), ws.data_ptr(), nws, amax.data_ptr(), st)
         assert rel(dw * 1e7, 2 * wr.grad) < TOL
+
+
+WINO2_CASES = [
+    # B, H, W, Cin, Cout, dil -- every case resolves to the F(2x2,3x3) tile (a side is not a multiple of 4 * dil)
+    (2, 28, 28, 256, 512, 2),       # enc_block5.c1 at a 224 crop, output stride 8
+    (2, 28, 28, 512, 512, 2),       # enc_block5.c2
+    (4, 28, 28, 256, 512, 2),       # ... with 2 images x 2 views: the weight gradient runs in two splits
+    (2, 14, 14, 1024, 512, 1),      # dec_block5.c1 at 224, output stride 16 / 32
+    (1, 32, 34, 1024, 512, 1),      # dec_block5.c1 of a native 256 x 272 slice: one side a multiple of 4, the other of 2 only
+    (1, 2, 2, 256, 64, 1),          # a single tile
+    (3, 6, 10, 256, 128, 1),        # odd tile counts (3 x 5 per image)
+    (1, 24, 8, 256, 72, 4),         # dilation 4 (sixteen 6 x 2 sub-images), ragged N: the N % 128 != 0 GEMM
+    (2, 12, 20, 12, 20, 2),         # small ragged channel counts
+]
+
+
+def _wino2_weights_ref(w):
+    """(Uf [16][O][C], Ub [16][C][O]) of F(2x2,3x3) in fp64: U = G g G^T, Ub from the kernel flipped in both axes."""
+    G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64)
+    w = w.double()
+
+    def u(k):
+        return torch.einsum('ar,ocrs,bs->aboc', G, k, G).reshape(16, *k.shape[:2])
+    return u(w), u(w.flip(2, 3)).transpose(1, 2)
+
+
+@pytest.mark.parametrize('B,H,W,Cin,Cout,dil', WINO2_CASES)
+def test_winograd_f2x2_conv(B, H, W, Cin, Cout, dil):
+    """F(2x2,3x3) Winograd (fp32 GEMMs) against nn.Conv2d / its autograd in fp64: weight packing (Uf and Ub), forward with and
+    without bias / kept V / accumulation, data gradient, weight gradient (own input transform, then the V kept by the forward,
+    accumulating), all with ld wider than the channel count and canaries in the padding columns."""
+    lib, st = _lib()
+    assert lib.pp_conv3x3_wino_tile(H, W, dil) == 2
+    splits = lib.pp_conv3x3_wino_bwd_weight_splits(Cout, Cin, B, H, W, dil)
+    g = torch.Generator().manual_seed(B * 100 + Cin + Cout + dil + H)
+    x = torch.randn(B, Cin, H, W, generator=g)
+    w = torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin)
+    b = torch.randn(Cout, generator=g)
+    dy = torch.randn(B, Cout, H, W, generator=g)
+    xr, wr = x.double().requires_grad_(True), w.double().requires_grad_(True)
+    yr = F.conv2d(xr, wr, None, 1, dil, dil)
+    yr.backward(dy.double())
+    yb = yr.detach() + b.double().view(1, -1, 1, 1)
+    ld_in, ld_out = Cin + 8, Cout + 4
+    xin = torch.full((B, H, W, ld_in), 7.0, device=dev()); xin[..., :Cin] = nhwc(x).to(dev())
+    dz = torch.full((B, H, W, ld_out), 7.0, device=dev()); dz[..., :Cout] = nhwc(dy).to(dev())
+    wd, bd = w.to(dev()), b.to(dev())
+    Uf = torch.full((16, Cout, Cin), 7.0, device=dev()); Ub = torch.full((16, Cin, Cout), 7.0, device=dev())
+    lib.pp_wino_pack_weights(wd.data_ptr(), Cout, Cin, 2, Uf.data_ptr(), Ub.data_ptr(), st)
+    uf_ref, ub_ref = _wino2_weights_ref(w)
+    assert rel(Uf, uf_ref) < 1e-6 and rel(Ub, ub_ref) < 1e-6
+    nws = max(lib.pp_conv3x3_wino_workspace(Cin, Cout, B, H, W, dil), lib.pp_conv3x3_wino_workspace(Cout, Cin, B, H, W, dil),
+              lib.pp_conv3x3_wino_bwd_weight_workspace(Cout, Cin, B, H, W, dil))
+    ws = torch.empty(nws + 64, dtype=torch.uint8, device=dev())
+    vk = torch.empty(lib.pp_conv3x3_wino_vkeep_elems(Cin, B, H, W, dil), device=dev())
+    out = torch.full((B, H, W, ld_out), 7.0, device=dev())
+    want = torch.zeros_like(yb)
+    for bias, acc, keep in ((True, 0, False), (False, 1, True), (False, 0, True), (True, 1, False)):
+        lib.pp_conv3x3_wino_fwd(xin.data_ptr(), ld_in, Cin, Uf.data_ptr(), bd.data_ptr() if bias else None, out.data_ptr(), ld_out,
+                                Cout, B, H, W, dil, acc, vk.data_ptr() if keep else None, ws.data_ptr(), nws, st)
+        want = (want if acc else 0) + (yb if bias else yr.detach())
+        assert rel(nchw(out[..., :Cout]), want) < TOL, (bias, acc, keep)
+        assert torch.all(out[..., Cout:] == 7.0), (bias, acc, keep)
+    dx = torch.full((B, H, W, ld_in), 3.0, device=dev())
+    for acc in (0, 1):
+        lib.pp_conv3x3_wino_bwd_data(dz.data_ptr(), ld_out, Cout, Ub.data_ptr(), dx.data_ptr(), ld_in, Cin, B, H, W, dil, acc,
+                                     ws.data_ptr(), nws, st)
+        assert rel(nchw(dx[..., :Cin]), (acc + 1) * xr.grad) < TOL, acc
+        assert torch.all(dx[..., Cin:] == 3.0), acc
+    dw = torch.full((Cout, Cin, 3, 3), 5.0, device=dev())
+    lib.pp_conv3x3_wino_bwd_weight(dz.data_ptr(), ld_out, Cout, xin.data_ptr(), ld_in, Cin, B, H, W, dil, dw.data_ptr(), 0,
+                                   None, ws.data_ptr(), nws, st)
+    assert rel(dw, wr.grad) < TOL, f'own input transform, {splits} split(s)'
+    lib.pp_conv3x3_wino_bwd_weight(dz.data_ptr(), ld_out, Cout, xin.data_ptr(), ld_in, Cin, B, H, W, dil, dw.data_ptr(), 1,
+                                   vk.data_ptr(), ws.data_ptr(), nws, st)
+    assert rel(dw, 2 * wr.grad) < TOL, f'kept V, accumulate, {splits} split(s)'
+
+
+def test_winograd_f2x2_cases_cover_one_and_several_splits():
+    """The F(2x2) weight gradient reduces over the tiles in one pass or in several splits (wino_wg_plan): both occur above."""
+    lib, _ = _lib()
+    splits = {c: lib.pp_conv3x3_wino_bwd_weight_splits(c[4], c[3], c[0], c[1], c[2], c[5]) for c in WINO2_CASES}
+    assert min(splits.values()) == 1 and max(splits.values()) > 1, splits
+
+
+@pytest.mark.parametrize('B,H,W,Cin,Cout,dil', [c for c in WINO2_CASES if c[3] % 4 == 0])
+def test_winograd_f2x2_bn_epilogue(B, H, W, Cin, Cout, dil):
+    """pp_conv3x3_wino_fwd_bn at the F(2x2) tile (the unfused BatchNorm kernels inside the call) against fp64 nn.Conv2d: mode 1
+    z and the per-group partial (sum, sum of squares) for one and two statistics groups, mode 2 y = lrelu(z * scale + shift)
+    written into a channel slice of a wider tensor -- the bounds of test_conv_bn_fused_epilogues."""
+    import ctypes
+    lib, st = _lib()
+    assert lib.pp_conv3x3_wino_tile(H, W, dil) == 2
+    g = torch.Generator().manual_seed(B * 31 + Cin + Cout + dil)
+    x = torch.randn(B, Cin, H, W, generator=g) * 1.5
+    w = torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin)
+    b = torch.randn(Cout, generator=g)
+    z_ref = F.conv2d(x.double(), w.double(), b.double(), 1, dil, dil)
+    xin = nhwc(x).to(dev())
+    wd, bd = w.to(dev()), b.to(dev())
+    U = torch.empty(16, Cout, Cin, device=dev())
+    lib.pp_wino_pack_weights(wd.data_ptr(), Cout, Cin, 2, U.data_ptr(), None, st)
+    nws = lib.pp_conv3x3_wino_workspace(Cin, Cout, B, H, W, dil)
+    ws = torch.empty(nws + 64, dtype=torch.uint8, device=dev())
+    vk = torch.empty(lib.pp_conv3x3_wino_vkeep_elems(Cin, B, H, W, dil), device=dev())
+    scale = (torch.rand(Cout, generator=g) + 0.5).to(dev())
+    shift = torch.randn(Cout, generator=g).to(dev())
+    rows = ctypes.c_int(0)
+    for groups in ((1, 2) if B % 2 == 0 else (1,)):
+        nstat = lib.pp_conv3x3_bn_stats_bytes(Cout, B, H, W, groups)
+        stats = torch.full((nstat // 8 + 2,), float('nan'), dtype=torch.float64, device=dev())
+        z = torch.full((B, H, W, Cout), 7.0, device=dev())
+        lib.pp_conv3x3_wino_fwd_bn(xin.data_ptr(), Cin, Cin, U.data_ptr(), bd.data_ptr(), z.data_ptr(), Cout, Cout, B, H, W, dil, 0,
+                                   vk.data_ptr(), ws.data_ptr(), nws, 1, None, None, 0.01, groups, stats.data_ptr(), nstat,
+                                   ctypes.byref(rows), st)
+        torch.cuda.synchronize()
+        assert rel(nchw(z), z_ref) < TOL, groups
+        r = rows.value
+        assert r >= 1
+        part = stats[:groups * r * 2 * Cout].view(groups, r, 2, Cout).cpu()
+        assert torch.isfinite(part).all(), 'a partial row was not written'
+        zc = z.double().cpu().view(groups, -1, Cout)
+        assert rel(part[:, :, 0].sum(1), zc.sum(1)) < 1e-5, groups
+        assert rel(part[:, :, 1].sum(1), zc.pow(2).sum(1)) < 1e-5, groups
+    ld = Cout + 8
+    y = torch.full((B, H, W, ld), 3.0, device=dev())
+    lib.pp_conv3x3_wino_fwd_bn(xin.data_ptr(), Cin, Cin, U.data_ptr(), bd.data_ptr(), y[..., 4:].data_ptr(), ld, Cout, B, H, W, dil, 0,
+                               None, ws.data_ptr(), nws, 2, scale.data_ptr(), shift.data_ptr(), 0.01, 2 if B % 2 == 0 else 1, None, 0,
+                               ctypes.byref(rows), st)
+    torch.cuda.synchronize()
+    pre = z_ref * scale.double().cpu().view(1, -1, 1, 1) + shift.double().cpu().view(1, -1, 1, 1)
+    assert rel(nchw(y[..., 4:4 + Cout]), torch.where(pre > 0, pre, pre * 0.01)) < TOL
+    assert bool((y[..., :4] == 3.0).all()) and bool((y[..., 4 + Cout:] == 3.0).all())
+
+
+@pytest.mark.parametrize('B,H,W,Cin,Cout,dil', [(2, 28, 28, 256, 512, 2), (1, 32, 34, 1024, 512, 1), (3, 6, 10, 256, 128, 1)])
+def test_split_fp16_winograd_refuses_the_f2x2_tile(B, H, W, Cin, Cout, dil):
+    """The split-fp16 Winograd GEMMs exist for the F(4x4) tile only: every entry point refuses an F(2x2) geometry with an argument
+    error before it launches anything, and leaves its output alone."""
+    import ctypes
+    from pacingpseudo_amd._lib import HipLibraryError
+    lib, st = _lib()
+    assert lib.pp_conv3x3_wino_tile(H, W, dil) == 2
+    wd = torch.randn(Cout, Cin, 3, 3, device=dev())
+    U = torch.empty(36, max(Cin, Cout), max(Cin, Cout), device=dev())
+    with pytest.raises(HipLibraryError, match='tile must be 4'):
+        lib.pp_wino_pack_weights_f16x3(wd.data_ptr(), Cout, Cin, 2, U.data_ptr(), None, st)
+    x = torch.randn(B, H, W, Cin, device=dev())
+    dz = torch.randn(B, H, W, Cout, device=dev())
+    nws = max(lib.pp_conv3x3_wino_workspace(Cin, Cout, B, H, W, dil), lib.pp_conv3x3_wino_workspace(Cout, Cin, B, H, W, dil),
+              lib.pp_conv3x3_wino_bwd_weight_workspace(Cout, Cin, B, H, W, dil))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev())
+    vk = torch.empty(lib.pp_conv3x3_wino_vkeep_elems(Cin, B, H, W, dil), device=dev())
+    out = torch.full((B, H, W, Cout), 7.0, device=dev())
+    dx = torch.full((B, H, W, Cin), 7.0, device=dev())
+    dw = torch.full((Cout, Cin, 3, 3), 7.0, device=dev())
+    nstat = lib.pp_conv3x3_bn_stats_bytes(Cout, B, H, W, 1)
+    stats = torch.zeros(nstat // 8 + 2, dtype=torch.float64, device=dev())
+    rows = ctypes.c_int(0)
+    calls = {
+        'fwd': lambda: lib.pp_conv3x3_wino_fwd_f16x3(x.data_ptr(), Cin, Cin, U.data_ptr(), None, out.data_ptr(), Cout, Cout, B, H, W,
+                                                     dil, 0, vk.data_ptr(), ws.data_ptr(), nws, st),
+        'fwd_bn': lambda: lib.pp_conv3x3_wino_fwd_bn(x.data_ptr(), Cin, Cin, U.data_ptr(), None, out.data_ptr(), Cout, Cout, B, H, W,
+                                                     dil, 1, vk.data_ptr(), ws.data_ptr(), nws, 1, None, None, 0.01, 1,
+                                                     stats.data_ptr(), nstat, ctypes.byref(rows), st),
+        'bwd_data': lambda: lib.pp_conv3x3_wino_bwd_data_f16x3(dz.data_ptr(), Cout, Cout, U.data_ptr(), dx.data_ptr(), Cin, Cin, B,
+                                                               H, W, dil, 0, ws.data_ptr(), nws, None, st),
+        'bwd_weight': lambda: lib.pp_conv3x3_wino_bwd_weight_f16x3(dz.data_ptr(), Cout, Cout, x.data_ptr(), Cin, Cin, B, H, W, dil,
+                                                                   dw.data_ptr(), 0, None, ws.data_ptr(), nws, None, st),
+    }
+    for name, call in calls.items():
+        with pytest.raises(HipLibraryError, match=r'F\(4x4,3x3\)'):
+            call()
+        torch.cuda.synchronize()
+        assert bool((out == 7.0).all()) and bool((dx == 7.0).all()) and bool((dw == 7.0).all()), name
 
 
 # ---- --is_stride_conv / --is_trans_conv (models/unet.py:100-152) ---------------------------------------------------------

@@ -553,6 +553,25 @@ int pp_adam_step_dev(float* p, const float* g, float* m, float* v, long long n, 
                      float beta2, float eps, float weight_decay, int* step_dev, int* skip, int count_skip, void* stream);
 int pp_sgd_momentum_step_dev(float* p, const float* g, float* momentum_buf, long long n, float lr, const float* lr_dev,
                              float momentum, float weight_decay, int* step_dev, int* skip, int count_skip, void* stream);
+/* Global gradient-norm clipping, torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) semantics (the reference trains
+ * without it, train_chaos.py:313-315; off by default here).  pp_grad_sumsq: sum of squares of g[0..n) formed in double, one double
+ * per block written to partial[0 .. pp_grad_sumsq_rows(n)) -- the row count depends on n alone and nothing is added atomically,
+ * so the result is the same bits in every run.  A step calls it once per active slab segment, each with its own rows of one
+ * scratch array, then pp_grad_clip_finalize ONCE over all `rows`: out2[0] = total = sqrt(sum), out2[1] = coef =
+ * min(1, max_norm / (total + 1e-6)) (double arithmetic, rounded once to fp32; max_norm = +inf: measure, never clip), and the
+ * statistics block stats = double[4] {steps, steps with coef < 1, sum of total, max of total} is advanced -- unless skip
+ * (nullable) says the overflow guard skips this step.  pp_adam_step_clip / pp_sgd_momentum_step_clip = the *_dev forms on
+ * gradients fl32(g * clip_dev[0]), clip_dev = out2 + 1: what the *_dev forms compute on a slab scaled in place; g is not written. */
+int pp_grad_sumsq_rows(long long n);
+int pp_grad_sumsq(const float* g, long long n, double* partial, void* stream);
+int pp_grad_clip_finalize(const double* partial, int rows, double max_norm, const int* skip, float* out2, double* stats,
+                          void* stream);
+int pp_adam_step_clip(float* p, const float* g, float* m, float* v, long long n, float lr, const float* lr_dev, float beta1,
+                      float beta2, float eps, float weight_decay, int* step_dev, int* skip, int count_skip, const float* clip_dev,
+                      void* stream);
+int pp_sgd_momentum_step_clip(float* p, const float* g, float* momentum_buf, long long n, float lr, const float* lr_dev,
+                              float momentum, float weight_decay, int* step_dev, int* skip, int count_skip, const float* clip_dev,
+                              void* stream);
 
 /* ---- diagnostics -------------------------------------------------------------------------------------------- */
 /* bare v_mfma_f32_32x32x2_f32 loop: the fp32 matrix rate this device sustains at its clock under load */

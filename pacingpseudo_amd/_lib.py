@@ -179,6 +179,11 @@ _PROTOS = {
     'pp_sgd_momentum_step_guard': (i32, [vp, vp, vp, i64, f32, f32, f32, i32, vp, vp]),
     'pp_adam_step_dev': (i32, [vp, vp, vp, vp, i64, f32, vp, f32, f32, f32, f32, vp, vp, i32, vp]),
     'pp_sgd_momentum_step_dev': (i32, [vp, vp, vp, i64, f32, vp, f32, f32, vp, vp, i32, vp]),
+    'pp_grad_sumsq_rows': (i32, [i64]),
+    'pp_grad_sumsq': (i32, [vp, i64, vp, vp]),
+    'pp_grad_clip_finalize': (i32, [vp, i32, C.c_double, vp, vp, vp, vp]),
+    'pp_adam_step_clip': (i32, [vp, vp, vp, vp, i64, f32, vp, f32, f32, f32, f32, vp, vp, i32, vp, vp]),
+    'pp_sgd_momentum_step_clip': (i32, [vp, vp, vp, i64, f32, vp, f32, f32, vp, vp, i32, vp, vp]),
     'pp_mfma_probe': (i32, [vp, i32, i32, C.POINTER(C.c_double), vp]),
     'pp_weighted_sum_fwd': (i32, [vp, vp, i32, vp, vp]),
     'pp_pack_conv3x3_weights_f16x3_batch': (i32, [vp, i32, vp]),
@@ -209,7 +214,7 @@ for _n in H16_ENTRIES:
 _H16_SET = frozenset(H16_ENTRIES) | {'pp_memory_update'}
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
-MIN_LIB_VERSION = 602      # include/pacingpseudo_hip.h with K <= 32 in the loss and head kernels (pp_runtime.cpp: PP_VERSION)
+MIN_LIB_VERSION = 603      # include/pacingpseudo_hip.h with the gradient-norm clipping entry points (pp_runtime.cpp: PP_VERSION)
 PROF_KINDS = ('conv_igemm', 'conv_wgrad', 'bn', 'spatial', 'loss', 'optim', 'misc', 'wino_gemm', 'wino_wgrad',
               'wino_xform', 'conv_f16x3', 'wino_gemm_f16x3', 'wino_wgrad_f16x3', 'conv_wgrad_f16x3', 'conv_halo_f16x3')
 
@@ -253,7 +258,7 @@ class _Lib:
             raise AttributeError(name)
         fn = getattr(self.load(), name)
         res = _PROTOS[name][0]
-        if res is not i32 or name in ('pp_version', 'pp_conv3x3_wino_tile', 'pp_conv3x3_wino_bwd_weight_splits', 'pp_conv3x3_lazy_ok', 'pp_conv3x3_lazy_ok_h16', 'pp_conv3x3_lazy_ok_bf16', 'pp_range_push', 'pp_range_pop', 'pp_get_matrix_products', 'pp_get_wgrad_cus'):      # sizes / queries / range depth: no status code
+        if res is not i32 or name in ('pp_version', 'pp_conv3x3_wino_tile', 'pp_conv3x3_wino_bwd_weight_splits', 'pp_conv3x3_lazy_ok', 'pp_conv3x3_lazy_ok_h16', 'pp_conv3x3_lazy_ok_bf16', 'pp_range_push', 'pp_range_pop', 'pp_get_matrix_products', 'pp_get_wgrad_cus', 'pp_grad_sumsq_rows'):      # sizes / queries / range depth: no status code
             return fn
 
         def checked(*a):

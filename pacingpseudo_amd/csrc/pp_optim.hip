@@ -3,11 +3,22 @@
 // HBM-bound: 16 B per lane, reads p,g,m,v and writes p,m,v once (28 B / parameter).
 #include "pp_common.h"
 
+// gc = fl32(g * coef): the gradient-norm clip of FusedAdam / FusedSGD.  The product is ROUNDED before anything else uses it --
+// `gc + wd * p` must stay the existing fma(wd, p, g') on g' = gc, exactly what the unclipped kernel computes on a slab that
+// torch.nn.utils.clip_grad_norm_ had scaled in place; contracted into fma(g, coef, wd * p) it would round differently.
+__device__ __forceinline__ float pp_mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// CLIP = false is the kernel as it always was (clip_dev is not read); CLIP = true scales every gradient element by the device
+// scalar clip_dev[0] first (the coefficient grad_clip_finalize_kernel writes).
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, long long n,
                                                    float lr, float b1, float b2, float eps, float wd, float bc1,
                                                    float sqrt_bc2, int* __restrict__ skip, const int* __restrict__ step_dev,
-                                                   const float* __restrict__ lr_dev) {
+                                                   const float* __restrict__ lr_dev, const float* __restrict__ clip_dev) {
   // skip (nullable): skip[0] != 0 -> the gradients of this step are not finite (16-bit storage: loss-scale overflow, found by
   // pp_scale_guard): leave p, m, v untouched.  The skipped update is counted in skip[1] by the caller's form: the *_guard entry
   // points count here (once per launch), the *_dev entry points in their commit kernel (once per optimizer step).
@@ -24,6 +35,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     sqrt_bc2 = (float)sqrt(1.0 - pow((double)b2, t));
   }
   if (lr_dev) lr = lr_dev[0];
+  const float coef = CLIP ? clip_dev[0] : 1.f;
   const long long n4 = n >> 2;
   const float step = lr / bc1;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
@@ -33,7 +45,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     float4 vv = reinterpret_cast<float4*>(v)[i];
 #define PP_ADAM1(f)                                              \
     {                                                            \
-      const float gr = gg.f + wd * pp.f;                         \
+      const float gc = CLIP ? pp_mul_rounded(gg.f, coef) : gg.f; \
+      const float gr = gc + wd * pp.f;                           \
       mm.f = b1 * mm.f + (1.f - b1) * gr;                        \
       vv.f = b2 * vv.f + (1.f - b2) * gr * gr;                   \
       pp.f -= step * (mm.f / (sqrtf(vv.f) / sqrt_bc2 + eps));    \
@@ -46,7 +59,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   // tail (n not a multiple of 4)
   const long long t = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n) {
-    const float gr = g[t] + wd * p[t];
+    const float gc = CLIP ? pp_mul_rounded(g[t], coef) : g[t];
+    const float gr = gc + wd * p[t];
     const float m1 = b1 * m[t] + (1.f - b1) * gr;
     const float v1 = b2 * v[t] + (1.f - b2) * gr * gr;
     m[t] = m1; v[t] = v1;
@@ -66,7 +80,8 @@ __global__ void optim_commit_kernel(int* __restrict__ step_dev, int* __restrict_
 
 static int adam_step_impl(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
                           float beta2, float eps, float weight_decay, int step, int* skip, void* stream,
-                          int* step_dev = nullptr, const float* lr_dev = nullptr, int count_skip = 0) {
+                          int* step_dev = nullptr, const float* lr_dev = nullptr, int count_skip = 0,
+                          const float* clip_dev = nullptr) {
   hipStream_t s = (hipStream_t)stream;
   PP_CHECK_ARG(p && g && m && v && n > 0 && (step >= 1 || step_dev), "adam_step: bad arguments");
   PP_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step: slabs must be 16-byte aligned");
@@ -75,8 +90,12 @@ static int adam_step_impl(float* p, const float* g, float* m, float* v, long lon
   int blocks = pp_cdiv(n / 4 + 1, 256);
   if (blocks > 4096) blocks = 4096;
   pp_prof_begin(PP_K_OPTIM, 0.0, 28.0 * (double)n, s);
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
-                     (float)bc1, (float)sqrt(bc2), skip, (const int*)step_dev, lr_dev);
+  if (clip_dev)
+    hipLaunchKernelGGL(adam_kernel<true>, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
+                       (float)bc1, (float)sqrt(bc2), skip, (const int*)step_dev, lr_dev, clip_dev);
+  else
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
+                       (float)bc1, (float)sqrt(bc2), skip, (const int*)step_dev, lr_dev, clip_dev);
   if (step_dev) hipLaunchKernelGGL(optim_commit_kernel, dim3(1), dim3(1), 0, s, step_dev, skip, count_skip);
   pp_prof_end(s);
   return pp_launch_status("adam_step");
@@ -101,19 +120,30 @@ extern "C" int pp_adam_step_dev(float* p, const float* g, float* m, float* v, lo
   PP_CHECK_ARG(step_dev, "adam_step_dev: step_dev is null");
   return adam_step_impl(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, 1, skip, stream, step_dev, lr_dev, count_skip);
 }
+// pp_adam_step_dev on gradients scaled by the clip coefficient clip_dev[0] (out2 + 1 of pp_grad_clip_finalize): every
+// element is first rounded to fl32(g * coef), the rest is the arithmetic above.  The gradient slab itself is not written.
+extern "C" int pp_adam_step_clip(float* p, const float* g, float* m, float* v, long long n, float lr, const float* lr_dev, float beta1,
+                                 float beta2, float eps, float weight_decay, int* step_dev, int* skip, int count_skip,
+                                 const float* clip_dev, void* stream) {
+  PP_CHECK_ARG(step_dev && clip_dev, "adam_step_clip: step_dev or clip_dev is null");
+  return adam_step_impl(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, 1, skip, stream, step_dev, lr_dev, count_skip, clip_dev);
+}
 
 // torch.optim.SGD(lr, momentum, weight_decay) (train_chaos.py:220-221, --optimizer momentum): g += wd*p;
 // buf = g on the first step, momentum*buf + g afterwards (dampening 0, no Nesterov); p -= lr*buf.  20 B / parameter.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                            float* __restrict__ buf, long long n, float lr, float mom,
                                                            float wd, int first, int* __restrict__ skip,
-                                                           const int* __restrict__ step_dev, const float* __restrict__ lr_dev) {
+                                                           const int* __restrict__ step_dev, const float* __restrict__ lr_dev,
+                                                           const float* __restrict__ clip_dev) {
   if (skip && skip[0]) {                      // non-finite gradients this step (see adam_kernel)
     if (!step_dev && blockIdx.x == 0 && threadIdx.x == 0) skip[1] += 1;
     return;
   }
   if (step_dev) first = step_dev[0] == 0;
   if (lr_dev) lr = lr_dev[0];
+  const float coef = CLIP ? clip_dev[0] : 1.f;          // see adam_kernel
   const long long n4 = n >> 2;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
     float4 pp = reinterpret_cast<float4*>(p)[i];
@@ -121,7 +151,8 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ p
     float4 bb = first ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<float4*>(buf)[i];
 #define PP_SGD1(f)                                   \
     {                                                \
-      const float gr = gg.f + wd * pp.f;             \
+      const float gc = CLIP ? pp_mul_rounded(gg.f, coef) : gg.f; \
+      const float gr = gc + wd * pp.f;               \
       bb.f = first ? gr : mom * bb.f + gr;           \
       pp.f -= lr * bb.f;                             \
     }
@@ -131,7 +162,8 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ p
   }
   const long long t = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n) {
-    const float gr = g[t] + wd * p[t];
+    const float gc = CLIP ? pp_mul_rounded(g[t], coef) : g[t];
+    const float gr = gc + wd * p[t];
     const float b1 = first ? gr : mom * buf[t] + gr;
     buf[t] = b1;
     p[t] -= lr * b1;
@@ -140,15 +172,19 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ p
 
 static int sgd_step_impl(float* p, const float* g, float* buf, long long n, float lr, float momentum,
                          float weight_decay, int step, int* skip, void* stream, int* step_dev = nullptr,
-                         const float* lr_dev = nullptr, int count_skip = 0) {
+                         const float* lr_dev = nullptr, int count_skip = 0, const float* clip_dev = nullptr) {
   hipStream_t s = (hipStream_t)stream;
   PP_CHECK_ARG(p && g && buf && n > 0 && (step >= 1 || step_dev), "sgd_momentum_step: bad arguments");
   PP_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0, "sgd_momentum_step: slabs must be 16-byte aligned");
   int blocks = pp_cdiv(n / 4 + 1, 256);
   if (blocks > 4096) blocks = 4096;
   pp_prof_begin(PP_K_OPTIM, 0.0, 20.0 * (double)n, s);
-  hipLaunchKernelGGL(sgd_momentum_kernel, dim3(blocks), dim3(256), 0, s, p, g, buf, n, lr, momentum, weight_decay,
-                     step == 1 ? 1 : 0, skip, (const int*)step_dev, lr_dev);
+  if (clip_dev)
+    hipLaunchKernelGGL(sgd_momentum_kernel<true>, dim3(blocks), dim3(256), 0, s, p, g, buf, n, lr, momentum, weight_decay,
+                       step == 1 ? 1 : 0, skip, (const int*)step_dev, lr_dev, clip_dev);
+  else
+    hipLaunchKernelGGL(sgd_momentum_kernel<false>, dim3(blocks), dim3(256), 0, s, p, g, buf, n, lr, momentum, weight_decay,
+                       step == 1 ? 1 : 0, skip, (const int*)step_dev, lr_dev, clip_dev);
   if (step_dev) hipLaunchKernelGGL(optim_commit_kernel, dim3(1), dim3(1), 0, s, step_dev, skip, count_skip);
   pp_prof_end(s);
   return pp_launch_status("sgd_momentum_step");
@@ -167,6 +203,106 @@ extern "C" int pp_sgd_momentum_step_dev(float* p, const float* g, float* buf, lo
                                         float momentum, float weight_decay, int* step_dev, int* skip, int count_skip, void* stream) {
   PP_CHECK_ARG(step_dev, "sgd_momentum_step_dev: step_dev is null");
   return sgd_step_impl(p, g, buf, n, lr, momentum, weight_decay, 2, skip, stream, step_dev, lr_dev, count_skip);
+}
+extern "C" int pp_sgd_momentum_step_clip(float* p, const float* g, float* buf, long long n, float lr, const float* lr_dev,
+                                         float momentum, float weight_decay, int* step_dev, int* skip, int count_skip,
+                                         const float* clip_dev, void* stream) {
+  PP_CHECK_ARG(step_dev && clip_dev, "sgd_momentum_step_clip: step_dev or clip_dev is null");
+  return sgd_step_impl(p, g, buf, n, lr, momentum, weight_decay, 2, skip, stream, step_dev, lr_dev, count_skip, clip_dev);
+}
+
+// ---- global gradient-norm clipping (torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) semantics) ----
+// Sum of squares of one slab segment, 4 B per parameter read once.  Every element is converted to double BEFORE it is squared
+// and added, so the only fp32 rounding of the norm is the final conversion.  No floating-point atomics: the grid is a pure
+// function of n (pp_grad_sumsq_rows), every block writes ONE double to its own row and grad_clip_finalize_kernel adds the rows
+// in a fixed order -- the norm of a slab is the same bits in every run, eager or replayed from a hipGraph.
+#define PP_SUMSQ_UNROLL 4          // independent 16-byte loads in flight per thread before the first use
+#define PP_SUMSQ_MAX_ROWS 1024     // 4 blocks of 256 threads per CU
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long long n, double* __restrict__ partial) {
+  __shared__ double sh[4];
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  const long long n4 = n >> 2;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  double acc[PP_SUMSQ_UNROLL];
+#pragma unroll
+  for (int u = 0; u < PP_SUMSQ_UNROLL; ++u) acc[u] = 0.0;
+#define PP_SUMSQ4(a, q)                                                                        \
+  {                                                                                            \
+    const double x = (double)(q).x, y = (double)(q).y, z = (double)(q).z, w = (double)(q).w;   \
+    a = fma(x, x, a); a = fma(y, y, a); a = fma(z, z, a); a = fma(w, w, a);                    \
+  }
+  for (; i + (PP_SUMSQ_UNROLL - 1) * stride < n4; i += PP_SUMSQ_UNROLL * stride) {
+    float4 q[PP_SUMSQ_UNROLL];
+#pragma unroll
+    for (int u = 0; u < PP_SUMSQ_UNROLL; ++u) q[u] = g4[i + u * stride];
+#pragma unroll
+    for (int u = 0; u < PP_SUMSQ_UNROLL; ++u) PP_SUMSQ4(acc[u], q[u])
+  }
+  for (; i < n4; i += stride) {
+    const float4 q = g4[i];
+    PP_SUMSQ4(acc[0], q)
+  }
+  // tail (n not a multiple of 4): the first block's first n % 4 threads
+  const long long t = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n) {
+    const double x = (double)g[t];
+    acc[1] = fma(x, x, acc[1]);
+  }
+  double a = pp_wave_sum_d((acc[0] + acc[1]) + (acc[2] + acc[3]));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+extern "C" int pp_grad_sumsq_rows(long long n) {
+  if (n <= 0) return 0;
+  const long long want = ((n >> 2) + 1 + 256 * PP_SUMSQ_UNROLL - 1) / (256 * PP_SUMSQ_UNROLL);
+  return (int)(want > PP_SUMSQ_MAX_ROWS ? PP_SUMSQ_MAX_ROWS : want);
+}
+
+extern "C" int pp_grad_sumsq(const float* g, long long n, double* partial, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PP_CHECK_ARG(g && partial && n > 0, "grad_sumsq: bad arguments");
+  PP_CHECK_ARG(((uintptr_t)g & 15) == 0 && ((uintptr_t)partial & 7) == 0, "grad_sumsq: g must be 16-byte aligned, partial 8-byte aligned");
+  pp_prof_begin(PP_K_OPTIM, 2.0 * (double)n, 4.0 * (double)n, s);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(pp_grad_sumsq_rows(n)), dim3(256), 0, s, g, n, partial);
+  pp_prof_end(s);
+  return pp_launch_status("grad_sumsq");
+}
+
+// One block per optimizer step: total = sqrt(sum of all rows), coef = min(1, max_norm / (total + 1e-6)) -- torch's
+// clip_coef_clamped -- both formed in double and rounded once.  out2 = [total, coef]; stats = double[4]: optimizer steps seen,
+// steps with coef < 1, sum of total, max of total.  A step the overflow guard is going to skip (skip[0] != 0) leaves the
+// statistics alone (its norm is not finite).
+__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* __restrict__ partial, int rows, double max_norm,
+                                                                 const int* __restrict__ skip, float* __restrict__ out2,
+                                                                 double* __restrict__ stats) {
+  __shared__ double sh[4];
+  double a = 0.0;
+  for (int r = threadIdx.x; r < rows; r += 256) a += partial[r];      // fixed order per thread, fixed butterfly, fixed wave order
+  a = pp_wave_sum_d(a);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double total = sqrt((sh[0] + sh[1]) + (sh[2] + sh[3]));
+  const double c = max_norm / (total + 1e-6);
+  const float coef = c < 1.0 ? (float)c : 1.f;
+  out2[0] = (float)total;
+  out2[1] = coef;
+  if (skip && skip[0]) return;
+  stats[0] += 1.0;
+  if (coef < 1.f) stats[1] += 1.0;
+  stats[2] += total;
+  if (total > stats[3]) stats[3] = total;
+}
+
+extern "C" int pp_grad_clip_finalize(const double* partial, int rows, double max_norm, const int* skip, float* out2, double* stats,
+                                     void* stream) {
+  PP_CHECK_ARG(partial && out2 && stats && rows > 0, "grad_clip_finalize: bad arguments");
+  PP_CHECK_ARG(max_norm > 0.0, "grad_clip_finalize: max_norm must be positive (+inf: measure only)");
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, rows, max_norm, skip, out2, stats);
+  return pp_launch_status("grad_clip_finalize");
 }
 
 // dst (+)= src over a flat slab (gradient accumulation across bucket copies, test helper)

@@ -12,12 +12,63 @@ corrections (``torch.cuda.amp.GradScaler.step`` does not count skipped steps eit
 however many segments the step had, and nothing the kernels read per step is a host value -- which is what lets a captured
 hipGraph of the whole iteration replay correctly.  The learning rate is mirrored into a device scalar for the same reason
 (``sync_hyper``: refreshed whenever ``param_groups[i]['lr']`` changed, i.e. once per epoch).
+
+Gradient-norm clipping (``max_grad_norm``, off by default): ``torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2)``
+over the parameters that carry a gradient, with the norm and the coefficient as DEVICE scalars -- per slab one streaming
+sum-of-squares launch per active segment (double accumulation, no atomics: bit-reproducible), one finalize launch, and the update
+kernels multiply every gradient element by the coefficient as they load it.  One difference from torch: the gradient slab is NOT
+scaled in place (a second 8 B / parameter pass for nothing) -- ``p.grad`` keeps the raw gradient after ``step()``.  ``step()`` runs
+behind the all-reduce and behind ``unscale_grads``, so data-parallel ranks compute the same coefficient from the same averaged
+slab without a collective, and 16-bit storage runs clip the unscaled gradients.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
 from ._lib import lib, prof_range, stream_ptr
+
+
+def check_max_grad_norm(value):
+    """``max_grad_norm`` as the optimizers store it: None (off) or a float > 0; +inf = measure the norm, never clip."""
+    if value is None:
+        return None
+    value = float(value)
+    if math.isnan(value) or value <= 0.0:
+        raise ValueError(f'max_grad_norm must be None (off) or > 0 (inf: measure only), got {value!r}')
+    return value
+
+
+def _nonneg_float(text):
+    import argparse
+    v = float(text)
+    if math.isnan(v) or v < 0.0:
+        raise argparse.ArgumentTypeError(f'must be >= 0 (0 = off, inf = measure only), got {text!r}')
+    return v
+
+
+def add_clip_flag(parser) -> None:
+    """``--clip_grad_norm X`` of both training drivers (0 = off; resume.py knows this default for state files older than the flag)."""
+    parser.add_argument('--clip_grad_norm', type=_nonneg_float, default=0.0,
+                        help='clip the global L2 norm of the gradients to this value before every optimizer step '
+                             '(torch.nn.utils.clip_grad_norm_ semantics, computed on the device; p.grad itself is not scaled); '
+                             'inf: only measure and log the norm; 0 = off')
+
+
+def log_clip_stats(optimizer, epoch: int, scalars=None, log=None) -> None:
+    """Per epoch, where the epoch already synchronised: the gradient-norm statistics of a run with --clip_grad_norm, as a log
+    line and as train/grad_norm, train/grad_norm_max, train/grad_clipped_frac; the statistics start over.  Nothing when off."""
+    st = optimizer.clip_stats(reset=True)
+    if st is None:
+        return
+    if log is not None:
+        log("epoch: {:03d}, grad_norm mean / max: {:.6f} / {:.6f}, {} of {} steps clipped".format(
+            epoch, st['mean_norm'], st['max_norm'], st['clipped'], st['steps']))
+    if scalars is not None:
+        scalars.add('train/grad_norm', st['mean_norm'], epoch)
+        scalars.add('train/grad_norm_max', st['max_norm'], epoch)
+        scalars.add('train/grad_clipped_frac', st['clipped'] / max(st['steps'], 1), epoch)
 
 
 class _SlabOptimizer(torch.optim.Optimizer):
@@ -62,6 +113,69 @@ class _SlabOptimizer(torch.optim.Optimizer):
                 if p.is_cuda:
                     self.lr_scalar(group, p.device)
                     break
+
+    # ---- gradient-norm clipping ---------------------------------------------------------------------------------
+    def _clip_buffers(self, flat, state) -> dict:
+        """Scratch rows, [norm, coefficient] and the statistics block of one slab: allocated once (their addresses are baked into
+        a captured hipGraph), rows for every segment of the slab so that any set of active segments fits."""
+        clip = state.get('clip')
+        if clip is None:
+            dev = flat.params.device
+            rows = sum(int(lib.pp_grad_sumsq_rows(b - a)) for a, b in flat.segments.values())
+            clip = dict(partial=torch.zeros(rows, device=dev, dtype=torch.float64),
+                        out2=torch.zeros(2, device=dev, dtype=torch.float32),
+                        stats=torch.zeros(4, device=dev, dtype=torch.float64))      # steps, clipped, sum of norms, max norm
+            state['clip'] = clip
+        return clip
+
+    def _clip_launch(self, group, flat, state, active, skip, st):
+        """With ``group['max_grad_norm']`` set: enqueue the norm of the active segments of `flat` and the clip coefficient;
+        returns the address of the coefficient for the ``*_step_clip`` launches (None: clipping is off, nothing was enqueued).
+        Segment ranges include the slab's alignment padding: that padding is zero in ``flat.grads`` -- the slab is allocated with
+        ``torch.zeros`` and written only through the parameter views, the whole-segment loss-scale removal (0 * x = 0) and the
+        all-reduce (a sum of zeros) -- so it adds nothing to the sum of squares (tests/test_gpu_clip.py checks the norm against
+        the parameters' own gradients)."""
+        max_norm = check_max_grad_norm(group.get('max_grad_norm'))
+        if max_norm is None:
+            return None
+        clip = self._clip_buffers(flat, state)
+        rows = 0
+        for name, a, b, _ in active:
+            lib.pp_grad_sumsq(flat.grads.data_ptr() + 4 * a, b - a, clip['partial'].data_ptr() + 8 * rows, st)
+            rows += int(lib.pp_grad_sumsq_rows(b - a))
+        lib.pp_grad_clip_finalize(clip['partial'].data_ptr(), rows, max_norm, skip, clip['out2'].data_ptr(),
+                                  clip['stats'].data_ptr(), st)
+        return clip['out2'].data_ptr() + 4
+
+    def _clip_state(self):
+        for state in self._slabs.values():
+            if 'clip' in state and any(g.get('max_grad_norm') is not None for g in self.param_groups):
+                return state['clip']
+        return None
+
+    @property
+    def last_grad_norm(self):
+        """Global L2 norm of the gradients of the last ``step()``, before clipping: a 1-element fp32 device tensor (no host sync);
+        None when ``max_grad_norm`` is off or no step ran yet."""
+        clip = self._clip_state()
+        return None if clip is None else clip['out2'][0:1]
+
+    @property
+    def last_clip_coef(self):
+        """The coefficient min(1, max_grad_norm / (norm + 1e-6)) the last ``step()`` applied (device tensor, as last_grad_norm)."""
+        clip = self._clip_state()
+        return None if clip is None else clip['out2'][1:2]
+
+    def clip_stats(self, reset: bool = False):
+        """dict(steps, clipped, mean_norm, max_norm) over the optimizer steps since the last reset (steps the overflow guard
+        skipped are not counted); None when ``max_grad_norm`` is off.  Reads the device: call it where the epoch synchronises."""
+        clip = self._clip_state()
+        if clip is None:
+            return None
+        steps, clipped, total, mx = clip['stats'].tolist()
+        if reset:
+            clip['stats'].zero_()
+        return dict(steps=int(steps), clipped=int(clipped), mean_norm=total / steps if steps else 0.0, max_norm=mx)
 
     def _steps_host(self, state) -> dict:
         vals = state['steps_dev'].tolist()                       # one host sync (state_dict / tests only)
@@ -117,6 +231,7 @@ class _SlabOptimizer(torch.optim.Optimizer):
     def load_state_dict(self, sd):
         for g, saved in zip(self.param_groups, sd['param_groups']):
             g.update(saved)
+            g['max_grad_norm'] = check_max_grad_norm(saved.get('max_grad_norm'))      # a state dict older than the key: off
         if sd.get('slabs'):
             if len(sd['slabs']) != 1:
                 raise ValueError('expected the state of exactly one parameter slab')
@@ -133,10 +248,11 @@ class _SlabOptimizer(torch.optim.Optimizer):
 class FusedAdam(_SlabOptimizer):
     STATE_KEYS = ('m', 'v')
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
         if lr < 0 or eps < 0 or weight_decay < 0:
             raise ValueError('invalid Adam hyper-parameter')
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      max_grad_norm=check_max_grad_norm(max_grad_norm)))
         self._init_state()
 
     @torch.no_grad()
@@ -150,11 +266,16 @@ class FusedAdam(_SlabOptimizer):
                 for flat, state, active in self._segments_with_grads(group):
                     skip = flat.guard.data_ptr() if getattr(flat, 'guard_on', False) else None      # 16-bit storage: overflow guard
                     lr_dev = self.lr_scalar(group, flat.params.device).data_ptr()
+                    clip_dev = self._clip_launch(group, flat, state, active, skip, st)
                     for j, (name, a, b, step_ptr) in enumerate(active):
-                        lib.pp_adam_step_dev(flat.params.data_ptr() + 4 * a, flat.grads.data_ptr() + 4 * a,
-                                             state['m'].data_ptr() + 4 * a, state['v'].data_ptr() + 4 * a, b - a,
-                                             float(group['lr']), lr_dev, float(b1), float(b2), float(group['eps']),
-                                             float(group['weight_decay']), step_ptr, skip, 1 if j == 0 else 0, st)
+                        common = (flat.params.data_ptr() + 4 * a, flat.grads.data_ptr() + 4 * a,
+                                  state['m'].data_ptr() + 4 * a, state['v'].data_ptr() + 4 * a, b - a,
+                                  float(group['lr']), lr_dev, float(b1), float(b2), float(group['eps']),
+                                  float(group['weight_decay']), step_ptr, skip, 1 if j == 0 else 0)
+                        if clip_dev is None:
+                            lib.pp_adam_step_dev(*common, st)
+                        else:
+                            lib.pp_adam_step_clip(*common, clip_dev, st)
                     flat.version += 1
         return None
 
@@ -164,10 +285,11 @@ class FusedSGD(_SlabOptimizer):
     L2-coupled decay, dampening 0, no Nesterov, momentum buffer initialised with the first gradient."""
     STATE_KEYS = ('momentum_buffer',)
 
-    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0):
+    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, max_grad_norm=None):
         if lr < 0 or momentum < 0 or weight_decay < 0:
             raise ValueError('invalid SGD hyper-parameter')
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
+                                      max_grad_norm=check_max_grad_norm(max_grad_norm)))
         self._init_state()
 
     @torch.no_grad()
@@ -179,10 +301,14 @@ class FusedSGD(_SlabOptimizer):
             for flat, state, active in self._segments_with_grads(group):
                 skip = flat.guard.data_ptr() if getattr(flat, 'guard_on', False) else None
                 lr_dev = self.lr_scalar(group, flat.params.device).data_ptr()
+                clip_dev = self._clip_launch(group, flat, state, active, skip, st)
                 for j, (name, a, b, step_ptr) in enumerate(active):
-                    lib.pp_sgd_momentum_step_dev(flat.params.data_ptr() + 4 * a, flat.grads.data_ptr() + 4 * a,
-                                                 state['momentum_buffer'].data_ptr() + 4 * a, b - a, float(group['lr']), lr_dev,
-                                                 float(group['momentum']), float(group['weight_decay']), step_ptr, skip,
-                                                 1 if j == 0 else 0, st)
+                    common = (flat.params.data_ptr() + 4 * a, flat.grads.data_ptr() + 4 * a,
+                              state['momentum_buffer'].data_ptr() + 4 * a, b - a, float(group['lr']), lr_dev,
+                              float(group['momentum']), float(group['weight_decay']), step_ptr, skip, 1 if j == 0 else 0)
+                    if clip_dev is None:
+                        lib.pp_sgd_momentum_step_dev(*common, st)
+                    else:
+                        lib.pp_sgd_momentum_step_clip(*common, clip_dev, st)
                 flat.version += 1
         return None

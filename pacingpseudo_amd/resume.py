@@ -28,6 +28,9 @@ VERSION = 1
 # (--graph_step replays the eager step bit for bit; --root / --tag only name the run directory, and a resumed run continues in
 # the directory its state file belongs to; --gpu_augment is an accepted no-op.)
 MAY_DIFFER = frozenset({'gpu', 'num_workers', 'graph_step', 'resume', 'state_interval', 'root', 'tag', 'gpu_augment'})
+# flags that are younger than the state-file format, with their parser defaults: a state file written before the flag existed
+# lacks the key, and the run it describes computed what the default computes
+ABSENT_DEFAULTS = {'clip_grad_norm': 0.0}
 # attributes the drivers add to the namespace after parsing (not flags)
 _DERIVED = frozenset({'child', 'train_ls', 'val_ls'})
 
@@ -115,6 +118,7 @@ def check_compatible(saved: dict, new: dict, world: int, saved_world: int) -> No
         raise ResumeError(f'--resume: the run was saved with world size {saved_world} and is resumed with world size {world}; '
                           'the data shards, batch statistics and RNG streams are per rank, so the world size must match')
     keys = sorted((set(saved) | set(new)) - MAY_DIFFER)
+    saved = {**{k: v for k, v in ABSENT_DEFAULTS.items() if k in new}, **saved}
     diff = [k for k in keys if saved.get(k) != new.get(k)]
     if diff:
         raise ResumeError('--resume: these flags differ from the saved run and would change what it computes: '

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import resume
+from .optim import add_clip_flag, log_clip_stats
 
 parser = argparse.ArgumentParser(description='PacingPseudo training on MI355X (flag surface of the reference driver)')
 
@@ -144,6 +145,7 @@ parser.add_argument('--norm_op', type=str, default='batch', choices=['batch', 'g
                     help='block normaliser of the U-Net: batch = nn.BatchNorm2d (the reference); group = nn.GroupNorm(--norm_groups, C): '
                          'per-image statistics, no running state, the same function in train and eval mode (fp32 storage only)')
 parser.add_argument('--norm_groups', type=int, default=8, help='channel groups of --norm_op group; must divide every block width')
+add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
 
 
@@ -216,9 +218,10 @@ def train_interface(args, resume_state=None):
         logging.info(model)
 
     if args.optimizer == 'adam':
-        optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd)
+        optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd, max_grad_norm=args.clip_grad_norm or None)
     elif args.optimizer == 'momentum':
-        optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.wd)
+        optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.wd,
+                             max_grad_norm=args.clip_grad_norm or None)
     else:
         raise ValueError('Unimplemented optimizer')
 
@@ -372,6 +375,9 @@ def train_interface(args, resume_state=None):
                          "loss_memory: {:.6f}, {:.2f} s/epoch".format(curr_epoch, new_lr, a[0] / cnt, a[1] / cnt, a[2] / cnt,
                                                                      a[3] / cnt, a[4] / its, epoch_toc - epoch_tic))
             logging.info("throughput: {:.1f} images/sec ({} GPU)".format(n_img * world / max(epoch_toc - epoch_tic, 1e-9), world))
+        # --clip_grad_norm: the epoch's gradient-norm statistics (every rank holds the same ones: the norm is taken behind the
+        # all-reduce), read behind the sync above; every rank starts them over
+        log_clip_stats(optimizer, curr_epoch, scalars if rank == 0 else None, logging.info if rank == 0 else None)
 
         # ---- validation (train_chaos.py:369-399); model.eval() is never undone, as in the reference
         if world > 1 and model.training and not args.sync_bn:

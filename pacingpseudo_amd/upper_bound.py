@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import resume
+from .optim import add_clip_flag, log_clip_stats
 
 parser = argparse.ArgumentParser()
 parser.add_argument('--gpu', type=str, default='1')
@@ -68,6 +69,7 @@ parser.add_argument('--norm_op', type=str, default='batch', choices=['batch', 'g
                          'per-image statistics, no running state, the same function in train and eval mode (fp32 storage only)')
 parser.add_argument('--norm_groups', type=int, default=8, help='channel groups of --norm_op group; must divide every block width')
 parser.add_argument('--gpu_augment', action='store_true', help='accepted for compatibility: the GPU pipeline is the default')
+add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
 
 
@@ -90,7 +92,7 @@ def train_interface(args, resume_state=None):
                  output_stride=args.output_stride, is_stride_conv=args.is_stride_conv, is_trans_conv=args.is_trans_conv,
                  elab_end_points=args.elab_end_points, **norm_kwargs(args)).cuda()
     logging.info(model)
-    optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd)
+    optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd, max_grad_norm=args.clip_grad_norm or None)
     ds_kw = dict(num_classes=args.num_classes, size=args.image_size, seed=args.seed)
     # the reference trains the upper bound with the whole WEAK pipeline (upper_bound_chaos.py:132-137: base_transforms =
     # Scaling, Elastic, Rotation, Mirroring, GaussianNoise, RandomCrop; no strong view): the same device pipeline as
@@ -154,6 +156,7 @@ def train_interface(args, resume_state=None):
         cnt = max(a[2], 1)
         logging.info("epoch: {:03d}, lr: {:.6f}, loss_ce: {:.6f}, loss_dice: {:.6f}, {:.2f} s/epoch".format(
             curr_epoch, new_lr, a[0] / cnt, a[1] / cnt, time.time() - epoch_tic))
+        log_clip_stats(optimizer, curr_epoch, scalars, logging.info)      # --clip_grad_norm: behind the sync above
 
         model.eval()                                   # upper_bound_chaos.py:180, never undone
         tic = time.time()

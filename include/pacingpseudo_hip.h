@@ -572,6 +572,23 @@ int pp_adam_step_clip(float* p, const float* g, float* m, float* v, long long n,
 int pp_sgd_momentum_step_clip(float* p, const float* g, float* momentum_buf, long long n, float lr, const float* lr_dev,
                               float momentum, float weight_decay, int* step_dev, int* skip, int count_skip, const float* clip_dev,
                               void* stream);
+/* Exponential moving average of the weights, kept on the device by the optimizer step itself (the reference trains without one,
+ * train_chaos.py:313-315; off by default here).  ema is an fp32 slab laid out as p.  With t = the segment's update count BEFORE
+ * this update (step_dev[0]; 0 for the first), d_t = min(ema_decay, (1 + t) / (10 + t)) in double and w = (float)(1 - d_t), every
+ * element becomes ema + fl32(w * fl32(p - ema)): three separately rounded fp32 operations, the torch fp32 chain e + w * (p - e)
+ * bit for bit.  0 < ema_decay < 1.  pp_adam_step_ema / pp_sgd_momentum_step_ema = the *_dev forms (clip_dev null) or the *_clip
+ * forms (clip_dev set) whose kernel also loads ema, moves it towards the p it has just computed and stores it (8 B / parameter
+ * more); a step the overflow guard skips leaves ema untouched, and t does not advance.  pp_ema_update: the same rule as a pass
+ * of its own over p[0..n) (not written) and ema[0..n), t = step_dev[0] when step_dev is set, else t_host >= 0.  pp_slab_swap:
+ * a[0..n) <-> b[0..n) in place (disjoint, 16-byte aligned), how the averaged weights are put where the live ones are. */
+int pp_adam_step_ema(float* p, const float* g, float* m, float* v, long long n, float lr, const float* lr_dev, float beta1,
+                     float beta2, float eps, float weight_decay, int* step_dev, int* skip, int count_skip, float* ema,
+                     double ema_decay, const float* clip_dev, void* stream);
+int pp_sgd_momentum_step_ema(float* p, const float* g, float* momentum_buf, long long n, float lr, const float* lr_dev,
+                             float momentum, float weight_decay, int* step_dev, int* skip, int count_skip, float* ema,
+                             double ema_decay, const float* clip_dev, void* stream);
+int pp_ema_update(const float* p, float* ema, long long n, double ema_decay, const int* step_dev, long long t_host, void* stream);
+int pp_slab_swap(float* a, float* b, long long n, void* stream);
 
 /* ---- diagnostics -------------------------------------------------------------------------------------------- */
 /* bare v_mfma_f32_32x32x2_f32 loop: the fp32 matrix rate this device sustains at its clock under load */

@@ -184,6 +184,10 @@ _PROTOS = {
     'pp_grad_clip_finalize': (i32, [vp, i32, C.c_double, vp, vp, vp, vp]),
     'pp_adam_step_clip': (i32, [vp, vp, vp, vp, i64, f32, vp, f32, f32, f32, f32, vp, vp, i32, vp, vp]),
     'pp_sgd_momentum_step_clip': (i32, [vp, vp, vp, i64, f32, vp, f32, f32, vp, vp, i32, vp, vp]),
+    'pp_adam_step_ema': (i32, [vp, vp, vp, vp, i64, f32, vp, f32, f32, f32, f32, vp, vp, i32, vp, C.c_double, vp, vp]),
+    'pp_sgd_momentum_step_ema': (i32, [vp, vp, vp, i64, f32, vp, f32, f32, vp, vp, i32, vp, C.c_double, vp, vp]),
+    'pp_ema_update': (i32, [vp, vp, i64, C.c_double, vp, i64, vp]),
+    'pp_slab_swap': (i32, [vp, vp, i64, vp]),
     'pp_mfma_probe': (i32, [vp, i32, i32, C.POINTER(C.c_double), vp]),
     'pp_weighted_sum_fwd': (i32, [vp, vp, i32, vp, vp]),
     'pp_pack_conv3x3_weights_f16x3_batch': (i32, [vp, i32, vp]),
@@ -214,7 +218,7 @@ for _n in H16_ENTRIES:
 _H16_SET = frozenset(H16_ENTRIES) | {'pp_memory_update'}
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
-MIN_LIB_VERSION = 603      # include/pacingpseudo_hip.h with the gradient-norm clipping entry points (pp_runtime.cpp: PP_VERSION)
+MIN_LIB_VERSION = 604      # include/pacingpseudo_hip.h with the EMA weight-averaging entry points (pp_runtime.cpp: PP_VERSION)
 PROF_KINDS = ('conv_igemm', 'conv_wgrad', 'bn', 'spatial', 'loss', 'optim', 'misc', 'wino_gemm', 'wino_wgrad',
               'wino_xform', 'conv_f16x3', 'wino_gemm_f16x3', 'wino_wgrad_f16x3', 'conv_wgrad_f16x3', 'conv_halo_f16x3')
 

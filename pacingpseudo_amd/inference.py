@@ -38,6 +38,9 @@ parser.add_argument('--fold', type=int, required=True, help='test fold; must app
 parser.add_argument('--checkpoint_file', type=str, required=True,
                     help='run directory of a training session (ckps/ckp_399.pth, or ckp_39.pth for lvsc, is taken) or a .pth file')
 parser.add_argument('--best_ckp', action='store_true', default=False, help='take best_ckp.pth of the run directory instead')
+parser.add_argument('--ema', action='store_true', default=False,
+                    help='evaluate the averaged weights of a run trained with --ema_decay: ckps/ema_ckp_399.pth (ema_ckp_39.pth for '
+                         'lvsc) of the run directory, best_ema_ckp.pth with --best_ckp; the files have the ordinary keys')
 parser.add_argument('--dataset', type=str, default='acdc', choices=['acdc', 'chaost1', 'chaost2', 'lvsc'])
 parser.add_argument('--num_classes', type=int, default=None,
                     help='segmentation classes incl. background the checkpoint was trained with, 1 .. 32 (default: the --dataset preset)')
@@ -152,10 +155,11 @@ def main(argv=None):
     os.makedirs(args.child, exist_ok=True)
     if os.path.isdir(args.checkpoint_file):                    # a run directory: pick the file the reference picks (:274-284)
         run = args.checkpoint_file
+        pre = 'ema_' if args.ema else ''
         if args.best_ckp:
-            cand = [os.path.join(run, 'ckps', 'best_ckp.pth'), os.path.join(run, 'best_ckp.pth')]
+            cand = [os.path.join(run, 'ckps', f'best_{pre}ckp.pth'), os.path.join(run, f'best_{pre}ckp.pth')]
         else:
-            cand = [os.path.join(run, 'ckps', 'ckp_39.pth' if args.dataset == 'lvsc' else 'ckp_399.pth')]
+            cand = [os.path.join(run, 'ckps', pre + ('ckp_39.pth' if args.dataset == 'lvsc' else 'ckp_399.pth'))]
         found = [c for c in cand if os.path.isfile(c)]
         if not found:
             raise FileNotFoundError(f'none of {cand} exists')

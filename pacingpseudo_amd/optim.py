@@ -20,9 +20,18 @@ kernels multiply every gradient element by the coefficient as they load it.  One
 scaled in place (a second 8 B / parameter pass for nothing) -- ``p.grad`` keeps the raw gradient after ``step()``.  ``step()`` runs
 behind the all-reduce and behind ``unscale_grads``, so data-parallel ranks compute the same coefficient from the same averaged
 slab without a collective, and 16-bit storage runs clip the unscaled gradients.
+
+EMA of the weights (``ema_decay``, off by default): every slab the optimizer updates gets an fp32 shadow slab ``ema``, created with
+the moments and initialised from the parameters, and the ``*_step_ema`` kernels move it towards the parameters they have just
+computed: ``e += fl32(w * fl32(p - e))``, ``w = fl32(1 - min(D, (1 + t) / (10 + t)))`` with t the segment's device step count
+before the update (``ema_warmup_weight``).  Nothing of it is a host value but D, so it replays from a hipGraph, respects the
+overflow guard (a skipped step leaves the shadow and t alone) and travels with ``state_dict()``.  Training does not depend on it.
+Slab ranges the optimizer never updated are not averaged.  ``ema_weights()`` swaps the average in for evaluation,
+``ema_state_dict(model)`` reads the model as it stands then.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 
 import torch
@@ -40,6 +49,23 @@ def check_max_grad_norm(value):
     return value
 
 
+def check_ema_decay(value):
+    """``ema_decay`` as the optimizers store it: None (off) or a float with 0 < D < 1."""
+    if value is None:
+        return None
+    value = float(value)
+    if math.isnan(value) or not 0.0 < value < 1.0:
+        raise ValueError(f'ema_decay must be None (off) or lie strictly between 0 and 1, got {value!r}')
+    return value
+
+
+def ema_warmup_weight(t: int, decay: float) -> float:
+    """The weight w of the update ``e += w * (p - e)`` that follows t earlier updates, as the kernels form it: d_t = min(D,
+    (1 + t) / (10 + t)) in double, w = 1 - d_t rounded once to fp32 (returned as the python float of that fp32 value)."""
+    t = float(int(t))
+    return float(torch.tensor(1.0 - min(float(decay), (1.0 + t) / (10.0 + t)), dtype=torch.float64).to(torch.float32))
+
+
 def _nonneg_float(text):
     import argparse
     v = float(text)
@@ -54,6 +80,33 @@ def add_clip_flag(parser) -> None:
                         help='clip the global L2 norm of the gradients to this value before every optimizer step '
                              '(torch.nn.utils.clip_grad_norm_ semantics, computed on the device; p.grad itself is not scaled); '
                              'inf: only measure and log the norm; 0 = off')
+
+
+def _decay_float(text):
+    import argparse
+    v = float(text)
+    if math.isnan(v) or not 0.0 <= v < 1.0:
+        raise argparse.ArgumentTypeError(f'must be 0 (off) or lie strictly between 0 and 1, got {text!r}')
+    return v
+
+
+def _positive_int(text):
+    import argparse
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f'must be >= 1, got {text!r}')
+    return v
+
+
+def add_ema_flags(parser) -> None:
+    """``--ema_decay D`` / ``--ema_val_interval N`` of both training drivers (0 = off; resume.py knows the defaults for state files
+    older than the flags)."""
+    parser.add_argument('--ema_decay', type=_decay_float, default=0.0,
+                        help='keep an exponential moving average of the weights with this decay, updated on the device by the '
+                             'optimizer step (warm-up min(D, (1 + t) / (10 + t))), validate it beside the live weights and write '
+                             'ckps/ema_ckp_<e>.pth / best_ema_ckp.pth; training itself does not depend on it; 0 = off')
+    parser.add_argument('--ema_val_interval', type=_positive_int, default=1,
+                        help='with --ema_decay: validate the averaged weights every this many epochs (and after the last one)')
 
 
 def log_clip_stats(optimizer, epoch: int, scalars=None, log=None) -> None:
@@ -177,6 +230,71 @@ class _SlabOptimizer(torch.optim.Optimizer):
             clip['stats'].zero_()
         return dict(steps=int(steps), clipped=int(clipped), mean_norm=total / steps if steps else 0.0, max_norm=mx)
 
+    # ---- EMA of the weights --------------------------------------------------------------------------------------
+    def _ema_on(self) -> bool:
+        return any(g.get('ema_decay') is not None for g in self.param_groups)
+
+    def _ema_slab(self, state, saved=None) -> torch.Tensor:
+        """The shadow slab of one parameter slab: allocated once (its address is baked into a captured hipGraph), bit for bit the
+        parameters of that moment -- or `saved`, the shadow of a loaded state."""
+        ema = state.get('ema')
+        if ema is None:
+            ema = state['flat'].params.detach().clone()
+            state['ema'] = ema
+        if saved is not None:
+            ema.copy_(saved.to(ema.device))
+        return ema
+
+    def _ema_ptr(self, group, state):
+        """Address of the shadow slab for the ``*_step_ema`` launches of `group`; None: ``ema_decay`` is off, today's entry points."""
+        if check_ema_decay(group.get('ema_decay')) is None:
+            return None
+        return self._ema_slab(state).data_ptr()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate on the averaged weights: inside the context the parameter slab holds the EMA and the shadow holds the live
+        weights (swapped in place on the device, no third copy); on exit they are swapped back, whatever happened inside.  Only the
+        segments the optimizer has updated are swapped -- every other parameter, and every buffer (BatchNorm running statistics),
+        stays the live model's.  ``flat.version`` is bumped both ways, so forward-only plans pack the weights they are about to
+        use.  Do not train inside the context.  Not re-entrant; not capturable."""
+        if not self._ema_on():
+            raise RuntimeError('ema_weights(): ema_decay is off')
+        if getattr(self, '_ema_swapped', False):
+            raise RuntimeError('ema_weights() is not re-entrant: the parameter slab already holds the averaged weights')
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ema_weights() cannot run during a stream capture (it reads the step counts on the host)')
+        todo = []
+        for state in self._slabs.values():
+            if 'ema' not in state:
+                continue
+            flat, done = state['flat'], self._steps_host(state)
+            ranges = [flat.segments[name] for name in state['names'] if name in done]
+            if ranges:
+                todo.append((flat, state['ema'], ranges))
+
+        def swap():
+            for flat, ema, ranges in todo:
+                with torch.cuda.device(flat.params.device):
+                    for a, b in ranges:
+                        lib.pp_slab_swap(flat.params.data_ptr() + 4 * a, ema.data_ptr() + 4 * a, b - a, stream_ptr())
+                flat.version += 1
+        self._ema_swapped = True
+        try:
+            swap()
+            yield self
+        finally:
+            try:
+                swap()
+            finally:
+                self._ema_swapped = False
+
+    def ema_state_dict(self, model) -> dict:
+        """``model.state_dict()`` as it reads inside ``ema_weights()``: the same keys, host tensors (averaged parameters; everything
+        the optimizer does not update, the buffers included, from the live model)."""
+        with self.ema_weights():
+            return {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+
     def _steps_host(self, state) -> dict:
         vals = state['steps_dev'].tolist()                       # one host sync (state_dict / tests only)
         return {name: int(vals[i]) for i, name in enumerate(state['names']) if vals[i] > 0}
@@ -205,11 +323,14 @@ class _SlabOptimizer(torch.optim.Optimizer):
                 state = {k: torch.zeros_like(flat.params) for k in self.STATE_KEYS}
                 state['names'] = list(flat.segments)
                 state['steps_dev'] = torch.zeros(len(state['names']), device=flat.params.device, dtype=torch.int32)
+                state['flat'] = flat
                 if self._pending is not None:
                     for k in self.STATE_KEYS:
                         state[k].copy_(self._pending[k].to(flat.params.device))
                     self._set_steps(state, self._pending['steps'])
-                    self._pending = None
+                if self._ema_on():
+                    self._ema_slab(state, None if self._pending is None else self._pending.get('ema'))
+                self._pending = None
                 self._slabs[id(flat)] = state
             active = []
             for i, (name, (a, b)) in enumerate(flat.segments.items()):
@@ -226,12 +347,17 @@ class _SlabOptimizer(torch.optim.Optimizer):
         sd = dict(param_groups=[{k: v for k, v in g.items() if k != 'params'} for g in self.param_groups])
         sd['slabs'] = [dict({k: st[k].detach().cpu() for k in self.STATE_KEYS}, steps=self._steps_host(st))
                        for st in self._slabs.values()]
+        if self._ema_on():                    # off: exactly the keys above
+            for out, st in zip(sd['slabs'], self._slabs.values()):
+                if 'ema' in st:
+                    out['ema'] = st['ema'].detach().cpu()
         return sd
 
     def load_state_dict(self, sd):
         for g, saved in zip(self.param_groups, sd['param_groups']):
             g.update(saved)
             g['max_grad_norm'] = check_max_grad_norm(saved.get('max_grad_norm'))      # a state dict older than the key: off
+            g['ema_decay'] = check_ema_decay(saved.get('ema_decay'))                  # the same
         if sd.get('slabs'):
             if len(sd['slabs']) != 1:
                 raise ValueError('expected the state of exactly one parameter slab')
@@ -241,6 +367,8 @@ class _SlabOptimizer(torch.optim.Optimizer):
                 for k in self.STATE_KEYS:
                     cur[k].copy_(st[k].to(cur[k].device))
                 self._set_steps(cur, st['steps'])
+                if self._ema_on():            # a state without a shadow: the average starts from the current parameters
+                    self._ema_slab(cur, st['ema'] if 'ema' in st else cur['flat'].params)
             else:
                 self._pending = st
 
@@ -248,11 +376,11 @@ class _SlabOptimizer(torch.optim.Optimizer):
 class FusedAdam(_SlabOptimizer):
     STATE_KEYS = ('m', 'v')
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None):
         if lr < 0 or eps < 0 or weight_decay < 0:
             raise ValueError('invalid Adam hyper-parameter')
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      max_grad_norm=check_max_grad_norm(max_grad_norm)))
+                                      max_grad_norm=check_max_grad_norm(max_grad_norm), ema_decay=check_ema_decay(ema_decay)))
         self._init_state()
 
     @torch.no_grad()
@@ -267,12 +395,15 @@ class FusedAdam(_SlabOptimizer):
                     skip = flat.guard.data_ptr() if getattr(flat, 'guard_on', False) else None      # 16-bit storage: overflow guard
                     lr_dev = self.lr_scalar(group, flat.params.device).data_ptr()
                     clip_dev = self._clip_launch(group, flat, state, active, skip, st)
+                    ema = self._ema_ptr(group, state)
                     for j, (name, a, b, step_ptr) in enumerate(active):
                         common = (flat.params.data_ptr() + 4 * a, flat.grads.data_ptr() + 4 * a,
                                   state['m'].data_ptr() + 4 * a, state['v'].data_ptr() + 4 * a, b - a,
                                   float(group['lr']), lr_dev, float(b1), float(b2), float(group['eps']),
                                   float(group['weight_decay']), step_ptr, skip, 1 if j == 0 else 0)
-                        if clip_dev is None:
+                        if ema is not None:
+                            lib.pp_adam_step_ema(*common, ema + 4 * a, group['ema_decay'], clip_dev, st)
+                        elif clip_dev is None:
                             lib.pp_adam_step_dev(*common, st)
                         else:
                             lib.pp_adam_step_clip(*common, clip_dev, st)
@@ -285,11 +416,11 @@ class FusedSGD(_SlabOptimizer):
     L2-coupled decay, dampening 0, no Nesterov, momentum buffer initialised with the first gradient."""
     STATE_KEYS = ('momentum_buffer',)
 
-    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, max_grad_norm=None):
+    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, max_grad_norm=None, ema_decay=None):
         if lr < 0 or momentum < 0 or weight_decay < 0:
             raise ValueError('invalid SGD hyper-parameter')
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
-                                      max_grad_norm=check_max_grad_norm(max_grad_norm)))
+                                      max_grad_norm=check_max_grad_norm(max_grad_norm), ema_decay=check_ema_decay(ema_decay)))
         self._init_state()
 
     @torch.no_grad()
@@ -302,11 +433,14 @@ class FusedSGD(_SlabOptimizer):
                 skip = flat.guard.data_ptr() if getattr(flat, 'guard_on', False) else None
                 lr_dev = self.lr_scalar(group, flat.params.device).data_ptr()
                 clip_dev = self._clip_launch(group, flat, state, active, skip, st)
+                ema = self._ema_ptr(group, state)
                 for j, (name, a, b, step_ptr) in enumerate(active):
                     common = (flat.params.data_ptr() + 4 * a, flat.grads.data_ptr() + 4 * a,
                               state['momentum_buffer'].data_ptr() + 4 * a, b - a, float(group['lr']), lr_dev,
                               float(group['momentum']), float(group['weight_decay']), step_ptr, skip, 1 if j == 0 else 0)
-                    if clip_dev is None:
+                    if ema is not None:
+                        lib.pp_sgd_momentum_step_ema(*common, ema + 4 * a, group['ema_decay'], clip_dev, st)
+                    elif clip_dev is None:
                         lib.pp_sgd_momentum_step_dev(*common, st)
                     else:
                         lib.pp_sgd_momentum_step_clip(*common, clip_dev, st)

@@ -26,11 +26,13 @@ VERSION = 1
 
 # flags that select where a run writes or how its host side is organised, never what it computes: they may differ on resume.
 # (--graph_step replays the eager step bit for bit; --root / --tag only name the run directory, and a resumed run continues in
-# the directory its state file belongs to; --gpu_augment is an accepted no-op.)
-MAY_DIFFER = frozenset({'gpu', 'num_workers', 'graph_step', 'resume', 'state_interval', 'root', 'tag', 'gpu_augment'})
+# the directory its state file belongs to; --gpu_augment is an accepted no-op; --ema_val_interval only says how often the
+# averaged weights are looked at.)
+MAY_DIFFER = frozenset({'gpu', 'num_workers', 'graph_step', 'resume', 'state_interval', 'root', 'tag', 'gpu_augment',
+                        'ema_val_interval'})
 # flags that are younger than the state-file format, with their parser defaults: a state file written before the flag existed
 # lacks the key, and the run it describes computed what the default computes
-ABSENT_DEFAULTS = {'clip_grad_norm': 0.0}
+ABSENT_DEFAULTS = {'clip_grad_norm': 0.0, 'ema_decay': 0.0, 'ema_val_interval': 1}
 # attributes the drivers add to the namespace after parsing (not flags)
 _DERIVED = frozenset({'child', 'train_ls', 'val_ls'})
 
@@ -192,11 +194,20 @@ def prime_persistent_loaders(loaders) -> None:
 
 
 # ---- the state file ----------------------------------------------------------------------------------------------------------
-def capture(args, epoch: int, model, optimizer, best, valdice, rngs, world: int) -> dict:
+def capture(args, epoch: int, model, optimizer, best, valdice, rngs, world: int, ema=None) -> dict:
+    """`ema` (runs with --ema_decay only): (dict(avg, epoch, avg_class) of the best averaged-weights validation, valdice_ema);
+    the shadow slab itself travels in ``optimizer.state_dict()``.  Without it the state has exactly the keys it always had."""
     flat = getattr(model, 'flat', None)
     engine = getattr(model, 'engine', None)
     best_avg, best_epoch, best_avg_class = best
+    extra = {}
+    if ema is not None:
+        best_ema, valdice_ema = ema
+        extra = dict(best_ema_avg=float(best_ema['avg']), best_ema_epoch=int(best_ema['epoch']),
+                     best_ema_avg_class=[float(v) for v in best_ema['avg_class']],
+                     valdice_ema=torch.from_numpy(np.asarray(valdice_ema[:epoch + 1], dtype=np.float64).copy()))
     return dict(
+        **extra,
         format=FORMAT, version=VERSION, args=flag_dict(args), world_size=int(world), epoch=int(epoch),
         model={k: v.detach().cpu() for k, v in model.state_dict().items()},
         optimizer=optimizer.state_dict(),
@@ -226,6 +237,13 @@ def restore(st: dict, model, optimizer, valdice):
     e = int(st['epoch'])
     valdice[:e + 1] = st['valdice'].numpy()
     return st['best_avg'], st['best_epoch'], list(st['best_avg_class'])
+
+
+def restore_ema(st: dict, valdice_ema) -> dict:
+    """The best-EMA bookkeeping of a run with --ema_decay (restore() has loaded the shadow slab with the optimizer)."""
+    e = int(st['epoch'])
+    valdice_ema[:e + 1] = st['valdice_ema'].numpy()
+    return dict(avg=st['best_ema_avg'], epoch=st['best_ema_epoch'], avg_class=list(st['best_ema_avg_class']))
 
 
 def open_state(parser, args, world: int):

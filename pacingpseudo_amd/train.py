@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import resume
-from .optim import add_clip_flag, log_clip_stats
+from .optim import add_clip_flag, add_ema_flags, log_clip_stats
 
 parser = argparse.ArgumentParser(description='PacingPseudo training on MI355X (flag surface of the reference driver)')
 
@@ -146,6 +146,7 @@ parser.add_argument('--norm_op', type=str, default='batch', choices=['batch', 'g
                          'per-image statistics, no running state, the same function in train and eval mode (fp32 storage only)')
 parser.add_argument('--norm_groups', type=int, default=8, help='channel groups of --norm_op group; must divide every block width')
 add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
+add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
 
 
@@ -218,10 +219,11 @@ def train_interface(args, resume_state=None):
         logging.info(model)
 
     if args.optimizer == 'adam':
-        optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd, max_grad_norm=args.clip_grad_norm or None)
+        optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd, max_grad_norm=args.clip_grad_norm or None,
+                              ema_decay=args.ema_decay or None)
     elif args.optimizer == 'momentum':
         optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.wd,
-                             max_grad_norm=args.clip_grad_norm or None)
+                             max_grad_norm=args.clip_grad_norm or None, ema_decay=args.ema_decay or None)
     else:
         raise ValueError('Unimplemented optimizer')
 
@@ -269,15 +271,34 @@ def train_interface(args, resume_state=None):
     names = _class_names(args.num_classes, args.dataset)
     scalars = ScalarLog(os.path.join(args.child, 'tb_summary', 'scalars.jsonl')) if rank == 0 else None
     valdice = np.zeros(args.epoch)
+    # --ema_decay: the same bookkeeping a second time for the averaged weights (epochs without an EMA validation pass stay 0)
+    ema_on = bool(args.ema_decay)
+    valdice_ema = np.zeros(args.epoch) if ema_on else None
+    best_ema = dict(avg=0, epoch=0, avg_class=[])
     graph_step = None                            # --graph_step: pacingpseudo_amd.graph.GraphedStep, built on first use
     aug_stream = torch.cuda.Stream() if (augmenter is not None and os.environ.get('PP_AUG_STREAM', '1') != '0') else None
     start_epoch = 0
     if resume_state is not None:
         best_avg, best_epoch, best_avg_class = resume.restore(resume_state, model, optimizer, valdice)
+        if ema_on:
+            best_ema = resume.restore_ema(resume_state, valdice_ema)
         train_dataset.set_epoch(0)                 # what the uninterrupted run's persistent workers were forked with
         resume.prime_persistent_loaders([train_loader, val_loader])
         resume.set_rng_states(resume_state['rng'][rank], device, augmenter)
         start_epoch = resume_state['epoch'] + 1
+
+    def validate():
+        """One pass over this rank's share of the validation slices with the weights the model holds: (per-class Dice, loss_pce)."""
+        meters = ValAccumulator(args.num_classes, device)
+        for groups in val_loader:
+            for batch in groups:                   # same-shape groups of one loader batch (collate_by_shape)
+                batch = expand_compact(batch, args.num_classes, device)      # uint8 class maps -> one-hot planes, on the device
+                with torch.no_grad():
+                    net_outputs = model(batch, mode='val')
+                meters.update(net_outputs['segmentation/logits'], batch['label'], net_outputs['loss_pce'])
+        dsc, loss_pce_val, _ = meters.result(parallel.all_reduce_sum if world > 1 else None)   # the one host sync
+        return dsc, loss_pce_val
+
     for curr_epoch in range(start_epoch, args.epoch):
         epoch_tic = time.time()
         if sampler is not None:
@@ -383,15 +404,8 @@ def train_interface(args, resume_state=None):
         if world > 1 and model.training and not args.sync_bn:
             parallel.sync_bn_buffers(model)        # per-rank epoch-0 statistics -> one set of running buffers
         model.eval()
-        meters = ValAccumulator(args.num_classes, device)
         tic = time.time()
-        for groups in val_loader:
-            for batch in groups:                   # same-shape groups of one loader batch (collate_by_shape)
-                batch = expand_compact(batch, args.num_classes, device)      # uint8 class maps -> one-hot planes, on the device
-                with torch.no_grad():
-                    net_outputs = model(batch, mode='val')
-                meters.update(net_outputs['segmentation/logits'], batch['label'], net_outputs['loss_pce'])
-        dsc, loss_pce_val, _ = meters.result(parallel.all_reduce_sum if world > 1 else None)   # the one host sync
+        dsc, loss_pce_val = validate()
         toc = time.time()
         avg_all = np.mean([dsc[_] for _ in range(1, args.num_classes)])
         if rank == 0:
@@ -418,16 +432,50 @@ def train_interface(args, resume_state=None):
                 best_epoch, best_avg = curr_epoch, avg_all
                 best_avg_class = [dsc[_] for _ in range(1, args.num_classes)]
                 torch.save(model.state_dict(), args.child + '/best_ckp.pth')
+        # ---- --ema_decay: the same validation on the averaged weights, swapped in place for the pass (every rank swaps its own
+        # identical slab and scores its share; BatchNorm running statistics stay the live model's), and the EMA checkpoints
+        last = curr_epoch + 1 == args.epoch
+        ema_val = ema_on and (last or (curr_epoch + 1) % args.ema_val_interval == 0)
+        ema_ckp = ema_on and (last or (curr_epoch + 1) % args.ckp_interval == 0)
+        if ema_val or ema_ckp:
+            with optimizer.ema_weights():
+                if ema_val:
+                    tic = time.time()
+                    dsc_e, loss_e = validate()
+                    toc = time.time()
+                    avg_e = np.mean([dsc_e[_] for _ in range(1, args.num_classes)])
+                    valdice_ema[curr_epoch] = avg_e
+                    if rank == 0:
+                        logging.info("val_ema: {:03d}, loss_pce: {:.6f}, time: {:.2f} s/epoch".format(curr_epoch, loss_e, toc - tic))
+                        logging.info("[" + ", ".join("{}: {:.4f}".format(nm, dsc_e[i]) for i, nm in enumerate(names))
+                                     + ", All: {:.4f}] (EMA)".format(avg_e))
+                        for i, nm in enumerate(names):
+                            scalars.add(f'DSC_EMA/{nm}', dsc_e[i], curr_epoch)
+                        scalars.add('DSC_EMA/All', avg_e, curr_epoch)
+                        scalars.add('DSC_EMA/Best', max(best_ema['avg'], avg_e), curr_epoch)
+                    if avg_e > best_ema['avg']:
+                        best_ema = dict(avg=avg_e, epoch=curr_epoch, avg_class=[dsc_e[_] for _ in range(1, args.num_classes)])
+                        if rank == 0:
+                            torch.save(model.state_dict(), args.child + '/best_ema_ckp.pth')
+                if ema_ckp and rank == 0:
+                    torch.save(model.state_dict(), os.path.join(args.child, 'ckps', 'ema_ckp_{:d}.pth'.format(curr_epoch)))
         if args.state_interval and ((curr_epoch + 1) % args.state_interval == 0 or curr_epoch + 1 == args.epoch):
             rngs = resume.gather_rng_states(device, augmenter, world)          # every rank's generators (a collective)
             if rank == 0:
                 resume.atomic_save(resume.capture(args, curr_epoch, model, optimizer, (best_avg, best_epoch, best_avg_class),
-                                                  valdice, rngs, world), resume.state_path(args.child, curr_epoch))
+                                                  valdice, rngs, world, ema=(best_ema, valdice_ema) if ema_on else None),
+                                   resume.state_path(args.child, curr_epoch))
     if rank == 0:
         logging.info("The best at epoch: {:d}, ".format(best_epoch)
                      + ", ".join("{}: {:.4f}".format(nm, v) for nm, v in zip(names[1:], best_avg_class))
                      + ", All: {:.4f}".format(best_avg))
-        np.savez(os.path.join(args.child, 'valdice'), valdice=valdice)
+        if ema_on:
+            logging.info("The best EMA at epoch: {:d}, ".format(best_ema['epoch'])
+                         + ", ".join("{}: {:.4f}".format(nm, v) for nm, v in zip(names[1:], best_ema['avg_class']))
+                         + ", All: {:.4f}".format(best_ema['avg']))
+            np.savez(os.path.join(args.child, 'valdice'), valdice=valdice, valdice_ema=valdice_ema)
+        else:
+            np.savez(os.path.join(args.child, 'valdice'), valdice=valdice)
     return valdice
 
 

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import resume
-from .optim import add_clip_flag, log_clip_stats
+from .optim import add_clip_flag, add_ema_flags, log_clip_stats
 
 parser = argparse.ArgumentParser()
 parser.add_argument('--gpu', type=str, default='1')
@@ -70,6 +70,7 @@ parser.add_argument('--norm_op', type=str, default='batch', choices=['batch', 'g
 parser.add_argument('--norm_groups', type=int, default=8, help='channel groups of --norm_op group; must divide every block width')
 parser.add_argument('--gpu_augment', action='store_true', help='accepted for compatibility: the GPU pipeline is the default')
 add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
+add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
 
 
@@ -92,7 +93,8 @@ def train_interface(args, resume_state=None):
                  output_stride=args.output_stride, is_stride_conv=args.is_stride_conv, is_trans_conv=args.is_trans_conv,
                  elab_end_points=args.elab_end_points, **norm_kwargs(args)).cuda()
     logging.info(model)
-    optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd, max_grad_norm=args.clip_grad_norm or None)
+    optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd, max_grad_norm=args.clip_grad_norm or None,
+                          ema_decay=args.ema_decay or None)
     ds_kw = dict(num_classes=args.num_classes, size=args.image_size, seed=args.seed)
     # the reference trains the upper bound with the whole WEAK pipeline (upper_bound_chaos.py:132-137: base_transforms =
     # Scaling, Elastic, Rotation, Mirroring, GaussianNoise, RandomCrop; no strong view): the same device pipeline as
@@ -121,13 +123,35 @@ def train_interface(args, resume_state=None):
     if args.lr_decay not in decay:
         raise ValueError('Unimplemented learning rate decay policy.')
     valdice = np.zeros(args.epoch)
+    ema_on = bool(args.ema_decay)                  # --ema_decay: see pacingpseudo_amd/train.py
+    valdice_ema = np.zeros(args.epoch) if ema_on else None
+    best_ema = dict(avg=0, epoch=0, avg_class=[])
     aug_stream = torch.cuda.Stream() if (augmenter is not None and os.environ.get('PP_AUG_STREAM', '1') != '0') else None
     start_epoch = 0
     if resume_state is not None:
         best_avg, best_epoch, best_avg_class = resume.restore(resume_state, model, optimizer, valdice)
+        if ema_on:
+            best_ema = resume.restore_ema(resume_state, valdice_ema)
         resume.prime_persistent_loaders([train_loader, val_loader])      # see pacingpseudo_amd/train.py
         resume.set_rng_states(resume_state['rng'][0], device, augmenter)
         start_epoch = resume_state['epoch'] + 1
+
+    def validate():
+        """One pass over the validation slices with the weights the model holds: (per-class Dice, loss_ce, loss_dice)."""
+        meters = ValAccumulator(args.num_classes, device)              # Dice meters + n-weighted loss_ce, on the device
+        dsum = torch.zeros(1, device=device, dtype=torch.float64)       # n-weighted loss_dice
+        for groups in val_loader:
+            for batch in groups:
+                batch = expand_compact(batch, args.num_classes, device)      # uint8 class maps -> one-hot planes, on the device
+                image, label = batch['image'], batch['label']
+                with torch.no_grad():
+                    logits = model(image)['segmentation/logits']
+                    target = torch.argmax(label, dim=1).long()
+                    meters.update(logits, label, partial_cross_entropy_loss(logits, target, args.ignored_index))
+                    dsum += dice_loss_fn(logits, label).double() * image.shape[0]
+        dsc, val_ce, n_val = meters.result()                            # the host sync of the validation epoch
+        return dsc, val_ce, float(dsum) / max(n_val, 1)
+
     for curr_epoch in range(start_epoch, args.epoch):
         epoch_tic = time.time()
         optimizer, new_lr = decay[args.lr_decay](optimizer, curr_epoch, args.epoch, args.lr)
@@ -160,19 +184,7 @@ def train_interface(args, resume_state=None):
 
         model.eval()                                   # upper_bound_chaos.py:180, never undone
         tic = time.time()
-        meters = ValAccumulator(args.num_classes, device)              # Dice meters + n-weighted loss_ce, on the device
-        dsum = torch.zeros(1, device=device, dtype=torch.float64)       # n-weighted loss_dice
-        for groups in val_loader:
-            for batch in groups:
-                batch = expand_compact(batch, args.num_classes, device)      # uint8 class maps -> one-hot planes, on the device
-                image, label = batch['image'], batch['label']
-                with torch.no_grad():
-                    logits = model(image)['segmentation/logits']
-                    target = torch.argmax(label, dim=1).long()
-                    meters.update(logits, label, partial_cross_entropy_loss(logits, target, args.ignored_index))
-                    dsum += dice_loss_fn(logits, label).double() * image.shape[0]
-        dsc, val_ce, n_val = meters.result()                            # the host sync of the validation epoch
-        val_dice = float(dsum) / max(n_val, 1)
+        dsc, val_ce, val_dice = validate()
         avg_all = np.mean([dsc[_] for _ in range(1, args.num_classes)])
         logging.info("val: {:03d}, loss_ce: {:.6f}, loss_dice: {:.6f}, {:.2f} s/epoch".format(
             curr_epoch, val_ce, val_dice, time.time() - tic))
@@ -195,14 +207,45 @@ def train_interface(args, resume_state=None):
             best_epoch, best_avg = curr_epoch, avg_all
             best_avg_class = [dsc[_] for _ in range(1, args.num_classes)]
             torch.save(model.state_dict(), args.child + '/best_ckp.pth')
+        # --ema_decay: the validation again on the averaged weights, and the EMA checkpoints (pacingpseudo_amd/train.py)
+        last = curr_epoch + 1 == args.epoch
+        ema_val = ema_on and (last or (curr_epoch + 1) % args.ema_val_interval == 0)
+        ema_ckp = ema_on and (last or (curr_epoch + 1) % args.ckp_interval == 0)
+        if ema_val or ema_ckp:
+            with optimizer.ema_weights():
+                if ema_val:
+                    tic = time.time()
+                    dsc_e, ce_e, dice_e = validate()
+                    avg_e = np.mean([dsc_e[_] for _ in range(1, args.num_classes)])
+                    valdice_ema[curr_epoch] = avg_e
+                    logging.info("val_ema: {:03d}, loss_ce: {:.6f}, loss_dice: {:.6f}, {:.2f} s/epoch".format(
+                        curr_epoch, ce_e, dice_e, time.time() - tic))
+                    logging.info("[" + ", ".join("{}: {:.4f}".format(nm, dsc_e[i]) for i, nm in enumerate(names))
+                                 + ", All: {:.4f}] (EMA)".format(avg_e))
+                    for i, nm in enumerate(names):
+                        scalars.add(f'DSC_EMA/{nm}', dsc_e[i], curr_epoch)
+                    scalars.add('DSC_EMA/All', avg_e, curr_epoch)
+                    scalars.add('DSC_EMA/Best', max(best_ema['avg'], avg_e), curr_epoch)
+                    if avg_e > best_ema['avg']:
+                        best_ema = dict(avg=avg_e, epoch=curr_epoch, avg_class=[dsc_e[_] for _ in range(1, args.num_classes)])
+                        torch.save(model.state_dict(), args.child + '/best_ema_ckp.pth')
+                if ema_ckp:
+                    torch.save(model.state_dict(), os.path.join(args.child, 'ckps', 'ema_ckp_{:d}.pth'.format(curr_epoch)))
         if args.state_interval and ((curr_epoch + 1) % args.state_interval == 0 or curr_epoch + 1 == args.epoch):
             resume.atomic_save(resume.capture(args, curr_epoch, model, optimizer, (best_avg, best_epoch, best_avg_class), valdice,
-                                              resume.gather_rng_states(device, augmenter, 1), 1),
+                                              resume.gather_rng_states(device, augmenter, 1), 1,
+                                              ema=(best_ema, valdice_ema) if ema_on else None),
                                resume.state_path(args.child, curr_epoch))
     logging.info("The best at epoch: {:d}, ".format(best_epoch)
                  + ", ".join("{}: {:.4f}".format(nm, v) for nm, v in zip(names[1:], best_avg_class))
                  + ", All: {:.4f}".format(best_avg))
-    np.savez(os.path.join(args.child, 'valdice'), valdice=valdice)
+    if ema_on:
+        logging.info("The best EMA at epoch: {:d}, ".format(best_ema['epoch'])
+                     + ", ".join("{}: {:.4f}".format(nm, v) for nm, v in zip(names[1:], best_ema['avg_class']))
+                     + ", All: {:.4f}".format(best_ema['avg']))
+        np.savez(os.path.join(args.child, 'valdice'), valdice=valdice, valdice_ema=valdice_ema)
+    else:
+        np.savez(os.path.join(args.child, 'valdice'), valdice=valdice)
     return valdice
 
 

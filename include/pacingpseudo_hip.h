@@ -527,6 +527,24 @@ int pp_dice_loss_fwd(const float* logits, const float* label_onehot, int N, int 
 int pp_dice_loss_bwd(const float* logits, const float* label_onehot, int N, int K, int HW, const double* sums,
                      const float* g, float grad_scale, float* dlogits, int accumulate, void* stream);
 
+/* Gated CRF / Potts regulariser on the weak-view logits (this implementation's addition):
+ *   L = (1/D) sum_n sum_i sum_j m_i m_j k_ij (1 - <p_i, p_j>),  p = softmax(logits),  j = i + (dy, dx) * dilation with
+ *   dy, dx in [-radius, radius] \ (0, 0) inside the image,
+ *   k_ij = exp(-(dy^2 + dx^2) / (2 sigma_xy^2)) * exp(-|x_i - x_j|^2 / (2 sigma_rgb^2))   (|.|^2 over the C image channels)
+ * logits (N,K,H,W), image (N,C,H,W), valid_mask (N,1,H,W) or NULL (m = 1); 1 <= K <= 32, C <= 4, 1 <= radius <= 8,
+ * 1 <= dilation <= 4, radius * dilation <= 16, sigma > 0.  pp_crf_loss_fwd writes sums[0] = numerator, sums[1] = sum m (the
+ * pixel count N H W without a mask) in double, in a fixed order (no atomics); the loss is sums[0] / D with D = sums[1], clamped
+ * as max(., 1e-8) with a mask -- data-parallel callers add `sums` over the ranks first.  With unit_grad (N,K,H,W) non-NULL the
+ * same pass stores u = m_i p_ic (G_ic - <p_i, G_i>);  pp_crf_loss_bwd then ACCUMULATES
+ *   dlogits[e] += grad_scale * g_up[0] * (-2 / D) * unit_grad[e],  e < n = N K H W
+ * reading D from `sums` on the device.  No gradient flows to the image or the mask. */
+size_t pp_crf_loss_workspace(int N, int H, int W);
+int pp_crf_loss_fwd(const float* logits, const float* image, const float* valid_mask, int N, int K, int C, int H, int W,
+                    int radius, int dilation, float sigma_xy, float sigma_rgb, float* unit_grad, double* sums,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int pp_crf_loss_bwd(const float* unit_grad, const double* sums, int has_mask, const float* g_up, float grad_scale,
+                    float* dlogits, long long n, void* stream);
+
 /* ---- optimiser (torch.optim.Adam(lr, weight_decay) at train_chaos.py:219) ------------------------------- */
 int pp_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                  float eps, float weight_decay, int step, void* stream);

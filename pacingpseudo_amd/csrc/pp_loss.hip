@@ -1098,6 +1098,259 @@ extern "C" int pp_dice_loss_bwd(const float* logits, const float* label_onehot, 
   return pp_launch_status("dice_loss_bwd");
 }
 
+// ---------------------------------------------------------------- gated CRF / Potts regulariser on the weak-view logits
+//   k_ij = exp(-(dy^2 + dx^2) / (2 sxy^2)) * exp(-|x_i - x_j|^2 / (2 srgb^2)),  j = i + (dy, dx) * d,  dy, dx in [-r, r] \ (0, 0)
+//   L = (1/D) sum_i sum_j m_i m_j k_ij (1 - <p_i, p_j>),  D = N H W, or max(sum m, 1e-8) with a mask
+// k and m_i m_j are symmetric, so the derivative is a gather: with G_ic = sum_j m_j k_ij p_jc and S_i = sum_j m_j k_ij pixel i
+// adds m_i (S_i - <p_i, G_i>) to the numerator and dL/dz_ic = -(2/D) m_i p_ic (G_ic - <p_i, G_i>).
+// Forward: a block of four waves owns a 64 x 4 tile (one wave per row, one pixel per lane) and stages tile + halo r*d into LDS,
+// pixel-major with an odd row length (consecutive lanes -> distinct banks of ds_read_b32; compile-time offsets for the planes):
+// soft-max probabilities of a chunk of KC classes (full-K normaliser, evaluated while staging), the image channels, the mask
+// (0 outside the image: such a j contributes nothing).  Every lane then walks the (2r+1)^2 - 1 offsets.  Both factors of k go
+// through ONE exp2: the spatial term (dy^2 + dx^2) * a_xy is uniform over the wave and seeds the exponent the channel differences
+// are accumulated into, so no table is read in the loop.  K > KC runs in class chunks (restage, walk again, k recomputed); the
+// LDS bound picks the chunk count, so every accepted (K, C, r, d) fits.  With `unit` the pass leaves u_ic = m_i p_ic (G_ic -
+// <p_i, G_i>) for the streaming backward, which never repeats the walk.  Per block one double partial of the numerator and of
+// sum m; crf_reduce_kernel adds them in a fixed order: the same bits run after run, no atomics.
+#define CRF_TW 64
+#define CRF_TH 4
+#define CRF_THREADS (CRF_TW * CRF_TH)
+#define CRF_MAXR 8
+#define CRF_MAXD 4
+#define CRF_MAXHALO 16
+#define CRF_MAXC 4
+#define CRF_KC 8                       // largest class chunk (= the K <= 8 bound of pp_by_class_bound)
+#define CRF_LDS_MAX (160 * 1024 - 256)   // dynamic part; the block also holds 64 B of static partial sums
+
+template <int KC, int CT>              // CT: image channels (1 or 3), 0: any count up to CRF_MAXC at run time
+struct CrfLayout {
+  static constexpr int NC = CT ? CT : CRF_MAXC;
+  static constexpr int P = (KC + NC + 1) | 1;        // floats per staged pixel: [0, KC) p, [KC, KC + NC) x, [KC + NC] m
+};
+static inline size_t crf_lds_bytes(int P, int halo) {
+  return (size_t)(CRF_TW + 2 * halo) * (CRF_TH + 2 * halo) * P * sizeof(float);
+}
+
+__device__ __forceinline__ void crf_softmax_norm(const float* __restrict__ zq, int K, int HW, float& mx, float& inv) {
+  mx = -INFINITY;
+  for (int k = 0; k < K; ++k) mx = fmaxf(mx, zq[(size_t)k * HW]);
+  float s = 0.f;
+  for (int k = 0; k < K; ++k) s += expf(zq[(size_t)k * HW] - mx);
+  inv = 1.f / s;
+}
+__device__ __forceinline__ float crf_prob(float z, float mx, float inv) { return expf(z - mx) * inv; }
+
+template <int KC, int CT>
+__global__ __launch_bounds__(CRF_THREADS) void crf_fwd_kernel(
+    const float* __restrict__ z, const float* __restrict__ img, const float* __restrict__ mask, int K, int C, int H, int W, int r,
+    int d, float a_xy, float a_rgb, int nchunks, float* __restrict__ unit, double* __restrict__ partial /*[blocks][2]*/) {
+  extern __shared__ float crf_lds[];
+  __shared__ double shd[2][CRF_TH];
+  constexpr int NC = CrfLayout<KC, CT>::NC, P = CrfLayout<KC, CT>::P;
+  const int R = r * d, LW = CRF_TW + 2 * R, LH = CRF_TH + 2 * R, HW = H * W;
+  const int n = blockIdx.z, x0 = blockIdx.x * CRF_TW, y0 = blockIdx.y * CRF_TH;
+  const float* zn = z + (size_t)n * K * HW;
+  const float* xn = img + (size_t)n * C * HW;
+  const float* mn = mask ? mask + (size_t)n * HW : nullptr;
+  const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
+  const int gx = x0 + lx, gy = y0 + ly, q = gy * W + gx;
+  const bool inside = gx < W && gy < H;
+  const float* ci = crf_lds + ((ly + R) * LW + lx + R) * P;      // this lane's own pixel
+  float dot = 0.f, S = 0.f;
+  for (int ch = 0; ch < nchunks; ++ch) {
+    const int c0 = ch * KC;
+    if (ch) __syncthreads();                                       // every lane is through with the previous chunk
+    for (int s = threadIdx.x; s < LW * LH; s += CRF_THREADS) {
+      const int sy = s / LW, sx = s - sy * LW;
+      const int py = y0 - R + sy, px = x0 - R + sx;
+      float* o = crf_lds + s * P;
+      if (px >= 0 && px < W && py >= 0 && py < H) {
+        const int sq = py * W + px;
+        if (nchunks == 1) {                                        // K <= KC: one load per logit
+          float v[KC];
+          float mx = -INFINITY;
+#pragma unroll
+          for (int c = 0; c < KC; ++c) { v[c] = c < K ? zn[(size_t)c * HW + sq] : -INFINITY; mx = fmaxf(mx, v[c]); }
+          float sum = 0.f;
+#pragma unroll
+          for (int c = 0; c < KC; ++c) { v[c] = c < K ? expf(v[c] - mx) : 0.f; sum += v[c]; }
+          const float inv = 1.f / sum;
+#pragma unroll
+          for (int c = 0; c < KC; ++c) o[c] = v[c] * inv;
+        } else {
+          float mx, inv;
+          crf_softmax_norm(zn + sq, K, HW, mx, inv);
+#pragma unroll
+          for (int c = 0; c < KC; ++c) o[c] = c0 + c < K ? crf_prob(zn[(size_t)(c0 + c) * HW + sq], mx, inv) : 0.f;
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) o[KC + c] = c < C ? xn[(size_t)c * HW + sq] : 0.f;
+        o[KC + NC] = mn ? mn[sq] : 1.f;
+      } else {
+#pragma unroll
+        for (int c = 0; c < KC + NC + 1; ++c) o[c] = 0.f;
+      }
+    }
+    __syncthreads();
+    float xi[NC], G[KC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) xi[c] = ci[KC + c];
+#pragma unroll
+    for (int c = 0; c < KC; ++c) G[c] = 0.f;
+    float Sc = 0.f;
+    for (int dy = -r; dy <= r; ++dy) {
+      const float* row = ci + dy * d * LW * P;
+#pragma unroll 2
+      for (int dx = -r; dx <= r; ++dx) {
+        const float* cj = row + dx * d * P;
+        float e = (float)(dy * dy + dx * dx) * a_xy;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { const float t = xi[c] - cj[KC + c]; e = __builtin_fmaf(t * t, a_rgb, e); }
+        const float k = __builtin_amdgcn_exp2f(e) * (cj[KC + NC] * ((dy | dx) ? 1.f : 0.f));      // (0, 0) is no neighbour: its mask times a uniform 0
+        Sc += k;
+#pragma unroll
+        for (int c = 0; c < KC; ++c) G[c] = __builtin_fmaf(k, cj[c], G[c]);
+      }
+    }
+    if (ch == 0) S = Sc;
+#pragma unroll
+    for (int c = 0; c < KC; ++c) dot = __builtin_fmaf(ci[c], G[c], dot);
+    if (unit && inside) {
+      float* un = unit + (size_t)n * K * HW + q;
+      if (nchunks == 1) {
+        const float mi = ci[KC + NC];
+#pragma unroll
+        for (int c = 0; c < KC; ++c) if (c < K) un[(size_t)c * HW] = mi * ci[c] * (G[c] - dot);
+      } else {
+#pragma unroll
+        for (int c = 0; c < KC; ++c) if (c0 + c < K) un[(size_t)(c0 + c) * HW] = G[c];      // finished below, once <p, G> is whole
+      }
+    }
+  }
+  const float mi = ci[KC + NC];
+  if (unit && inside && nchunks > 1) {
+    // same lane, same addresses as the stores above; the probabilities are the staged ones (one expression: crf_prob)
+    float* un = unit + (size_t)n * K * HW + q;
+    float mx, inv;
+    crf_softmax_norm(zn + q, K, HW, mx, inv);
+    for (int k = 0; k < K; ++k) un[(size_t)k * HW] = mi * crf_prob(zn[(size_t)k * HW + q], mx, inv) * (un[(size_t)k * HW] - dot);
+  }
+  double a = inside ? (double)(mi * (S - dot)) : 0.0, b = inside ? (double)mi : 0.0;
+  a = pp_wave_sum_d(a);
+  b = pp_wave_sum_d(b);
+  if (lx == 0) { shd[0][ly] = a; shd[1][ly] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* o = partial + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2;
+    o[0] = ((shd[0][0] + shd[0][1]) + shd[0][2]) + shd[0][3];
+    o[1] = ((shd[1][0] + shd[1][1]) + shd[1][2]) + shd[1][3];
+  }
+}
+
+// sums[0] = numerator, sums[1] = sum m (mask) or the pixel count: thread t adds blocks t, t + 256, ... in order, then the butterfly
+__global__ __launch_bounds__(256) void crf_reduce_kernel(const double* __restrict__ partial, int nblocks, int has_mask,
+                                                         double unmasked_den, double* __restrict__ sums) {
+  __shared__ double sh[2][4];
+  double a = 0.0, b = 0.0;
+  for (int i = threadIdx.x; i < nblocks; i += 256) { a += partial[(size_t)i * 2]; b += partial[(size_t)i * 2 + 1]; }
+  a = pp_wave_sum_d(a);
+  b = pp_wave_sum_d(b);
+  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = a; sh[1][threadIdx.x >> 6] = b; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  sums[0] = ((sh[0][0] + sh[0][1]) + sh[0][2]) + sh[0][3];
+  sums[1] = has_mask ? ((sh[1][0] + sh[1][1]) + sh[1][2]) + sh[1][3] : unmasked_den;
+}
+
+// dlogits += grad_scale * g_up * (-2 / D) * u: 16-byte accesses, D read on the device (behind the cross-rank reduction of sums)
+__global__ __launch_bounds__(LS_THREADS) void crf_bwd_kernel(const float* __restrict__ unit, const double* __restrict__ sums,
+                                                             int has_mask, const float* __restrict__ g_up, float grad_scale,
+                                                             float* __restrict__ dz, long long n, long long n4) {
+  const double D = has_mask ? fmax(sums[1], 1e-8) : sums[1];
+  const float f = (float)(-2.0 * (double)(*g_up * grad_scale) / D);
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+  for (long long i = t; i < n4; i += step) {
+    const float4 u = reinterpret_cast<const float4*>(unit)[i];
+    float4 g = reinterpret_cast<float4*>(dz)[i];
+    g.x = __builtin_fmaf(f, u.x, g.x); g.y = __builtin_fmaf(f, u.y, g.y); g.z = __builtin_fmaf(f, u.z, g.z); g.w = __builtin_fmaf(f, u.w, g.w);
+    reinterpret_cast<float4*>(dz)[i] = g;
+  }
+  for (long long i = n4 * 4 + t; i < n; i += step) dz[i] = __builtin_fmaf(f, unit[i], dz[i]);
+}
+
+static inline int crf_blocks(int N, int H, int W) { return N * pp_cdiv(H, CRF_TH) * pp_cdiv(W, CRF_TW); }
+
+extern "C" size_t pp_crf_loss_workspace(int N, int H, int W) {
+  if (N < 1 || H < 1 || W < 1) return 0;
+  return (size_t)crf_blocks(N, H, W) * 2 * sizeof(double);
+}
+
+extern "C" int pp_crf_loss_fwd(const float* logits, const float* image, const float* valid_mask, int N, int K, int C, int H, int W,
+                               int radius, int dilation, float sigma_xy, float sigma_rgb, float* unit_grad, double* sums,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PP_CHECK_ARG(logits && image && sums && workspace, "crf_loss_fwd: null pointer");
+  // (N and the rows of tiles are grid.z and grid.y: 65535 each)
+  PP_CHECK_ARG(N >= 1 && N <= 65535 && H >= 1 && H <= 65535 * CRF_TH && W >= 1 && (long long)H * W * K < 0x7fffffffLL,
+               "crf_loss_fwd: N=%d (<= 65535) H=%d (<= %d) W=%d", N, H, 65535 * CRF_TH, W);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && C >= 1 && C <= CRF_MAXC, "crf_loss_fwd: K=%d (1..%d) C=%d (1..%d)", K, PP_MAXK, C, CRF_MAXC);
+  PP_CHECK_ARG(radius >= 1 && radius <= CRF_MAXR && dilation >= 1 && dilation <= CRF_MAXD && radius * dilation <= CRF_MAXHALO,
+               "crf_loss_fwd: radius=%d (1..%d) dilation=%d (1..%d), radius * dilation <= %d", radius, CRF_MAXR, dilation, CRF_MAXD, CRF_MAXHALO);
+  PP_CHECK_ARG(sigma_xy > 0.f && sigma_rgb > 0.f && sigma_xy < INFINITY && sigma_rgb < INFINITY, "crf_loss_fwd: sigma_xy=%g sigma_rgb=%g (> 0)",
+               (double)sigma_xy, (double)sigma_rgb);
+  if (workspace_bytes < pp_crf_loss_workspace(N, H, W)) {
+    pp_set_error("crf_loss_fwd: workspace too small (%zu < %zu)", workspace_bytes, pp_crf_loss_workspace(N, H, W));
+    return PP_ERR_WORKSPACE;
+  }
+  const int halo = radius * dilation, NC = (C == 1 || C == 3) ? C : CRF_MAXC;
+  // class chunks: as few as the LDS bound allows, of equal width (K = 9 -> 5 + 4, not 8 + 1)
+  int nchunks = pp_cdiv(K, CRF_KC), KC = pp_cdiv(K, nchunks);
+  while (crf_lds_bytes((KC + NC + 1) | 1, halo) > CRF_LDS_MAX) { ++nchunks; KC = pp_cdiv(K, nchunks); }
+  nchunks = pp_cdiv(K, KC);
+  const size_t lds = crf_lds_bytes((KC + NC + 1) | 1, halo);
+  const double log2e = 1.4426950408889634;
+  const float a_xy = (float)(-log2e / (2.0 * (double)sigma_xy * sigma_xy)), a_rgb = (float)(-log2e / (2.0 * (double)sigma_rgb * sigma_rgb));
+  const dim3 grid(pp_cdiv(W, CRF_TW), pp_cdiv(H, CRF_TH), N);
+  const int blocks = crf_blocks(N, H, W);
+  const double P = (double)N * H * W, nb = (2.0 * radius + 1.0) * (2.0 * radius + 1.0) - 1.0;
+  pp_prof_begin(PP_K_LOSS, P * nb * nchunks * (2.0 * KC + 3.0 * C + 4.0), P * (4.0 * K * (unit_grad ? 2 : 1) + 4.0 * C + 4.0), s);
+#define CRF_LAUNCH(KC_, CT_)                                                                                                   \
+  do {                                                                                                                           \
+    auto kern = crf_fwd_kernel<KC_, CT_>;                                                                                        \
+    pp_max_lds(reinterpret_cast<const void*>(kern), CRF_LDS_MAX);                                                                \
+    hipLaunchKernelGGL(kern, grid, dim3(CRF_THREADS), lds, s, logits, image, valid_mask, K, C, H, W, radius, dilation, a_xy,     \
+                       a_rgb, nchunks, unit_grad, (double*)workspace);                                                          \
+  } while (0)
+#define CRF_BY_C(KC_) do { if (C == 1) CRF_LAUNCH(KC_, 1); else if (C == 3) CRF_LAUNCH(KC_, 3); else CRF_LAUNCH(KC_, 0); } while (0)
+  switch (KC) {
+    case 1: CRF_BY_C(1); break;
+    case 2: CRF_BY_C(2); break;
+    case 3: CRF_BY_C(3); break;
+    case 4: CRF_BY_C(4); break;
+    case 5: CRF_BY_C(5); break;
+    case 6: CRF_BY_C(6); break;
+    case 7: CRF_BY_C(7); break;
+    default: CRF_BY_C(8); break;
+  }
+#undef CRF_BY_C
+#undef CRF_LAUNCH
+  hipLaunchKernelGGL(crf_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)workspace, blocks, valid_mask ? 1 : 0, P, sums);
+  pp_prof_end(s);
+  return pp_launch_status("crf_loss_fwd");
+}
+
+extern "C" int pp_crf_loss_bwd(const float* unit_grad, const double* sums, int has_mask, const float* g_up, float grad_scale,
+                               float* dlogits, long long n, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PP_CHECK_ARG(unit_grad && sums && g_up && dlogits && n >= 1, "crf_loss_bwd: bad arguments");
+  const long long n4 = ((((uintptr_t)unit_grad | (uintptr_t)dlogits) & 15) == 0) ? n >> 2 : 0;
+  pp_prof_begin(PP_K_LOSS, 2.0 * (double)n, 12.0 * (double)n, s);
+  hipLaunchKernelGGL(crf_bwd_kernel, dim3(ls_blocks(n4 ? n4 : n, 8192)), dim3(LS_THREADS), 0, s, unit_grad, sums, has_mask, g_up, grad_scale,
+                     dlogits, n, n4);
+  pp_prof_end(s);
+  return pp_launch_status("crf_loss_bwd");
+}
+
 // ---------------------------------------------------------------- 95 % Hausdorff distance (inference.py:217-237)
 // The reference calls medpy.metric.binary.hd95(pred == k, label == k, spacing, connectivity 1): the surface of a mask is
 // mask XOR erode(mask, 4-neighbourhood cross, outside = background); each directed set is the Euclidean distance (in

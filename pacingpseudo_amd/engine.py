@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import PpBnCoefItem, PpLazyIn, PpPackItem, PpWinoPackItem, lib, lib_for, prof_range, stream_ptr
+from .losses.losses import check_crf_params
 
 WINO_ENABLED = os.environ.get('PP_WINO', '1') != '0'      # A/B switch for the Winograd path
 # split-fp16 ("f16x3") direct convolution for the non-Winograd layers with at least this many output channels
@@ -513,10 +514,20 @@ class _Plan:
                 self.aux_fork, self.aux_join = torch.cuda.Event(), torch.cuda.Event()
         # loss denominators / numerators, packed so that data-parallel runs all-reduce them ONCE per step:
         # [0:6] segmentation losses (pp_seg_losses_fwd), [6:8] auxiliary partial CE (pp_aux_pce_fwd)
-        self.all_sums = torch.zeros(8, device=dev, dtype=torch.float64)
+        # With the gated-CRF loss (--do_loss_crf) its two sums sit between them, [6:8] (pp_crf_loss_fwd), and the auxiliary pair at
+        # [8:10]: a step without the auxiliary path still reduces one contiguous block.  Its buffers exist in such plans only.
+        self.crf = None
+        if eng.crf is not None:
+            check_crf_params(K=net.num_classes, C=net.input_ch, **eng.crf)
+            self.all_sums = torch.zeros(10, device=dev, dtype=torch.float64)
+            nws = lib.pp_crf_loss_workspace(B, H, W)
+            self.crf = dict(sums=self.all_sums[6:8], ws=torch.empty(nws, device=dev, dtype=torch.uint8), ws_bytes=nws,
+                            unit=torch.empty((B, net.num_classes, H, W), **f32) if trainable else None)
+        else:
+            self.all_sums = torch.zeros(8, device=dev, dtype=torch.float64)
         self.sums = self.all_sums[:6]
         if self.aux is not None:
-            self.aux['sums'] = self.all_sums[6:8]
+            self.aux['sums'] = self.all_sums[8:10] if self.crf is not None else self.all_sums[6:8]
         self.target = torch.empty((B, H, W), device=dev, dtype=torch.int64)
 
     def ws_args(self):
@@ -643,6 +654,13 @@ class StepEngine:
         self._bwd_plan = None            # plan of the backward pass in flight
         # 16-bit storage of activations / activation gradients for TRAINING plans (`--storage fp16`, BASELINE config 5; PP_ACT_H16=1
         # forces it for A/B runs).  Forward-only plans (validation, inference at native slice sizes) stay fp32.
+        # --do_loss_crf: the gated-CRF regulariser on the weak logits; its parameters are constants of the run (checked here, before
+        # any launch).  None: no launch, no buffer, no output key.
+        self.crf = None
+        if getattr(args, 'do_loss_crf', False):
+            self.crf = check_crf_params(radius=getattr(args, 'crf_radius', 5), dilation=getattr(args, 'crf_dilation', 1),
+                                        sigma_xy=getattr(args, 'crf_sigma_xy', 6.0), sigma_rgb=getattr(args, 'crf_sigma_rgb', 0.1),
+                                        K=backbone.num_classes)
         self.storage = getattr(args, 'storage', 'fp32') or 'fp32'
         if os.environ.get('PP_ACT_H16', '0') == '1' and self.storage == 'fp32':
             self.storage = 'fp16'
@@ -1495,6 +1513,14 @@ class StepEngine:
         plan.K.pp_seg_losses_fwd(logits.data_ptr(), zs.data_ptr() if do_cr else None, plan.target.data_ptr(), mask_ptr,
                               B, K, H * W, args.ignored_index, int(do_ent), variant, plan.sums.data_ptr(),
                               plan.ws.data_ptr(), plan.ws_bytes, st)
+        do_crf_loss = bool(train and plan.crf is not None)
+        crf_mask = valid_mask if do_crf_loss else None      # the mask applies whenever the batch has one, entropy / consistency on or off
+        if do_crf_loss:
+            c = self.crf
+            plan.K.pp_crf_loss_fwd(logits.data_ptr(), image.data_ptr(), crf_mask.data_ptr() if crf_mask is not None else None,
+                                   B, K, Cin, H, W, c['radius'], c['dilation'], c['sigma_xy'], c['sigma_rgb'],
+                                   plan.crf['unit'].data_ptr() if need_grad else None, plan.crf['sums'].data_ptr(),
+                                   plan.crf['ws'].data_ptr(), plan.crf['ws_bytes'], st)
         if do_aux:
             if side is not None:
                 torch.cuda.current_stream().wait_event(plan.aux_join)
@@ -1503,7 +1529,7 @@ class StepEngine:
             ax, a = self.aux, plan.aux
             drop, feat, wfc, logits_aux = A['drop'], A['feat'], A['wfc'], A['logits_aux']
         if self.comm is not None:
-            self.comm.allreduce_sums(plan.all_sums if do_aux else plan.sums)
+            self.comm.allreduce_sums(plan.all_sums if do_aux else (plan.all_sums[:8] if do_crf_loss else plan.sums))
         out = {}
         loss_pce = torch.empty((), device=dev, dtype=torch.float32)
         loss_ent = torch.empty((), device=dev, dtype=torch.float32) if do_ent else None
@@ -1517,6 +1543,11 @@ class StepEngine:
         if do_cr:
             out['loss_cr'] = loss_cr
             out['segmentation/logits_strong'] = logits[B:]
+        if do_crf_loss:
+            # numerator / max(denominator, 1e-8): the masked-ratio slot of pp_losses_finalize reads sums[2] / sums[3]
+            loss_crf = torch.empty((), device=dev, dtype=torch.float32)
+            plan.K.pp_losses_finalize(plan.all_sums[4:].data_ptr(), 1 if crf_mask is not None else 0, None, loss_crf.data_ptr(), None, st)
+            out['loss_crf'] = loss_crf
 
         if do_aux:
             loss_aux = torch.empty((), device=dev, dtype=torch.float32)
@@ -1541,6 +1572,8 @@ class StepEngine:
                              bn_training=bn_training, aux_training=self.aux.training if self.aux is not None else False,
                              aux_group=aux_group, logits_aux=out.get('logits_aux_cls'),
                              drop=self.last_drop_masks if do_aux else None)
+            if do_crf_loss:
+                self.last.update(do_crf=True, crf_mask=crf_mask)
         return out
 
     def _aux_input(self, plan, aux_group, st) -> View:
@@ -1629,6 +1662,10 @@ class StepEngine:
                                   B, K, H * W, args.ignored_index, int(S['do_ent']), S['variant'],
                                   1 if getattr(args, 'detach_weak_cr', False) else 0, plan.sums.data_ptr(),
                                   gp('loss_pce'), gp('loss_ent'), gp('loss_cr'), plan.loss_scale, plan.dlogits.data_ptr(), dzs_ptr, st)
+            if S.get('do_crf') and gp('loss_crf') is not None:
+                # streaming add of the unit gradient the forward left, behind the kernel that WRITES dlogits[:B]
+                plan.K.pp_crf_loss_bwd(plan.crf['unit'].data_ptr(), plan.crf['sums'].data_ptr(), 1 if S['crf_mask'] is not None else 0,
+                                       gp('loss_crf'), plan.loss_scale, plan.dlogits.data_ptr(), B * K * H * W, st)
         with prof_range('backward: decoder'):
             g6 = self._unet_backward_decoder(plan, S['bn_training'], grads, st)
         if S['do_aux']:

@@ -192,6 +192,79 @@ def dice_loss_fn(input, target):
     return _DiceLoss.apply(_check(input, 'input'), _check(target, 'target'))
 
 
+CRF_MAX_RADIUS, CRF_MAX_DILATION, CRF_MAX_HALO, CRF_MAX_CHANNELS, CRF_MAX_CLASSES = 8, 4, 16, 4, 32
+
+
+def check_crf_params(radius=5, dilation=1, sigma_xy=6.0, sigma_rgb=0.1, K=None, C=None) -> dict:
+    """The accepted ranges of the gated-CRF loss (include/pacingpseudo_hip.h: pp_crf_loss_fwd), checked before any launch:
+    ValueError for values that are no neighbourhood / no kernel width at all, NotImplementedError for sizes beyond what the
+    kernel stages in LDS.  Returns the normalised parameters."""
+    import math
+    if int(radius) != radius or int(dilation) != dilation:
+        raise ValueError(f'gated CRF: radius and dilation must be integers (got {radius!r}, {dilation!r})')
+    radius, dilation, sigma_xy, sigma_rgb = int(radius), int(dilation), float(sigma_xy), float(sigma_rgb)
+    if radius < 1 or dilation < 1:
+        raise ValueError(f'gated CRF: radius and dilation must be >= 1 (got {radius}, {dilation})')
+    for name, v in (('sigma_xy', sigma_xy), ('sigma_rgb', sigma_rgb)):
+        if not (v > 0.0 and math.isfinite(v)):
+            raise ValueError(f'gated CRF: {name} must be a positive finite number (got {v!r})')
+    if radius > CRF_MAX_RADIUS or dilation > CRF_MAX_DILATION or radius * dilation > CRF_MAX_HALO:
+        raise NotImplementedError(f'gated CRF: radius <= {CRF_MAX_RADIUS}, dilation <= {CRF_MAX_DILATION} and radius * dilation <= '
+                                  f'{CRF_MAX_HALO} (got {radius}, {dilation})')
+    if K is not None and not 1 <= K <= CRF_MAX_CLASSES:
+        raise NotImplementedError(f'gated CRF: 1 .. {CRF_MAX_CLASSES} classes (got {K})')
+    if C is not None and not 1 <= C <= CRF_MAX_CHANNELS:
+        raise NotImplementedError(f'gated CRF: 1 .. {CRF_MAX_CHANNELS} image channels (got {C})')
+    return dict(radius=radius, dilation=dilation, sigma_xy=sigma_xy, sigma_rgb=sigma_rgb)
+
+
+class _CrfLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, image, mask, prm):
+        N, K, H, W = z.shape
+        st = stream_ptr()
+        dev = z.device
+        # [2:4] = numerator, denominator: where pp_losses_finalize's masked-ratio slot reads them
+        sums = torch.zeros(4, device=dev, dtype=torch.float64)
+        nws = lib.pp_crf_loss_workspace(N, H, W)
+        ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+        unit = torch.empty_like(z) if ctx.needs_input_grad[0] else None
+        lib.pp_crf_loss_fwd(z.data_ptr(), image.data_ptr(), mask.data_ptr() if mask is not None else None, N, K, image.shape[1], H, W,
+                            prm['radius'], prm['dilation'], prm['sigma_xy'], prm['sigma_rgb'],
+                            unit.data_ptr() if unit is not None else None, sums[2:].data_ptr(), ws.data_ptr(), nws, st)
+        out = torch.empty((), device=dev, dtype=torch.float32)
+        lib.pp_losses_finalize(sums.data_ptr(), 1 if mask is not None else 0, None, out.data_ptr(), None, st)
+        ctx.unit, ctx.sums, ctx.has_mask = unit, sums, mask is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        unit = ctx.unit
+        g = g.to(torch.float32).contiguous()
+        dz = torch.zeros_like(unit)
+        lib.pp_crf_loss_bwd(unit.data_ptr(), ctx.sums[2:].data_ptr(), 1 if ctx.has_mask else 0, g.data_ptr(), 1.0, dz.data_ptr(),
+                            unit.numel(), stream_ptr())
+        return dz, None, None, None
+
+
+def gated_crf_loss(input, image, valid_mask=None, radius=5, dilation=1, sigma_xy=6.0, sigma_rgb=0.1):
+    """Local pairwise gated-CRF / Potts regulariser (this implementation's addition; the reference has no such loss):
+    (1/D) sum_i sum_j m_i m_j k_ij (1 - <p_i, p_j>) with p = softmax(input), j = i + (dy, dx) * dilation over dy, dx in
+    [-radius, radius] \\ (0, 0) inside the image, k_ij = exp(-(dy^2 + dx^2) / (2 sigma_xy^2)) exp(-|x_i - x_j|^2 / (2 sigma_rgb^2))
+    on the `image` channels, D = N H W or max(sum(valid_mask), 1e-8).  Differentiable in `input` only."""
+    z, x = _check(input, 'input'), _check(image, 'image')
+    N, K, H, W = z.shape
+    if x.shape[0] != N or tuple(x.shape[2:]) != (H, W):
+        raise ValueError(f'image must be (N,C,H,W) with the N, H, W of input {tuple(z.shape)}, got {tuple(x.shape)}')
+    m = None
+    if valid_mask is not None:
+        m = _check(valid_mask, 'valid_mask')
+        if tuple(m.shape) != (N, 1, H, W):
+            raise ValueError(f'valid_mask must be {(N, 1, H, W)}, got {tuple(m.shape)}')
+    prm = check_crf_params(radius, dilation, sigma_xy, sigma_rgb, K=K, C=x.shape[1])
+    return _CrfLoss.apply(z, x, m, prm)
+
+
 class _WeightedSum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weights, *terms):

@@ -26,7 +26,7 @@ from .aux_path_memory import AuxPath
 from ..engine import StepEngine
 from ..flat import FlatSlab
 
-_LOSS_KEYS = ('loss_pce', 'loss_ent', 'loss_cr', 'loss_aux_cls', 'loss_memory')
+_LOSS_KEYS = ('loss_pce', 'loss_ent', 'loss_cr', 'loss_crf', 'loss_aux_cls', 'loss_memory')
 
 
 class _StepFunction(torch.autograd.Function):
@@ -111,6 +111,8 @@ class ConsistencyRegulr(nn.Module):
                 keys.append('loss_ent')
             if a.do_decoder_consistency:
                 keys += ['loss_cr', 'segmentation/logits_strong']
+            if getattr(a, 'do_loss_crf', False):
+                keys.append('loss_crf')
             if a.do_aux_path:
                 keys += ['logits_aux_cls', 'loss_aux_cls']
                 if a.do_memory:

@@ -98,6 +98,17 @@ def _positive_int(text):
     return v
 
 
+positive_int = _positive_int          # the drivers' own flags use the same validators
+
+
+def positive_float(text):
+    import argparse
+    v = float(text)
+    if not (v > 0.0 and v < math.inf):
+        raise argparse.ArgumentTypeError(f'must be a positive finite number, got {text!r}')
+    return v
+
+
 def add_ema_flags(parser) -> None:
     """``--ema_decay D`` / ``--ema_val_interval N`` of both training drivers (0 = off; resume.py knows the defaults for state files
     older than the flags)."""

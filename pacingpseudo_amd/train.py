@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from . import resume
-from .optim import add_clip_flag, add_ema_flags, log_clip_stats
+from .losses.losses import check_crf_params
+from .optim import add_clip_flag, add_ema_flags, log_clip_stats, positive_float, positive_int
 
 parser = argparse.ArgumentParser(description='PacingPseudo training on MI355X (flag surface of the reference driver)')
 
@@ -145,6 +146,16 @@ parser.add_argument('--norm_op', type=str, default='batch', choices=['batch', 'g
                     help='block normaliser of the U-Net: batch = nn.BatchNorm2d (the reference); group = nn.GroupNorm(--norm_groups, C): '
                          'per-image statistics, no running state, the same function in train and eval mode (fp32 storage only)')
 parser.add_argument('--norm_groups', type=int, default=8, help='channel groups of --norm_op group; must divide every block width')
+# gated-CRF / Potts regulariser on the weak-view prediction (pp_crf_loss_*); the reference has no such loss
+parser.add_argument('--do_loss_crf', action='store_true',
+                    help='add the local pairwise gated-CRF loss: neighbouring pixels of similar intensity are pulled towards the same '
+                         'class (bilateral kernel on position and image intensity, one tiled HIP kernel per step)')
+parser.add_argument('--loss_crf_weight', type=float, default=0.1, help='its weight')
+parser.add_argument('--ramp_up_loss_crf', action='store_true', help='Gaussian ramp-up of that weight over the epochs (--ramp_up_scale)')
+parser.add_argument('--crf_radius', type=positive_int, default=5, help='neighbourhood radius r: offsets dy, dx in [-r, r] (1 .. 8)')
+parser.add_argument('--crf_dilation', type=positive_int, default=1, help='spacing d of the neighbourhood offsets in pixels (1 .. 4, r * d <= 16)')
+parser.add_argument('--crf_sigma_xy', type=positive_float, default=6.0, help='width of the position kernel, in offsets')
+parser.add_argument('--crf_sigma_rgb', type=positive_float, default=0.1, help='width of the intensity kernel, in units of the network input')
 add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
 add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
@@ -182,6 +193,16 @@ def apply_dataset_preset(args, argv=None):
     for key in ('num_classes', 'ignored_index', 'image_size'):
         if getattr(args, key, None) is None:
             setattr(args, key, preset[key])
+    return args
+
+
+def parse_args(argv=None):
+    """parser.parse_args plus the checks that span several flags (argparse errors: exit status 2)."""
+    args = parser.parse_args(argv)
+    try:
+        check_crf_params(args.crf_radius, args.crf_dilation, args.crf_sigma_xy, args.crf_sigma_rgb)
+    except (ValueError, NotImplementedError) as e:
+        parser.error(f'--crf_radius / --crf_dilation / --crf_sigma_xy / --crf_sigma_rgb: {e}')
     return args
 
 
@@ -315,6 +336,7 @@ def train_interface(args, resume_state=None):
 
         # loss meters live on the GPU: [sum pce*n, sum ent*n, sum cr*n, sum aux*n, sum mem, n, iterations]
         acc = torch.zeros(7, device=device, dtype=torch.float64)
+        acc_crf = torch.zeros(1, device=device, dtype=torch.float64) if args.do_loss_crf else None      # sum crf*n (--do_loss_crf only)
         n_img = 0
         for idx, batch in enumerate(train_loader):
             if args.max_iters and idx >= args.max_iters:
@@ -331,6 +353,8 @@ def train_interface(args, resume_state=None):
             # loss assembly of train_chaos.py:273-310; the ramp-up weights depend on the epoch only
             w_ent = gaussian_ramp_up(t=curr_epoch, base_value=args.loss_ent_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_ent else 1.0
             w_cr = gaussian_ramp_up(t=curr_epoch, base_value=args.loss_cr_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_cr else 1.0
+            w_crf = (gaussian_ramp_up(t=curr_epoch, base_value=args.loss_crf_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_crf
+                     else args.loss_crf_weight)
 
             def assemble(out, _epoch=None):
                 # train_chaos.py:273-310: pce + ent * w_ent + cr * w_cr + aux * w_aux + memory * w_mem -- one launch each way
@@ -344,6 +368,8 @@ def train_interface(args, resume_state=None):
                     terms.append(out['loss_aux_cls']); weights.append(args.loss_aux_weight)
                     if args.do_memory:
                         terms.append(out['loss_memory']); weights.append(args.loss_memory_weight)
+                if args.do_loss_crf:
+                    terms.append(out['loss_crf']); weights.append(w_crf)
                 return weighted_loss_sum(terms, weights)
             if args.graph_step and n == args.batch_size:      # (a ragged last batch runs eagerly: another shape, another plan)
                 if graph_step is None:
@@ -366,10 +392,12 @@ def train_interface(args, resume_state=None):
                 acc[3] += net_outputs['loss_aux_cls'].detach() * (args.loss_aux_weight * n)
                 if args.do_memory:
                     acc[4] += net_outputs['loss_memory'].detach() * args.loss_memory_weight
+            if args.do_loss_crf:
+                acc_crf[0] += net_outputs['loss_crf'].detach() * (w_crf * n)
             acc[5] += n
             acc[6] += 1
             n_img += n
-        a = acc.cpu().numpy()                      # the one host sync of the epoch
+        a = (torch.cat([acc, acc_crf]) if args.do_loss_crf else acc).cpu().numpy()      # the one host sync of the epoch
         epoch_toc = time.time()
         cnt, its = max(a[5], 1), max(a[6], 1)
         # 16-bit storage: optimizer steps the overflow guard skipped this epoch (a static loss scale that keeps
@@ -392,9 +420,10 @@ def train_interface(args, resume_state=None):
                     raise FloatingPointError('every optimizer step of the epoch was skipped even at loss scale < 1: the gradients '
                                              'themselves are not finite')
         if rank == 0:
+            crf_col = ", loss_crf: {:.6f}".format(a[7] / cnt) if args.do_loss_crf else ""
             logging.info("epoch: {:03d}, lr: {:.6f}, loss_pce: {:.6f}, loss_ent: {:.6f}, loss_cr: {:.6f}, loss_aux_cls: {:.6f}, "
-                         "loss_memory: {:.6f}, {:.2f} s/epoch".format(curr_epoch, new_lr, a[0] / cnt, a[1] / cnt, a[2] / cnt,
-                                                                     a[3] / cnt, a[4] / its, epoch_toc - epoch_tic))
+                         "loss_memory: {:.6f}{}, {:.2f} s/epoch".format(curr_epoch, new_lr, a[0] / cnt, a[1] / cnt, a[2] / cnt,
+                                                                       a[3] / cnt, a[4] / its, crf_col, epoch_toc - epoch_tic))
             logging.info("throughput: {:.1f} images/sec ({} GPU)".format(n_img * world / max(epoch_toc - epoch_tic, 1e-9), world))
         # --clip_grad_norm: the epoch's gradient-norm statistics (every rank holds the same ones: the norm is taken behind the
         # all-reduce), read behind the sync above; every rank starts them over
@@ -418,6 +447,8 @@ def train_interface(args, resume_state=None):
             scalars.add('losses/loss_ent', a[1] / cnt, curr_epoch)
             scalars.add('losses/loss_aux_cls', a[3] / cnt, curr_epoch)
             scalars.add('losses/loss_memory', a[4] / its, curr_epoch)
+            if args.do_loss_crf:
+                scalars.add('train/loss_crf', a[7] / cnt, curr_epoch)
             scalars.add('lr/current_lr', new_lr, curr_epoch)
             scalars.add('losses/loss_pce_val', loss_pce_val, curr_epoch)
             for i, nm in enumerate(names):
@@ -480,7 +511,7 @@ def train_interface(args, resume_state=None):
 
 
 def train_main(argv=None):
-    args = apply_dataset_preset(parser.parse_args(argv), argv)
+    args = apply_dataset_preset(parse_args(argv), argv)
     state_file, resume_state = resume.open_state(parser, args, int(os.environ.get('WORLD_SIZE', '1'))) if args.resume else (None, None)
     if 'LOCAL_RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu

@@ -39,6 +39,7 @@ def _worker(rank, world, port, q):
     torch.set_num_threads(2)
     from pacingpseudo_amd import parallel
     from pacingpseudo_amd.flat import FlatSlab
+    from tests._bucket_probe import tiling_errors
     w, r, _ = parallel.init_from_env('gloo')
     assert (w, r) == (world, rank)
     comm = parallel.Comm()
@@ -57,6 +58,7 @@ def _worker(rank, world, port, q):
     a0, b0 = flat.segments['backbone']
     a1, b1 = flat.segments['aux_path']
     assert covered[0][0] == a0 and covered[-1][1] <= b1
+    assert tiling_errors(flat, {tag: red._range(flat, tag) for tag, _ in buckets}, ['backbone', 'aux_path']) == []
     # ---- 2. semantic check: sum of per-rank gradients == gradient of the concatenated batch
     sd = O.init_state(args, seed=3)
     for k in sd:                                   # non-trivial BN statistics for the eval-mode forward
@@ -167,3 +169,43 @@ def test_gradient_buckets_cover_the_strided_transposed_variant():
     seen = [p for _, ps in parallel.backbone_buckets(model) for p in ps]
     assert len(seen) == len(set(map(id, seen))) == len(flat.offsets)
     assert any(p is model.backbone.dec_block3.up_samp.weight for p in seen)
+    _assert_exact_tiling(model, flat)
+
+
+def _assert_exact_tiling(model, flat):
+    """The bucket ranges (GradReducer._range, the product's own) are pairwise disjoint and tile each segment without a gap from its
+    start to the end of its last parameter; without the auxiliary path (no 'aux' announcement) the rest tiles the backbone."""
+    from pacingpseudo_amd import parallel
+    from tests._bucket_probe import tiling_errors
+    red = parallel.GradReducer(model, None)
+    ranges = {tag: red._range(flat, tag) for tag, _ in parallel.backbone_buckets(model)}
+    assert len(ranges) == 6
+    assert tiling_errors(flat, ranges, ['backbone', 'aux_path']) == []
+    assert tiling_errors(flat, {t: r for t, r in ranges.items() if t != 'aux'}, ['backbone']) == []
+    # the check itself: a gap, an overlap and a missing bucket are each reported
+    lo, hi = ranges['enc5']
+    assert tiling_errors(flat, dict(ranges, enc5=(lo + 1, hi)), ['backbone', 'aux_path'])
+    assert tiling_errors(flat, dict(ranges, enc5=(lo, hi + 1)), ['backbone', 'aux_path'])
+    assert tiling_errors(flat, {t: r for t, r in ranges.items() if t != 'dec5'}, ['backbone', 'aux_path'])
+    assert tiling_errors(flat, ranges, ['backbone'])
+
+
+def test_gradient_buckets_cover_the_groupnorm_variant():
+    """--norm_op group: the GroupNorm holders' weight / bias take the BatchNorm parameters' places in the slab; same exact tiling."""
+    from pacingpseudo_amd import parallel
+    from pacingpseudo_amd.flat import FlatSlab
+    from pacingpseudo_amd.models import ConsistencyRegulr
+    args = O.default_args(init_ch=8, max_ch=32, hid_ch=8, feat_ch=[32, 32], do_loss_ent=True, do_decoder_consistency=True,
+                          do_aux_path=True, do_memory=False)
+    model = ConsistencyRegulr(
+        kwargs_unet=dict(input_ch=1, init_ch=8, max_ch=32, num_classes=5, output_stride=8, is_stride_conv=False, is_trans_conv=False,
+                         elab_end_points=True, norm_op='group', norm_groups=4),
+        kwargs_aux_path=dict(num_classes=5, feat_stage=args.feat_stage, feat_ch=args.feat_ch, hid_ch=8, aux_drop_prob=0.0,
+                             do_memory=False, max_step=400, update_momentum=0.9, ensemble_mode='cosine_similarity'),
+        args_parser=args)
+    flat = FlatSlab([('backbone', [p for p in model.backbone.parameters() if p.requires_grad]),
+                     ('aux_path', [p for p in model.aux_path.parameters() if p.requires_grad])])
+    seen = [p for _, ps in parallel.backbone_buckets(model) for p in ps]
+    assert len(seen) == len(set(map(id, seen))) == len(flat.offsets)
+    assert isinstance(model.backbone.enc_block1.conv_block.conv_layer1.norm_op, torch.nn.GroupNorm)
+    _assert_exact_tiling(model, flat)

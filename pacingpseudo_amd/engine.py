@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import PpBnCoefItem, PpLazyIn, PpPackItem, PpWinoPackItem, lib, lib_for, prof_range, stream_ptr
+from .convop import ConvOp, select as conv_select
 from .losses.losses import check_crf_params
 
 WINO_ENABLED = os.environ.get('PP_WINO', '1') != '0'      # A/B switch for the Winograd path
@@ -179,9 +180,7 @@ class _Layer:
         self.y: Optional[View] = None
         self.z = None
         self.coef = None
-        self.wf = self.wb = None
         self.groups = 1
-        self.wino = False           # set per plan: Winograd F(2x2,3x3) path for this layer
 
 
 class _Plan:
@@ -264,40 +263,13 @@ class _Plan:
         self.zbuf: Dict[str, torch.Tensor] = {}
         self.coef: Dict[str, torch.Tensor] = {}
         self.bn_sums: Dict[str, torch.Tensor] = {}
-        self.wf: Dict[str, torch.Tensor] = {}
-        self.wb: Dict[str, torch.Tensor] = {}
-
-        self.wino: Dict[str, bool] = {}
-        self.f16: Dict[str, bool] = {}
-        self.wino16_fwd: Dict[str, bool] = {}
-        self.wino16_bwd: Dict[str, bool] = {}
-        self.wino16_wg: Dict[str, bool] = {}
-        self.amax: Dict[str, torch.Tensor] = {}
-        self.vkeep: Dict[str, torch.Tensor] = {}
-        self.wino_tile: Dict[str, int] = {}
+        self.conv: Dict[str, ConvOp] = {}  # per layer: its kernel family (.sel) and packed weights, bound to self.K
         self.wino_ws = 0
         self.wg_ws_bytes = 0               # workspace of the weight-gradient calls alone (they may run on a second stream)
         # stride-2 convolutions run as stride-1 convolutions at the input resolution: full-resolution z and (zero-stuffed) dz
         self.zfull: Dict[str, torch.Tensor] = {}
         self.dzfull: Dict[str, torch.Tensor] = {}
         self.ct_ws = 0                     # ConvTranspose2d weight-gradient workspace (--is_trans_conv)
-
-        def conv_select(L: _Layer, h, w):
-            """Kernel family of one conv layer at (h, w) -- a pure function of the shape: (Winograd?, tile, split-fp16
-            Winograd GEMMs?, split-fp16 direct kernels?)."""
-            # Winograd F(4x4,3x3) / F(2x2,3x3) for the wide layers: 4x / 2.25x less MFMA work (measured 1.3-3.2x per
-            # layer from 128 input channels up, scripts/bench_wino.py); narrow high-resolution layers stay direct
-            use = (WINO_ENABLED and L.cin >= WINO_MIN_CIN and L.cout >= WINO_MIN_COUT and L.cin == L.cin_pad
-                   and h % (2 * L.dil) == 0 and w % (2 * L.dil) == 0 and L.stride == 1)
-            tile = lib.pp_conv3x3_wino_tile(h, w, L.dil) if use else 0
-            # split-fp16 GEMMs on pre-split operands (octets along the GEMM K: 8 channels); forward and weight gradient
-            # share the kept transformed input, so they take the same path
-            ok16 = bool(use and F16X3_ENABLED and tile == 4 and L.cin % 8 == 0 and L.cout % 8 == 0)
-            if self.h16 and use and not ok16:      # 16-bit storage has the split-fp16 F(4x4,3x3) Winograd path only
-                use, tile = False, 0
-            f16 = bool(F16X3_ENABLED and not use and L.cin_pad == L.cin and L.cin % 4 == 0 and L.cout % 4 == 0
-                       and L.cout >= F16X3_MIN_COUT)
-            return use, tile, ok16, f16
 
         # ---- which layer outputs stay LAZY in train-mode BN (static per plan): every consumer of the tensor must have a
         # kernel form that applies BatchNorm + LeakyReLU while loading.  Decided before any buffer is laid out, because a
@@ -306,44 +278,38 @@ class _Plan:
         aux_alias = bool(stages == [6, 5] and decs[5].identity_up and len({sizes[s_ - 1] for s_ in stages}) == 1)
         def halo_lazy_ok(Lc: _Layer, h, w):
             """The direct (two-half halo) forward kernel and the halo-tile weight-gradient kernels of layer Lc read a lazy input."""
-            use, _, _, f16 = conv_select(Lc, h, w)
+            sel = conv_select(Lc, h, w, self.h16)
             # (fp32 storage by default: with fp16 tensors the saved pass is half as long -- same-box A/B by family: BatchNorm
             # -0.5 ms, halo +0.16, weight gradients +0.07 with fp32 storage; -0.23 / +0.20 / +0.10 with 16-bit storage, i.e. nothing:
             # engine.LAZY_HALO_H16 switches it on there)
-            return bool(LAZY_HALO and (not self.h16 or LAZY_HALO_H16) and not use and f16 and Lc.stride == 1 and G <= 2
+            return bool(LAZY_HALO and (not self.h16 or LAZY_HALO_H16) and sel.kind == 'f16x3' and Lc.stride == 1 and G <= 2
                         and self.K.pp_conv3x3_lazy_ok(Lc.cin, Lc.cout, self.Bt, h, w, Lc.dil) == 1)
-        self.lazy_out: Dict[str, bool] = self._decide_lazy(eng, encs, decs, sizes, conv_select, stages, aux_alias, halo_lazy_ok)
+        self.lazy_out: Dict[str, bool] = self._decide_lazy(eng, sizes, halo_lazy_ok)
 
         def conv_bufs(L: _Layer, n, h, w):
             """Packed-weight buffers of one conv layer and the choice direct vs Winograd."""
             nonlocal max_elems
-            use, tile, ok16, f16 = conv_select(L, h, w)
-            self.wino[L.name] = use
-            self.wino16_fwd[L.name] = self.wino16_bwd[L.name] = self.wino16_wg[L.name] = False
-            if use:
-                self.wino16_fwd[L.name] = self.wino16_bwd[L.name] = self.wino16_wg[L.name] = ok16
-                planes = (tile + 2) ** 2                                        # 16 or 36
-                self.wino_tile[L.name] = tile
-                self.wf[L.name] = torch.empty((planes, L.cout, L.cin), **f32)   # Uf
-                self.wb[L.name] = torch.empty((planes, L.cin, L.cout), **f32)   # Ub
+            sel = conv_select(L, h, w, self.h16)
+            vkeep = amax = None
+            if sel.kind == 'wino':
+                planes = (sel.tile + 2) ** 2                                    # 16 or 36
+                wf = torch.empty((planes, L.cout, L.cin), **f32)                # Uf
+                wb = torch.empty((planes, L.cin, L.cout), **f32)                # Ub
                 # transformed input of the forward pass, kept for the weight gradient (2.25-4x the activation, a few
                 # GB in total at the benchmark shape: cheaper in 288 GB of HBM than a second transform pass)
                 if trainable:
-                    self.vkeep[L.name] = torch.empty(lib.pp_conv3x3_wino_vkeep_elems(L.cin, n, h, w, L.dil), **f32)
+                    vkeep = torch.empty(lib.pp_conv3x3_wino_vkeep_elems(L.cin, n, h, w, L.dil), **f32)
                     self.wino_ws = max(self.wino_ws, lib.pp_conv3x3_wino_workspace(L.cout, L.cin, n, h, w, L.dil),
                                        lib.pp_conv3x3_wino_bwd_weight_workspace(L.cout, L.cin, n, h, w, L.dil))
                     self.wg_ws_bytes = max(self.wg_ws_bytes, lib.pp_conv3x3_wino_bwd_weight_workspace(L.cout, L.cin, n, h, w, L.dil))
                 self.wino_ws = max(self.wino_ws, lib.pp_conv3x3_wino_workspace(L.cin, L.cout, n, h, w, L.dil))
             else:
-                self.wf[L.name] = torch.empty((L.cout, 9, L.cin_pad), **f32)
-                self.wb[L.name] = torch.empty((L.cin, 9, L.cout), **f32) if L.cin_pad == L.cin else None
-            # same buffers hold the [hi4 | lo4] fp16 pairs when the layer runs on the split-fp16 kernels
-            self.f16[L.name] = f16
-            if self.h16 and not use and not f16 and L.cin_pad == L.cin:
-                raise NotImplementedError(f'16-bit storage: {L.name} ({L.cin}->{L.cout}) has no split-fp16 kernel '
-                                          f'(needs >= {F16X3_MIN_COUT} output channels)')
-            if trainable and (self.f16[L.name] or self.wino16_bwd[L.name] or self.wino16_wg[L.name]):
-                self.amax[L.name] = torch.zeros(1, **f32)       # max |dz| of the step, written by the BN backward
+                # (the same buffers hold the [hi4 | lo4] fp16 pairs when the layer runs on the split-fp16 kernels)
+                wf = torch.empty((L.cout, 9, L.cin_pad), **f32)
+                wb = torch.empty((L.cin, 9, L.cout), **f32) if L.cin_pad == L.cin else None
+            if trainable and (sel.kind == 'f16x3' or sel.split):
+                amax = torch.zeros(1, **f32)                    # max |dz| of the step, written by the BN backward
+            self.conv[L.name] = ConvOp(sel, L, self.K, SLOPE, wf, wb, vkeep, amax)
             max_elems = max(max_elems, n * h * w * max(L.cout, L.cin_pad))
 
         self.bn_stats_bytes = 0
@@ -496,7 +462,7 @@ class _Plan:
             if L is eng.aux_layer:      # what the auxiliary forward needs when it runs on the second stream (its own workspace / statistics rows)
                 aux_side_ws = max(lib.pp_bn_workspace(L.cout, (n // g) * hL * wL, g) + 12 * g * L.cout, loss_ws,
                                   lib.pp_conv1x1_bwd_workspace(net.num_classes, L.cout, n, hL * wL),
-                                  lib.pp_conv3x3_wino_workspace(L.cin, L.cout, n, hL, wL, L.dil) if self.wino[L.name] else 0)
+                                  lib.pp_conv3x3_wino_workspace(L.cin, L.cout, n, hL, wL, L.dil) if self.conv[L.name].sel.kind == 'wino' else 0)
         head = lib.pp_conv1x1_bwd_workspace(net.num_classes, ch[0], Bt, H * W)
         if self.aux is not None:
             head = max(head, lib.pp_conv1x1_bwd_workspace(net.num_classes, eng.aux_layer.cout, B,
@@ -560,7 +526,7 @@ class _Plan:
         return act(self.Bt, h, w, c, self.G)[1]
 
     @staticmethod
-    def _decide_lazy(eng, encs, decs, sizes, conv_select, stages, aux_alias, halo_lazy_ok=None) -> Dict[str, bool]:
+    def _decide_lazy(eng, sizes, halo_lazy_ok=None) -> Dict[str, bool]:
         """{layer name: its output is a lazy tensor in train-mode BN}.  The consumers of a layer output are: the next
         convolution (directly, or through a concatenation buffer it is a slice of), the max-pooling / up-sampling in front
         of the next stage, the 1x1 head, the auxiliary path.  Each must be able to apply BatchNorm + LeakyReLU on load."""
@@ -752,18 +718,11 @@ class StepEngine:
             if getattr(plan, 'pack_batch_key', None) != bkey:
                 direct, wino, single = [], [], []
                 for L in layers:
-                    wb = plan.wb[L.name]
-                    w, wf = L.conv.weight.data_ptr(), plan.wf[L.name].data_ptr()
-                    wbp = wb.data_ptr() if wb is not None else None
-                    if plan.wino[L.name]:
-                        if plan.wino16_fwd[L.name] and plan.wino16_bwd[L.name] and plan.wino_tile[L.name] == 4:
-                            wino.append(PpWinoPackItem(w, L.cout, L.cin, wf, wbp))
-                        else:
-                            single.append(L)
-                    elif plan.f16[L.name]:
-                        direct.append(PpPackItem(w, L.cout, L.cin, L.cin_pad, wf, wbp))
-                    else:
+                    item = plan.conv[L.name].pack_item()
+                    if item is None:
                         single.append(L)
+                    else:
+                        (wino if isinstance(item, PpWinoPackItem) else direct).append(item)
                 plan.pack_batch = ((PpPackItem * len(direct))(*direct) if direct else None, len(direct),
                                    (PpWinoPackItem * len(wino))(*wino) if wino else None, len(wino), single)
                 plan.pack_batch_key = bkey
@@ -773,53 +732,14 @@ class StepEngine:
             if w_n:
                 lib.pp_wino_pack_weights_f16x3_batch(w_arr, w_n, st)
         for L in layers:
-            wb = plan.wb[L.name]
-            w, wf = L.conv.weight.data_ptr(), plan.wf[L.name].data_ptr()
-            wbp = wb.data_ptr() if wb is not None else None
-            if plan.wino[L.name]:
-                tile = plan.wino_tile[L.name]
-                f16f, f16b = plan.wino16_fwd[L.name], plan.wino16_bwd[L.name]
-                fn_f = plan.K.pp_wino_pack_weights_f16x3 if f16f else plan.K.pp_wino_pack_weights
-                fn_b = plan.K.pp_wino_pack_weights_f16x3 if f16b else plan.K.pp_wino_pack_weights
-                if fn_f is fn_b:
-                    fn_f(w, L.cout, L.cin, tile, wf, wbp, st)
-                else:
-                    fn_f(w, L.cout, L.cin, tile, wf, None, st)
-                    fn_b(w, L.cout, L.cin, tile, None, wbp, st)
-            else:
-                fn = plan.K.pp_pack_conv3x3_weights_f16x3 if plan.f16[L.name] else plan.K.pp_pack_conv3x3_weights
-                fn(w, L.cout, L.cin, L.cin_pad, wf, wbp, st)
+            plan.conv[L.name].pack(st)
         plan.packed_key = key
-
-    def _conv_bn_fused(self, plan, L: _Layer, x: View, out_ptr, ld_out, groups, mode, scale, shift, st):
-        """Forward convolution with the BatchNorm side fused into its epilogue (pp_conv3x3[_wino]_fwd_bn); returns the
-        number of partial-statistics rows per group (mode 1).  A lazy x is normalised + activated while it is loaded."""
-        C = L.cout
-        rows = plan.rows_out
-        stats, nbytes = plan.stats_args()
-        ws_ptr, ws_len = plan.ws_args()
-        lz = x.lazy_arg()
-        if plan.wino[L.name]:
-            vk = plan.vkeep[L.name].data_ptr() if L.name in plan.vkeep else None     # forward-only plans keep no V
-            a = (x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), out_ptr, ld_out, C,
-                 x.N, x.H, x.W, L.dil, 1 if plan.wino16_fwd[L.name] else 0, vk,
-                 ws_ptr, ws_len, mode, scale, shift, SLOPE, groups, stats, nbytes, ctypes.byref(rows))
-            assert lz is None, f'{L.name}: the Winograd path has no lazy-input form'
-            plan.K.pp_conv3x3_wino_fwd_bn(*a, st)
-        else:
-            a = (x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), out_ptr, ld_out, C,
-                 x.N, x.H, x.W, L.dil, 1 if plan.f16[L.name] else 0, None, mode, scale, shift, SLOPE, groups,
-                 stats, nbytes, ctypes.byref(rows))
-            if lz is not None:          # (a shape without a lazy form fails inside: plan.lazy_out asked pp_conv3x3_lazy_ok)
-                plan.K.pp_conv3x3_fwd_bn_lazy(*a, ctypes.byref(lz), st)
-            else:
-                plan.K.pp_conv3x3_fwd_bn(*a, st)
-        return rows.value
 
     def _convbn_fwd(self, plan, L: _Layer, x: View, y: View, groups, training, st, pool_out: Optional[View] = None):
         """conv3x3 + BatchNorm + LeakyReLU of one layer.  pool_out: where the 2x2 max-pooled copy of the output goes when the
         caller wants it from the same pass; returns True when it was written (train-mode apply pass), else the caller pools."""
         coef = plan.coef[L.name]
+        op = plan.conv[L.name]
         C = L.cout
         assert x.C == L.cin_pad, (L.name, x.C, L.cin_pad)
         ppg = (x.N // groups) * (x.H // L.stride) * (x.W // L.stride)        # pixels of the OUTPUT per group
@@ -850,20 +770,15 @@ class StepEngine:
                 plan.K.pp_bn_train_finalize(*args, st)
 
         if L.stride == 2:
-            assert x.lazy_arg() is None and not lazy
+            assert not lazy
             # stride-2 / padding-1 convolution = the stride-1 convolution sampled at the even pixels (pp_spatial.hip)
             zf = plan.zfull[L.name]
-            if plan.f16[L.name]:
-                plan.K.pp_conv3x3_fwd_f16x3(x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), zf.data_ptr(), C, C,
-                                         x.N, x.H, x.W, L.dil, 0, None, st)
-            else:
-                plan.K.pp_conv3x3_fwd(x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), zf.data_ptr(), C, C,
-                                   x.N, x.H, x.W, L.dil, 0, st)
+            op.fwd(x, zf.data_ptr(), C, plan.ws_args(), st)
             plan.K.pp_stride2_gather(zf.data_ptr(), C, zptr, C, C, x.N, x.H // 2, x.W // 2, st)
         elif FUSE_BN:
             if training:
                 # z + per-block (sum, sum of squares) from the conv epilogue -> finalize -> y = lrelu(z*scale + shift)
-                rows = self._conv_bn_fused(plan, L, x, zptr, zld, groups, 1, None, None, st)
+                rows = op.fwd_bn(x, zptr, zld, groups, 1, None, None, plan.stats_args(), plan.ws_args(), plan.rows_out, st)
                 if sync:
                     # reference semantics under sharding: statistics of the WHOLE batch (models/unet.py:189) -- the local
                     # sums are taken again in ONE row per group (the epilogue's per-block rows are not all-reduced)
@@ -885,22 +800,10 @@ class StepEngine:
                 if L.name not in self._coefs_ready:
                     plan.K.pp_bn_eval_coeffs(C, groups, BN_EPS, bn.weight.data_ptr(), bn.bias.data_ptr(),
                                           bn.running_mean.data_ptr(), bn.running_var.data_ptr(), mean, invstd, scale, shift, st)
-                self._conv_bn_fused(plan, L, x, y.ptr, y.ld, groups, 2, scale, shift, st)
+                op.fwd_bn(x, y.ptr, y.ld, groups, 2, scale, shift, plan.stats_args(), plan.ws_args(), plan.rows_out, st)
             return
-        elif plan.wino[L.name]:
-            assert x.lazy_arg() is None, 'the unfused Winograd call has no lazy-input form (PP_FUSE_BN=0 implies PP_LAZY_BN=0)'
-            vk = plan.vkeep[L.name].data_ptr() if L.name in plan.vkeep else None
-            fwd = plan.K.pp_conv3x3_wino_fwd_f16x3 if plan.wino16_fwd[L.name] else plan.K.pp_conv3x3_wino_fwd
-            fwd(x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), zptr,
-                                    zld, C, x.N, x.H, x.W, L.dil, 0, vk, *plan.ws_args(), st)
-        elif plan.f16[L.name]:
-            assert x.lazy_arg() is None
-            plan.K.pp_conv3x3_fwd_f16x3(x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), zptr, zld, C,
-                                     x.N, x.H, x.W, L.dil, 0, None, st)
-        else:
-            assert x.lazy_arg() is None
-            plan.K.pp_conv3x3_fwd(x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), zptr, zld, C,
-                               x.N, x.H, x.W, L.dil, 0, st)
+        else:               # (PP_FUSE_BN=0 implies PP_LAZY_BN=0: no input is lazy here)
+            op.fwd(x, zptr, zld, plan.ws_args(), st)
         if sync:
             # reference semantics under sharding: statistics of the WHOLE batch (models/unet.py:189)
             sums = plan.bn_sums[L.name][0]
@@ -923,18 +826,8 @@ class StepEngine:
         """conv3x3 + GroupNorm + LeakyReLU of one layer, the same in train and eval mode: z = conv(x) (no fused epilogue),
         per-(image, group) statistics (pp_gn_stats), then the BatchNorm apply pass with one coefficient row per image."""
         C, gn = L.cout, L.bn
-        assert x.lazy_arg() is None and L.stride == 1
-        if plan.wino[L.name]:
-            vk = plan.vkeep[L.name].data_ptr() if L.name in plan.vkeep else None
-            fwd = plan.K.pp_conv3x3_wino_fwd_f16x3 if plan.wino16_fwd[L.name] else plan.K.pp_conv3x3_wino_fwd
-            fwd(x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), zptr, zld, C, x.N, x.H, x.W, L.dil, 0, vk,
-                *plan.ws_args(), st)
-        elif plan.f16[L.name]:
-            plan.K.pp_conv3x3_fwd_f16x3(x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), zptr, zld, C,
-                                     x.N, x.H, x.W, L.dil, 0, None, st)
-        else:
-            plan.K.pp_conv3x3_fwd(x.ptr, x.ld, x.C, plan.wf[L.name].data_ptr(), L.conv.bias.data_ptr(), zptr, zld, C,
-                               x.N, x.H, x.W, L.dil, 0, st)
+        assert L.stride == 1
+        plan.conv[L.name].fwd(x, zptr, zld, plan.ws_args(), st)
         coef = plan.coef[L.name]
         mean, invstd, scale, shift, xbar = (coef[i].data_ptr() for i in range(5))
         N, HW = x.N, x.H * x.W
@@ -954,13 +847,15 @@ class StepEngine:
         x, y_rec, groups, lazy_out, x_lazy = self._bwd_rec[L.name]
         # pre-BatchNorm output of the forward: in the layer's own z buffer, or -- lazy layer -- in the buffer of its output
         zptr, zld = (y_rec.ptr, y_rec.ld) if lazy_out else ((plan.zbuf[L.name].data_ptr(), C) if L.name in plan.zbuf else (None, C))
-        xlz = x.lazy_arg() if (x_lazy and not plan.wino[L.name]) else None      # (Winograd: the kept V was made from y already)
-        assert not x_lazy or plan.wino[L.name] or (xlz is not None and plan.f16[L.name]), f'{L.name}: lazy input without a lazy weight gradient'
+        op = plan.conv[L.name]
+        kind = op.sel.kind
+        xlz = x.lazy_arg() if (x_lazy and kind != 'wino') else None      # (Winograd: the kept V was made from y already)
+        assert not x_lazy or kind == 'wino' or (xlz is not None and kind == 'f16x3'), f'{L.name}: lazy input without a lazy weight gradient'
         ppg = (x.N // groups) * (x.H // L.stride) * (x.W // L.stride)        # pixels of the layer OUTPUT per group
         mean, invstd, scale, shift = (coef[i].data_ptr() for i in range(4))
         gw, gb, gg, gbeta = grads[L.conv.weight], grads[L.conv.bias], grads[L.bn.weight], grads[L.bn.bias]
         if (FUSE_WG1 and not L.gn and dx is None and pool is None and L.cin == 1 and L.stride == 1 and L.dil == 1 and not x_lazy
-                and not plan.wino[L.name] and not plan.f16[L.name] and not (training and self.comm is not None and self.sync_bn)):
+                and kind == 'fp32' and not (training and self.comm is not None and self.sync_bn)):
             # the first layer: dz has one reader, the weight gradient -- formed and consumed in one pass, never written
             if FUSE_BN and not training:
                 plan.K.pp_bn_lrelu_bwd_eval_wgrad_c1(dy.ptr, dy.ld, y_rec.ptr, y_rec.ld, scale, L.bn.weight.data_ptr(), L.bn.bias.data_ptr(),
@@ -980,11 +875,9 @@ class StepEngine:
             if plan.wg_pending[slot]:                   # the weight gradient that last read this dz buffer (two layers ago)
                 torch.cuda.current_stream().wait_event(plan.wg_done[slot])
         dz = (plan.s1b if slot else plan.s1).data_ptr()
-        f16 = plan.f16[L.name]
-        need_amax = L.name in plan.amax                      # split-fp16 consumers scale dz by a power of two from max |dz|
+        am = op.amax.data_ptr() if op.amax is not None else None      # split-fp16 consumers scale dz by a power of two from max |dz|
         if L.gn:
             # GroupNorm: statistics of this forward per (image, group), whatever `training` and sync_bn say
-            am = plan.amax[L.name].data_ptr() if need_amax else None
             xbar, gn = coef[4].data_ptr(), L.bn
             if pool is not None:
                 y = y_rec
@@ -996,7 +889,6 @@ class StepEngine:
                                        gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C, x.H * x.W, x.N, gn.num_groups, SLOPE,
                                        plan.ws.data_ptr(), plan.ws_bytes, am, st)
         elif pool is not None:
-            am = plan.amax[L.name].data_ptr() if need_amax else None
             y = y_rec
             if FUSE_BN and not training:
                 plan.K.pp_bn_lrelu_bwd_eval_pool(dy.ptr, dy.ld, pool.ptr, pool.ld, y.ptr, y.ld, scale, L.bn.weight.data_ptr(),
@@ -1011,7 +903,7 @@ class StepEngine:
             y = y_rec
             plan.K.pp_bn_lrelu_bwd_eval(dy.ptr, dy.ld, y.ptr, y.ld, scale, L.bn.weight.data_ptr(), L.bn.bias.data_ptr(), dz, C,
                                      gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C, ppg * groups, SLOPE,
-                                     plan.ws.data_ptr(), plan.ws_bytes, plan.amax[L.name].data_ptr() if need_amax else None, st)
+                                     plan.ws.data_ptr(), plan.ws_bytes, am, st)
         elif training and self.comm is not None and self.sync_bn:
             loc, glob = plan.bn_sums[L.name][1], plan.bn_sums[L.name][2]
             plan.K.pp_bn_lrelu_bwd_sums(dy.ptr, dy.ld, zptr, zld, scale, shift, mean, invstd, C, ppg, groups, SLOPE,
@@ -1021,11 +913,11 @@ class StepEngine:
             plan.K.pp_bn_lrelu_bwd_apply(dy.ptr, dy.ld, zptr, zld, scale, shift, mean, invstd, L.bn.weight.data_ptr(), 1,
                                       loc.data_ptr(), glob.data_ptr(), ppg * self.world, dz, C, gg.data_ptr(),
                                       gbeta.data_ptr(), gb.data_ptr(), 0, C, ppg, groups, SLOPE, plan.ws.data_ptr(),
-                                      plan.ws_bytes, plan.amax[L.name].data_ptr() if need_amax else None, st)
-        elif need_amax:
+                                      plan.ws_bytes, am, st)
+        elif am is not None:
             plan.K.pp_bn_lrelu_bwd_amax(dy.ptr, dy.ld, zptr, zld, scale, shift, mean, invstd, L.bn.weight.data_ptr(),
                                      1 if training else 0, dz, C, gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C, ppg,
-                                     groups, SLOPE, plan.ws.data_ptr(), plan.ws_bytes, plan.amax[L.name].data_ptr(), st)
+                                     groups, SLOPE, plan.ws.data_ptr(), plan.ws_bytes, am, st)
         else:
             plan.K.pp_bn_lrelu_bwd(dy.ptr, dy.ld, zptr, zld, scale, shift, mean, invstd, L.bn.weight.data_ptr(),
                                 1 if training else 0, dz, C, gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C, ppg,
@@ -1035,59 +927,22 @@ class StepEngine:
             dzf = plan.dzfull[L.name]
             plan.K.pp_stride2_scatter(dz, C, dzf.data_ptr(), C, C, x.N, x.H // 2, x.W // 2, st)
             dz = dzf.data_ptr()
-        am = plan.amax[L.name].data_ptr() if need_amax else None
-
-        def weight_gradient():
-            """On the second stream when there is one (it then gets its own workspace): it waits for everything the main stream
-            has enqueued so far."""
-            wst, wws, wws_bytes = st, plan.ws.data_ptr(), plan.ws_bytes
-            if side is not None:
-                plan.dz_ready[slot].record(torch.cuda.current_stream())
-                side.wait_event(plan.dz_ready[slot])
-                wst, wws, wws_bytes = side.cuda_stream, plan.ws_wg.data_ptr(), plan.wg_ws_bytes
-            if plan.wino[L.name]:
-                if plan.wino16_wg[L.name]:
-                    plan.K.pp_conv3x3_wino_bwd_weight_f16x3(dz, C, C, x.ptr, x.ld, L.cin, x.N, x.H, x.W, L.dil, gw.data_ptr(), 0,
-                                                         plan.vkeep[L.name].data_ptr(), wws, wws_bytes, am, wst)
-                else:
-                    plan.K.pp_conv3x3_wino_bwd_weight(dz, C, C, x.ptr, x.ld, L.cin, x.N, x.H, x.W, L.dil, gw.data_ptr(), 0,
-                                                   plan.vkeep[L.name].data_ptr(), wws, wws_bytes, wst)
-            elif f16 and xlz is not None:      # x is the raw output of the layer in front: normalised + activated while it is staged
-                plan.K.pp_conv3x3_bwd_weight_f16x3_lazy(dz, C, C, x.ptr, x.ld, L.cin_pad, L.cin, x.N, x.H, x.W, L.dil, gw.data_ptr(), 0,
-                                                        wws, wws_bytes, plan.amax[L.name].data_ptr(), ctypes.byref(xlz), wst)
-            elif f16:     # split-fp16 halo kernel where the shape qualifies, the fp32 kernels otherwise
-                plan.K.pp_conv3x3_bwd_weight_f16x3(dz, C, C, x.ptr, x.ld, L.cin_pad, L.cin, x.N, x.H, x.W, L.dil, gw.data_ptr(), 0,
-                                                wws, wws_bytes, plan.amax[L.name].data_ptr(), wst)
-            else:
-                plan.K.pp_conv3x3_bwd_weight(dz, C, C, x.ptr, x.ld, L.cin_pad, L.cin, x.N, x.H, x.W, L.dil, gw.data_ptr(), 0,
-                                          wws, wws_bytes, wst)
-            if side is not None:
-                plan.wg_done[slot].record(side)
-                plan.wg_pending[slot] = True
-
-        def data_gradient():
-            """The critical chain, always on the main stream."""
-            if plan.wino[L.name]:
-                if plan.wino16_bwd[L.name]:
-                    plan.K.pp_conv3x3_wino_bwd_data_f16x3(dz, C, C, plan.wb[L.name].data_ptr(), dx.ptr, dx.ld, L.cin, x.N, x.H, x.W,
-                                                       L.dil, 1 if dx_accumulate else 0, plan.ws.data_ptr(), plan.ws_bytes, am, st)
-                else:
-                    plan.K.pp_conv3x3_wino_bwd_data(dz, C, C, plan.wb[L.name].data_ptr(), dx.ptr, dx.ld, L.cin, x.N, x.H, x.W,
-                                                 L.dil, 1 if dx_accumulate else 0, plan.ws.data_ptr(), plan.ws_bytes, st)
-            elif f16:
-                plan.K.pp_conv3x3_bwd_data_f16x3(dz, C, C, plan.wb[L.name].data_ptr(), dx.ptr, dx.ld, L.cin, x.N, x.H, x.W, L.dil,
-                                              1 if dx_accumulate else 0, plan.amax[L.name].data_ptr(), st)
-            else:
-                plan.K.pp_conv3x3_bwd_data(dz, C, C, plan.wb[L.name].data_ptr(), dx.ptr, dx.ld, L.cin, x.N, x.H, x.W, L.dil,
-                                        1 if dx_accumulate else 0, st)
 
         # Order on two streams: the weight gradient starts WITH the data gradient.  (Round 5 measured the alternative -- the weight
         # gradient enqueued behind the data gradient, so that it runs beside the HBM-bound BatchNorm backward of the next layer
         # instead of beside another matrix kernel: 31.9 -> 32.9 ms, the BatchNorm family 7.5 -> 9.7 ms.  The direct weight
         # gradients read 2 - 2.5 GB per launch themselves; profiles/r05_experiments/wgrad_behind_dgrad.log.)
-        weight_gradient()
-        if dx is not None:
-            data_gradient()
+        ws = (plan.ws.data_ptr(), plan.ws_bytes)
+        if side is None:
+            op.bwd_weight(dz, x, gw.data_ptr(), ws, xlz, st)
+        else:       # on the second stream, with its own workspace: it waits for everything the main stream has enqueued so far
+            plan.dz_ready[slot].record(torch.cuda.current_stream())
+            side.wait_event(plan.dz_ready[slot])
+            op.bwd_weight(dz, x, gw.data_ptr(), (plan.ws_wg.data_ptr(), plan.wg_ws_bytes), xlz, side.cuda_stream)
+            plan.wg_done[slot].record(side)
+            plan.wg_pending[slot] = True
+        if dx is not None:          # the critical chain, always on the main stream
+            op.bwd_data(dz, x, dx, dx_accumulate, ws, st)
 
     def _side_stream(self, plan):
         """The second stream of the weight gradients, or None (switched off, or a plan without the second dz buffer)."""

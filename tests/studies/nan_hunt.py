@@ -94,10 +94,11 @@ for ep in range(a.epochs):
                 bufs['z:' + n] = t
             for n, t in plan.coef.items():
                 bufs['coef:' + n] = t
-            for n, t in plan.amax.items():
+            amax = {n: op.amax for n, op in plan.conv.items() if op.amax is not None}
+            for n, t in amax.items():
                 bufs['amax:' + n] = t
             found['buffers'] = {k: fin(v) for k, v in bufs.items()}
-            found['amax_values'] = {n: float(t) for n, t in plan.amax.items()}
+            found['amax_values'] = {n: float(t) for n, t in amax.items()}
             break
         opt.step()
     if found:

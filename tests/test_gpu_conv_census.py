@@ -1,6 +1,6 @@
 """Census of the convolution launches of real steps, each replayed against a float64 reference.
 
-The per-kernel parity tests use hand-picked case lists; which kernel a layer gets is a function of its shape (engine.conv_select).
+The per-kernel parity tests use hand-picked case lists; which kernel a layer gets is a function of its shape (convop.select).
 Here every convolution-family launch of real full-width steps is recorded -- the engine's entry-point table (plan.K) is wrapped in a
 recording proxy -- and every distinct launch (entry point, storage kind, every non-pointer argument, which optional pointers were
 null, the ld / groups of a lazy input) is replayed on seeded random operands with the recorded ld's and flags and canaries in the

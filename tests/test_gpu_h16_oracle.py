@@ -32,7 +32,7 @@ def _split_k(L, h, w, plan) -> int:
     pp_conv.hip: 128 < Cin <= 192, Cin % 64 == 0, and the one-row halo kernel takes Cin / 2 -- dil 1, Cout % 32 == 0,
     Cout <= 192, W % 32 == 0, H % 4 == 0).  The first launch stores its half-sum (bias included) in the 16-bit output buffer and
     the second adds to what it reads back."""
-    if plan.wino[L.name] or not plan.f16[L.name]:
+    if plan.conv[L.name].sel.kind != 'f16x3':
         return 0
     c = L.cin
     if not (128 < c <= 192 and c % 64 == 0):
@@ -231,7 +231,7 @@ def test_per_layer_forward_teacher_forced(kind, bn_eval):
         x = logical_input(L.x)[:, :L.cin]
         w, b = sd[p + '.conv.weight'].double(), sd[p + '.conv.bias'].double()
         c1 = sites[p + ':split']
-        z, noise = _conv64(x, w, b, L.dil, c1, kind, plan.wino[L.name])
+        z, noise = _conv64(x, w, b, L.dil, c1, kind, plan.conv[L.name].sel.kind == 'wino')
         coef = plan.coef[L.name].double().cpu()          # (4, groups, C): mean, invstd, scale, shift
         n = z.shape[0] // L.groups
         per_img = lambda r: torch.cat([r[g][None, :, None, None].expand(n, -1, -1, -1) for g in range(L.groups)])  # noqa: E731

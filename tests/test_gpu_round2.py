@@ -61,9 +61,9 @@ def test_benchmark_shape_step_against_oracle():
               f'{sum(n for _, n, _ in O.MASK_STATS)} LeakyReLU branches and {sum(n for _, n, _ in O.POOL_STATS)} pool windows re-aligned')
         if not plan_checked:                       # the plan really is the benchmark's selection
             plan = model.engine.last_plan
-            assert plan.wino['dec_block5.conv_block.conv_layer1'] and plan.wino16_fwd['enc_block6.conv_block.conv_layer1']
-            assert plan.wino_tile['enc_block6.conv_block.conv_layer2'] == 4
-            assert plan.f16['dec_block1.conv_block.conv_layer1'] and plan.f16['enc_block2.conv_block.conv_layer2']
+            assert plan.conv['dec_block5.conv_block.conv_layer1'].sel.kind == 'wino' and plan.conv['enc_block6.conv_block.conv_layer1'].sel.split
+            assert plan.conv['enc_block6.conv_block.conv_layer2'].sel.tile == 4
+            assert all(plan.conv[n].sel.kind == 'f16x3' for n in ('dec_block1.conv_block.conv_layer1', 'enc_block2.conv_block.conv_layer2'))
             plan_checked = True
         sd.update({k: v.detach().cpu().clone() for k, v in model.state_dict().items()})
 

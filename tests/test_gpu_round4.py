@@ -55,10 +55,10 @@ def test_benchmark_batch_gradients_against_oracle(bn_training):
     # the plan is the benchmark's: 64 images per launch, Winograd F(4x4) split-fp16 GEMMs on the 32x32 maps, split-fp16
     # halo kernels above; the weight-gradient split counts quoted here are functions of exactly this shape
     assert (plan.Bt, plan.H, plan.W, plan.G) == (64, 256, 256, 2)
-    assert plan.wino['dec_block5.conv_block.conv_layer1'] and plan.wino16_wg['enc_block6.conv_block.conv_layer1']
-    assert plan.f16['dec_block1.conv_block.conv_layer1'] and plan.f16['enc_block2.conv_block.conv_layer2']
+    assert plan.conv['dec_block5.conv_block.conv_layer1'].sel.kind == 'wino' and plan.conv['enc_block6.conv_block.conv_layer1'].sel.split
+    assert all(plan.conv[n].sel.kind == 'f16x3' for n in ('dec_block1.conv_block.conv_layer1', 'enc_block2.conv_block.conv_layer2'))
     splits = {n: lib.pp_conv3x3_wino_bwd_weight_splits(L.cout, L.cin, 64, 32, 32, L.dil)
-              for n, L in ((L.name, L) for L in model.engine.layers) if plan.wino[n] and plan.sizes[3] == (32, 32)
+              for n, L in ((L.name, L) for L in model.engine.layers) if plan.conv[n].sel.kind == 'wino' and plan.sizes[3] == (32, 32)
               and L.name != 'dec_block3.conv_block.conv_layer1'}
     splits2 = {n: lib.pp_conv3x3_wino_bwd_weight_splits(L.cout, L.cin, 4, 32, 32, L.dil)
                for n, L in ((L.name, L) for L in model.engine.layers) if n in splits}

@@ -545,6 +545,27 @@ int pp_crf_loss_fwd(const float* logits, const float* image, const float* valid_
 int pp_crf_loss_bwd(const float* unit_grad, const double* sums, int has_mask, const float* g_up, float grad_scale,
                     float* dlogits, long long n, void* stream);
 
+/* Connected components of class maps and the keep-largest-component filter of an evaluation pipeline (this implementation's
+ * addition: the reference scores its raw arg-max, inference.py:159-190).  cls: int64 class maps [N][H][W].
+ * Two pixels of ONE image are connected when they are neighbours -- the 4-neighbourhood for connectivity 1, the 8-neighbourhood
+ * for connectivity 2 (scipy.ndimage.generate_binary_structure(2, connectivity); 1 is what hd95 uses) -- and hold the same
+ * value, whatever the value: background is labelled like every class, all in one pass.
+ * pp_label_components: labels[n][y][x] (int32) = the smallest row-major index y * W + x among the pixels of that pixel's
+ *   component within its image: a canonical form, unique and independent of scheduling.
+ * pp_keep_largest_components: for every image and every foreground class k in 1 .. K-1 the pixels of class k outside that
+ *   class's largest component become 0; everything else is copied (class 0 is never filtered; a value outside [0, K) is copied
+ *   and counted nowhere).  Of components of equal size the one with the smallest label is kept, i.e. the one that holds the
+ *   lowest row-major pixel (numpy.argmax(numpy.bincount(scipy_labels)[1:])).  out may alias cls.  stats: int32 [N][K][2] =
+ *   {components of class k before filtering, pixels kept}; {0, 0} for k = 0 and for absent classes.
+ * 1 <= K <= 32, N H W < 2^31.  Both calls enqueue a launch sequence fixed by the shape (no host synchronisation, no block waits
+ * for another, integer atomics only: the same bits in every run) and need pp_components_workspace(N, K, H, W) bytes
+ * (pp_label_components: the value for K = 1 suffices). */
+size_t pp_components_workspace(int N, int K, int H, int W);
+int pp_label_components(const int64_t* cls, int N, int H, int W, int connectivity, int32_t* labels, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int pp_keep_largest_components(const int64_t* cls, int N, int K, int H, int W, int connectivity, int64_t* out, int32_t* stats,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser (torch.optim.Adam(lr, weight_decay) at train_chaos.py:219) ------------------------------- */
 int pp_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                  float eps, float weight_decay, int step, void* stream);

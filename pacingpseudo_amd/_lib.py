@@ -172,6 +172,9 @@ _PROTOS = {
     'pp_crf_loss_workspace': (sz, [i32, i32, i32]),
     'pp_crf_loss_fwd': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, sz, vp]),
     'pp_crf_loss_bwd': (i32, [vp, vp, i32, vp, f32, vp, i64, vp]),
+    'pp_components_workspace': (sz, [i32, i32, i32, i32]),
+    'pp_label_components': (i32, [vp, i32, i32, i32, i32, vp, vp, sz, vp]),
+    'pp_keep_largest_components': (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     'pp_adam_step': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp]),
     'pp_sgd_momentum_step': (i32, [vp, vp, vp, i64, f32, f32, f32, i32, vp]),
     'pp_channel_scale': (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),
@@ -221,7 +224,7 @@ for _n in H16_ENTRIES:
 _H16_SET = frozenset(H16_ENTRIES) | {'pp_memory_update'}
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
-MIN_LIB_VERSION = 605      # include/pacingpseudo_hip.h with the gated-CRF loss entry points (pp_runtime.cpp: PP_VERSION)
+MIN_LIB_VERSION = 606      # include/pacingpseudo_hip.h with the connected-component entry points (pp_runtime.cpp: PP_VERSION)
 PROF_KINDS = ('conv_igemm', 'conv_wgrad', 'bn', 'spatial', 'loss', 'optim', 'misc', 'wino_gemm', 'wino_wgrad',
               'wino_xform', 'conv_f16x3', 'wino_gemm_f16x3', 'wino_wgrad_f16x3', 'conv_wgrad_f16x3', 'conv_halo_f16x3')
 

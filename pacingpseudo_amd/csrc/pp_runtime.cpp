@@ -5,7 +5,7 @@
 #include <vector>
 #include <mutex>
 
-#define PP_VERSION 605      // 605: gated-CRF loss (pp_crf_loss_workspace / _fwd / _bwd); 604: EMA weight averaging (pp_*_step_ema, pp_ema_update, pp_slab_swap); 603: gradient-norm clipping (pp_grad_sumsq, pp_grad_clip_finalize, *_step_clip); 602: 9 <= K <= 32 classes in the loss and head kernels; 601: GroupNorm entry points; 600: round 6 (the ABI changed incompatibly in round 5 without a bump: ADVICE r05); _lib.py checks a minimum
+#define PP_VERSION 606      // 606: connected components / keep-largest-component filter (pp_components_workspace, pp_label_components, pp_keep_largest_components); 605: gated-CRF loss (pp_crf_loss_workspace / _fwd / _bwd); 604: EMA weight averaging (pp_*_step_ema, pp_ema_update, pp_slab_swap); 603: gradient-norm clipping (pp_grad_sumsq, pp_grad_clip_finalize, *_step_clip); 602: 9 <= K <= 32 classes in the loss and head kernels; 601: GroupNorm entry points; 600: round 6 (the ABI changed incompatibly in round 5 without a bump: ADVICE r05); _lib.py checks a minimum
 
 static thread_local char g_err[512] = "";
 

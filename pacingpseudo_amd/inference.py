@@ -60,6 +60,12 @@ parser.add_argument('--norm_op', type=str, default='batch', choices=['batch', 'g
                     help='block normaliser the checkpoint was trained with: batch = nn.BatchNorm2d (the reference); group = nn.GroupNorm(--norm_groups, C): '
                          'per-image statistics, no running state, the same function in train and eval mode (fp32 storage only)')
 parser.add_argument('--norm_groups', type=int, default=8, help='channel groups of --norm_op group; must divide every block width')
+parser.add_argument('--keep_largest_cc', action='store_true', default=False,
+                    help='post-process the arg-max on the device before scoring: of every foreground class keep only the largest connected '
+                         'component of each slice (ties: the one holding the lowest row-major pixel), the rest becomes background; '
+                         'eval_data.npz gains ncomp and removed')
+parser.add_argument('--cc_connectivity', type=int, default=1, choices=[1, 2],
+                    help='neighbourhood of --keep_largest_cc: 1 = 4-neighbourhood (what HD95 uses), 2 = 8-neighbourhood')
 
 
 def load_backbone(model, state_dict):
@@ -78,11 +84,15 @@ def load_backbone(model, state_dict):
     return model
 
 
-def evaluate(model, loader, num_classes, spacing, device):
-    """-> (dicearr, hd95arr), both (slices, classes) float32 with NaN where the reference skips a class."""
+def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False, cc_connectivity=1):
+    """-> (dicearr, hd95arr), both (slices, classes) float32 with NaN where the reference skips a class.  With keep_largest_cc the
+    arg-max is filtered on the device first (utils.postprocess.keep_largest_components) and both metrics score the filtered map;
+    then -> (dicearr, hd95arr, ncomp, removed): ncomp (slices, classes) int32 = components per class before filtering, removed
+    (slices,) int64 = pixels set to background."""
     from .data import expand_compact
     from .utils.metrics import batch_dice_counts, batch_hd95
-    dice_rows, hd_rows = [], []
+    from .utils.postprocess import keep_largest_components
+    dice_rows, hd_rows, ncomp_rows, removed_rows = [], [], [], []
     model.eval()
     for groups in loader:
         for batch in (groups if isinstance(groups, list) else [groups]):   # same-shape groups (data.collate_by_shape)
@@ -90,13 +100,25 @@ def evaluate(model, loader, num_classes, spacing, device):
             image, label = batch['image'], batch['label']
             with torch.no_grad():
                 logits = model(image)['segmentation/logits']
-            c = batch_dice_counts(logits, label)                           # |P & T|, |P|, |T| per (slice, class), one launch
+            if keep_largest_cc:
+                raw = logits.argmax(1)
+                pred, stats = keep_largest_components(raw, num_classes, cc_connectivity, return_stats=True)
+                ncomp_rows.extend(stats[..., 0].tolist())
+                removed_rows.extend((pred != raw).flatten(1).sum(1).tolist())
+                # the counting kernel takes an arg-max itself: the arg-max of a one-hot map is the map, exactly
+                scores = torch.nn.functional.one_hot(pred, num_classes).permute(0, 3, 1, 2)
+            else:
+                scores = logits
+            c = batch_dice_counts(scores, label)                           # |P & T|, |P|, |T| per (slice, class), one launch
             inter, ps, ts = c[..., 0], c[..., 1], c[..., 2]
             with np.errstate(invalid='ignore', divide='ignore'):
                 dice = 2.0 * inter / np.maximum(ps + ts, 1e-8)             # inference.py:211-213 (no smoothing term here)
             dice[(ps == 0) & (ts == 0)] = np.nan                           # :208-209
             dice_rows.extend(dice.tolist())
-            hd_rows.extend(batch_hd95(logits.argmax(1), label.argmax(1), num_classes, spacing).tolist())
+            hd_rows.extend(batch_hd95(pred if keep_largest_cc else logits.argmax(1), label.argmax(1), num_classes, spacing).tolist())
+    if keep_largest_cc:
+        return (np.array(dice_rows, np.float32), np.array(hd_rows, np.float32),
+                np.array(ncomp_rows, np.int32).reshape(-1, num_classes), np.array(removed_rows, np.int64))
     return np.array(dice_rows, np.float32), np.array(hd_rows, np.float32)
 
 
@@ -123,8 +145,14 @@ def main_interface(args):
                                          multiprocessing_context=loader_context(args.num_workers))
     logging.info('Length {}'.format(len(loader)))
     load_backbone(model, torch.load(args.checkpoint_file, map_location=device))
-    dicearr, hd95arr = evaluate(model, loader, num_classes, spacing, device)
-    np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr)
+    if args.keep_largest_cc:
+        dicearr, hd95arr, ncomp, removed = evaluate(model, loader, num_classes, spacing, device, True, args.cc_connectivity)
+        np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, ncomp=ncomp, removed=removed)
+        logging.info('Largest-component filter (connectivity {}): {} pixels set to background, {} of {} slices changed'.format(
+            args.cc_connectivity, int(removed.sum()), int((removed > 0).sum()), len(removed)))
+    else:
+        dicearr, hd95arr = evaluate(model, loader, num_classes, spacing, device)
+        np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr)
     meter_dice = [AvgMeter() for _ in range(num_classes)]
     meter_hd95 = [AvgMeter() for _ in range(num_classes)]
     for drow, hrow in zip(dicearr, hd95arr):

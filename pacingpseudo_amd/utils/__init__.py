@@ -1,1 +1,2 @@
 from .utils import AvgMeter, cosine_lr_decay, gaussian_ramp_up, linear_lr_decay, poly_lr_decay  # noqa: F401
+from .postprocess import keep_largest_components, label_components  # noqa: F401

@@ -566,6 +566,22 @@ int pp_label_components(const int64_t* cls, int N, int H, int W, int connectivit
 int pp_keep_largest_components(const int64_t* cls, int N, int K, int H, int W, int connectivity, int64_t* out, int32_t* stats,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Test-time augmentation over flips and quarter turns (this implementation's addition: the reference scores one forward pass per
+ * slice, inference.py:159-190).  op in 0 .. 7: bit 0 flips the last axis (W), bit 1 flips H, bit 2 transposes
+ * them; the forward view of a[..][H][W] is built as transpose, then flip H, then flip W, and has shape (W, H) under bit 2, (H, W)
+ * otherwise.  H and W are ALWAYS those of the un-viewed frame.
+ * pp_tta_view: x [planes][H][W] -> out [planes][H'][W'], the forward view (planes = N * C); out must not overlap x.
+ * pp_tta_accumulate: logits [N][K][H'][W'] = the network's output for view `op`; per pixel the soft-max over K (fp32, the maximum
+ *   subtracted) goes to the inverse-mapped position of acc [N][K][H][W]: stored when first != 0 -- the previous contents of acc
+ *   are never read, callers need not clear it -- and added otherwise, one fp32 addition per element.
+ * pp_tta_finalize: acc *= 1 / views in place (views 1, 2, 4 or 8: exact) and, unless cls is null, cls [N][H][W] = the arg-max
+ *   over K of the scaled values, the first maximum as in pp_argmax_channels.
+ * 1 <= K <= 32, H, W >= 1 of any size, N K H W < 2^31.  One launch each, fixed by the shape and op; no atomics, no host
+ * synchronisation: with the views accumulated in a fixed order the result is the same bits in every run. */
+int pp_tta_view(const float* x, int planes, int H, int W, int op, float* out, void* stream);
+int pp_tta_accumulate(const float* logits, int N, int K, int H, int W, int op, int first, float* acc, void* stream);
+int pp_tta_finalize(float* acc, int N, int K, int H, int W, int views, int64_t* cls, void* stream);
+
 /* ---- optimiser (torch.optim.Adam(lr, weight_decay) at train_chaos.py:219) ------------------------------- */
 int pp_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                  float eps, float weight_decay, int step, void* stream);

@@ -175,6 +175,9 @@ _PROTOS = {
     'pp_components_workspace': (sz, [i32, i32, i32, i32]),
     'pp_label_components': (i32, [vp, i32, i32, i32, i32, vp, vp, sz, vp]),
     'pp_keep_largest_components': (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    'pp_tta_view': (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    'pp_tta_accumulate': (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    'pp_tta_finalize': (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
     'pp_adam_step': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp]),
     'pp_sgd_momentum_step': (i32, [vp, vp, vp, i64, f32, f32, f32, i32, vp]),
     'pp_channel_scale': (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),

@@ -1,6 +1,7 @@
 // Post-processing of hard class maps on the device: connected-component labelling and the keep-largest-component filter of an
 // evaluation pipeline (include/pacingpseudo_hip.h; DESIGN.md section 7, "Largest-component filter").  The reference scores its raw
-// arg-max (inference.py:159-190); class maps are integers, so there is one build of this file in every storage mode.
+// arg-max (inference.py:159-190); class maps are integers, so there is one build of this file in every storage mode.  The second
+// half of the file holds the test-time-augmentation kernels (views, soft-max accumulation, finalize) on the fp32 logits.
 //
 // Two pixels of one image are connected when they are neighbours (4- or 8-neighbourhood) and hold the same value.  The label of a
 // pixel is the smallest row-major index of its component, so the result is unique.  Structure: a union-find forest over pixel
@@ -317,4 +318,318 @@ extern "C" int pp_keep_largest_components(const int64_t* cls, int N, int K, int 
                      w.best, w.ncomp, H * W, total, items, K, (long long*)out, stats);
   pp_prof_end(s);
   return pp_launch_status("keep_largest_components");
+}
+
+// ================================================================================================================================
+// Test-time augmentation over the dihedral group (include/pacingpseudo_hip.h; DESIGN.md section 7, "Test-time augmentation").
+// op: bit 0 flips W, bit 1 flips H, bit 2 transposes; the forward view of a[H][W] is transpose, then flip H, then flip W, so the view
+// pixel (i, j) of a view of shape (Hv, Wv) -- (W, H) under bit 2, else (H, W) -- is the source pixel
+//   i2 = op & 2 ? Hv - 1 - i : i,  j2 = op & 1 ? Wv - 1 - j : j,  (y, x) = op & 4 ? (j2, i2) : (i2, j2).
+//   tta_view_*_kernel   out[view pixel] = x[source pixel]                                   per plane
+//   tta_acc_*_kernel    acc[k][source pixel] (+)= softmax_k(logits[.][view pixel])          the K values of a pixel in registers
+//   tta_finalize_kernel acc *= 1 / views, cls = first-maximum arg-max of the scaled values
+// Ops without bit 2 (*_row_kernel): a thread takes 4 consecutive pixels of a row (16-byte accesses) when W % 4 == 0 and the pointers
+// are 16-byte aligned, one pixel otherwise; under a W flip lane l + 1 reads / writes the vector (or word) just below lane l's and the
+// vector is reversed, so both global sides are runs of consecutive addresses.
+// Ops with bit 2 (*_tile_kernel): a block owns a 32 x 32 pixel tile.  Each thread loads its pixels along the rows of the side it
+// reads (32 lanes = 128 consecutive bytes), the planes go through LDS tiles of 32 rows x 33 words and come back transposed, so the
+// other side is walked along ITS rows, 128 consecutive bytes per 32 lanes again.  Bank rule (ds_write_b32 / ds_read_b32: bank =
+// word address % 32, conflicts inside a 32-lane half): the write of a half is row r, columns 0 .. 31 -> banks (33 r + c) % 32, 32
+// different ones; the read is rows 0 .. 31 of column c -> banks (33 l + c) % 32 = (l + c) % 32, 32 different ones: 0 extra cycles
+// on either side (an unpadded row of 32 words would put the whole read on one bank: 32-way).
+// No atomics, no host synchronisation, a launch fixed by the shape and op; every acc element is touched by exactly one thread per
+// launch and the views are added in the caller's order: the same bits in every run.
+#define TTA_THREADS 256
+#define TTA_TILE 32
+#define TTA_LD (TTA_TILE + 1)
+#define TTA_ROWS (TTA_THREADS / TTA_TILE)            // tile rows one pass of the block covers: 8
+#define TTA_PER (TTA_TILE / TTA_ROWS)                // pixels per thread: 4
+#define TTA_CHUNK 8                                  // planes in LDS at a time: 8 x 32 x 33 x 4 B = 33 KiB, four blocks per CU
+#define TTA_MAX_BLOCKS (1 << 20)
+
+__device__ __forceinline__ int tta_flip(int v, int n, int on) { return on ? n - 1 - v : v; }
+
+// the soft-max of one pixel in place, the maximum subtracted
+template <int MK>
+__device__ __forceinline__ void tta_softmax(float (&v)[MK], int K) {
+  float m = v[0];
+#pragma unroll
+  for (int k = 1; k < MK; ++k)
+    if (k < K) m = fmaxf(m, v[k]);
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < MK; ++k)
+    if (k < K) { v[k] = expf(v[k] - m); s += v[k]; }
+  const float inv = 1.f / s;
+#pragma unroll
+  for (int k = 0; k < MK; ++k)
+    if (k < K) v[k] *= inv;
+}
+
+__device__ __forceinline__ float4 tta_rev4(float4 v, int on) { return on ? make_float4(v.w, v.z, v.y, v.x) : v; }
+
+// ---- ops 0 .. 3: rows stay rows ----
+// x, out: [planes][H][W]
+template <bool VEC>
+__global__ __launch_bounds__(TTA_THREADS) void tta_view_row_kernel(const float* __restrict__ x, int H, int W, int op, long long total,
+                                                                   float* __restrict__ out) {
+  const int Wq = VEC ? W / 4 : W;                                       // items per row
+  for (long long g = (long long)blockIdx.x * TTA_THREADS + threadIdx.x; g < total; g += (long long)gridDim.x * TTA_THREADS) {
+    const long long row = g / Wq;                                        // plane * H + i
+    const int q = (int)(g - row * Wq), i = (int)(row % H);
+    const long long src_row = row - i + tta_flip(i, H, op & 2);
+    if (VEC) {
+      const float4 v = *reinterpret_cast<const float4*>(x + src_row * W + 4 * tta_flip(q, Wq, op & 1));
+      *reinterpret_cast<float4*>(out + row * W + 4 * q) = tta_rev4(v, op & 1);
+    } else {
+      out[row * W + q] = x[src_row * W + tta_flip(q, W, op & 1)];
+    }
+  }
+}
+
+// logits, acc: [N][K][H][W]; total = N * H * (VEC ? W / 4 : W)
+template <int MK, bool VEC>
+__global__ __launch_bounds__(TTA_THREADS) void tta_acc_row_kernel(const float* __restrict__ logits, int K, int H, int W, int op, int first,
+                                                                  long long total, float* __restrict__ acc) {
+  const int Wq = VEC ? W / 4 : W;
+  const size_t HW = (size_t)H * W;
+  for (long long g = (long long)blockIdx.x * TTA_THREADS + threadIdx.x; g < total; g += (long long)gridDim.x * TTA_THREADS) {
+    const long long row = g / Wq;                                        // n * H + i
+    const int q = (int)(g - row * Wq), n = (int)(row / H), i = (int)(row - (long long)n * H);
+    const float* src = logits + (size_t)n * K * HW + (size_t)i * W + (VEC ? 4 * q : q);
+    float* dst = acc + (size_t)n * K * HW + (size_t)tta_flip(i, H, op & 2) * W + (VEC ? 4 : 1) * tta_flip(q, Wq, op & 1);
+    if (VEC) {
+      float a[MK], b[MK], c[MK], d[MK];
+#pragma unroll
+      for (int k = 0; k < MK; ++k)
+        if (k < K) {
+          const float4 v = *reinterpret_cast<const float4*>(src + k * HW);
+          a[k] = v.x; b[k] = v.y; c[k] = v.z; d[k] = v.w;
+        }
+      tta_softmax(a, K); tta_softmax(b, K); tta_softmax(c, K); tta_softmax(d, K);
+#pragma unroll
+      for (int k = 0; k < MK; ++k)
+        if (k < K) {
+          float4 p = tta_rev4(make_float4(a[k], b[k], c[k], d[k]), op & 1);
+          float4* o = reinterpret_cast<float4*>(dst + k * HW);
+          if (!first) { const float4 t = *o; p = make_float4(t.x + p.x, t.y + p.y, t.z + p.z, t.w + p.w); }
+          *o = p;
+        }
+    } else {
+      float v[MK];
+#pragma unroll
+      for (int k = 0; k < MK; ++k)
+        if (k < K) v[k] = src[k * HW];
+      tta_softmax(v, K);
+#pragma unroll
+      for (int k = 0; k < MK; ++k)
+        if (k < K) dst[k * HW] = first ? v[k] : dst[k * HW] + v[k];
+    }
+  }
+}
+
+// ---- ops 4 .. 7: through an LDS tile transpose ----
+// x: [planes][H][W] -> out: [planes][W][H].  The block reads source rows y0 + r, columns x0 .. x0 + 31 and writes view rows: the
+// source pixel (y, x) is the view pixel (i, j) with i2 = x, j2 = y.
+__global__ __launch_bounds__(TTA_THREADS) void tta_view_tile_kernel(const float* __restrict__ x, int H, int W, int op, int tiles_x,
+                                                                    int tiles_y, long long ntiles, float* __restrict__ out) {
+  __shared__ float s[TTA_TILE * TTA_LD];
+  const int tx = threadIdx.x % TTA_TILE, ty = threadIdx.x / TTA_TILE;
+  const int per_plane = tiles_x * tiles_y;
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long plane = t / per_plane;
+    const int r = (int)(t - plane * per_plane), y0 = (r / tiles_x) * TTA_TILE, x0 = (r % tiles_x) * TTA_TILE;
+    const float* src = x + (size_t)plane * H * W;
+    float* dst = out + (size_t)plane * H * W;
+    __syncthreads();                                                     // the previous tile of this block has been read out
+#pragma unroll
+    for (int e = 0; e < TTA_PER; ++e) {
+      const int ly = ty + e * TTA_ROWS;
+      if (y0 + ly < H && x0 + tx < W) s[ly * TTA_LD + tx] = src[(size_t)(y0 + ly) * W + x0 + tx];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < TTA_PER; ++e) {
+      const int lx = ty + e * TTA_ROWS;                                  // source column = view row (before the flip)
+      const int sx = x0 + lx, sy = y0 + tx;
+      if (sx < W && sy < H) dst[(size_t)tta_flip(sx, W, op & 2) * H + tta_flip(sy, H, op & 1)] = s[tx * TTA_LD + lx];
+    }
+  }
+}
+
+// logits: [N][K][W][H] (the view), acc: [N][K][H][W].  The block reads view rows i0 + r, columns j0 .. j0 + 31; the view pixel
+// (i, j) lands on acc row y = j2, column x = i2.
+template <int MK>
+__global__ __launch_bounds__(TTA_THREADS) void tta_acc_tile_kernel(const float* __restrict__ logits, int K, int H, int W, int op,
+                                                                   int first, int tiles_x, int tiles_y, long long ntiles,
+                                                                   float* __restrict__ acc) {
+  __shared__ float s[TTA_CHUNK * TTA_TILE * TTA_LD];
+  const int Hv = W, Wv = H;
+  const int tx = threadIdx.x % TTA_TILE, ty = threadIdx.x / TTA_TILE;
+  const int per_image = tiles_x * tiles_y;
+  const size_t HW = (size_t)H * W;
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int n = (int)(t / per_image), r = (int)(t - (long long)n * per_image);
+    const int i0 = (r / tiles_x) * TTA_TILE, j0 = (r % tiles_x) * TTA_TILE;
+    const float* src = logits + (size_t)n * K * HW;
+    float* dst = acc + (size_t)n * K * HW;
+    float v[TTA_PER][MK];
+#pragma unroll
+    for (int e = 0; e < TTA_PER; ++e) {
+      const int i = i0 + ty + e * TTA_ROWS, j = j0 + tx;
+      const bool in = i < Hv && j < Wv;
+#pragma unroll
+      for (int k = 0; k < MK; ++k)
+        if (k < K) v[e][k] = in ? src[k * HW + (size_t)i * Wv + j] : 0.f;
+      tta_softmax(v[e], K);
+    }
+#pragma unroll
+    for (int c0 = 0; c0 < MK; c0 += TTA_CHUNK) {
+      if (c0 < K) {                                                      // uniform over the block
+        __syncthreads();                                                 // the previous chunk / tile has been read out
+#pragma unroll
+        for (int c = 0; c < TTA_CHUNK; ++c)
+          if (c0 + c < MK && c0 + c < K) {
+#pragma unroll
+            for (int e = 0; e < TTA_PER; ++e) s[(c * TTA_TILE + ty + e * TTA_ROWS) * TTA_LD + tx] = v[e][c0 + c];
+          }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < TTA_PER; ++e) {
+          const int lj = ty + e * TTA_ROWS;                              // view column = acc row (before the flip)
+          const int i = i0 + tx, j = j0 + lj;
+          if (i < Hv && j < Wv) {
+            float* o = dst + (size_t)tta_flip(j, Wv, op & 1) * W + tta_flip(i, Hv, op & 2);
+#pragma unroll
+            for (int c = 0; c < TTA_CHUNK; ++c)
+              if (c0 + c < MK && c0 + c < K) {
+                const float p = s[(c * TTA_TILE + tx) * TTA_LD + lj];
+                o[(c0 + c) * HW] = first ? p : o[(c0 + c) * HW] + p;
+              }
+          }
+        }
+      }
+    }
+  }
+}
+
+// acc: [N][K][HW] scaled in place; cls (nullable): [N][HW].  total = N * (VEC ? HW / 4 : HW)
+template <bool VEC>
+__global__ __launch_bounds__(TTA_THREADS) void tta_finalize_kernel(float* __restrict__ acc, int K, int HW, float scale, long long total,
+                                                                   long long* __restrict__ cls) {
+  const int per = VEC ? HW / 4 : HW;
+  for (long long g = (long long)blockIdx.x * TTA_THREADS + threadIdx.x; g < total; g += (long long)gridDim.x * TTA_THREADS) {
+    const int n = (int)(g / per), q = (int)(g - (long long)n * per);
+    float* b = acc + (size_t)n * K * HW + (VEC ? 4 * q : q);
+    if (VEC) {
+      float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+      int kx = 0, ky = 0, kz = 0, kw = 0;
+      for (int k = 0; k < K; ++k) {
+        float4 v = *reinterpret_cast<float4*>(b + (size_t)k * HW);
+        v = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
+        *reinterpret_cast<float4*>(b + (size_t)k * HW) = v;
+        if (k == 0) m = v;
+        if (v.x > m.x) { m.x = v.x; kx = k; }
+        if (v.y > m.y) { m.y = v.y; ky = k; }
+        if (v.z > m.z) { m.z = v.z; kz = k; }
+        if (v.w > m.w) { m.w = v.w; kw = k; }
+      }
+      if (cls) {
+        longlong2* o = reinterpret_cast<longlong2*>(cls + (size_t)n * HW + 4 * q);      // HW % 4 == 0: 32-byte aligned with cls
+        o[0] = make_longlong2(kx, ky);
+        o[1] = make_longlong2(kz, kw);
+      }
+    } else {
+      float m = 0.f;
+      int best = 0;
+      for (int k = 0; k < K; ++k) {
+        const float v = b[(size_t)k * HW] * scale;
+        b[(size_t)k * HW] = v;
+        if (k == 0) m = v;
+        if (v > m) { m = v; best = k; }
+      }
+      if (cls) cls[(size_t)n * HW + q] = best;
+    }
+  }
+}
+
+// ---- host side ----
+static inline int tta_blocks(long long items) {
+  const long long b = (items + TTA_THREADS - 1) / TTA_THREADS;
+  return (int)(b < TTA_MAX_BLOCKS ? b : TTA_MAX_BLOCKS);
+}
+static inline bool tta_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int pp_tta_view(const float* x, int planes, int H, int W, int op, float* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PP_CHECK_ARG(x && out, "tta_view: null pointer");
+  PP_CHECK_ARG(planes >= 1 && H >= 1 && W >= 1, "tta_view: bad shape planes=%d H=%d W=%d", planes, H, W);
+  PP_CHECK_ARG(op >= 0 && op <= 7, "tta_view: op=%d (0..7: bit 0 flips W, bit 1 flips H, bit 2 transposes)", op);
+  PP_CHECK_ARG((long long)planes * H * W < 0x80000000LL, "tta_view: planes*H*W must be below 2^31");
+  const long long total = (long long)planes * H * W;
+  PP_CHECK_ARG(out + total <= x || x + total <= out, "tta_view: out must not overlap x");
+  pp_prof_begin(PP_K_MISC, 0.0, 8.0 * (double)total, s);
+  if (op & 4) {
+    const int tiles_x = pp_cdiv(W, TTA_TILE), tiles_y = pp_cdiv(H, TTA_TILE);
+    const long long ntiles = (long long)planes * tiles_x * tiles_y;
+    hipLaunchKernelGGL(tta_view_tile_kernel, dim3((unsigned)(ntiles < TTA_MAX_BLOCKS ? ntiles : TTA_MAX_BLOCKS)), dim3(TTA_THREADS), 0, s, x, H,
+                       W, op, tiles_x, tiles_y, ntiles, out);
+  } else if (W % 4 == 0 && tta_al16(x) && tta_al16(out)) {
+    hipLaunchKernelGGL(tta_view_row_kernel<true>, dim3(tta_blocks(total / 4)), dim3(TTA_THREADS), 0, s, x, H, W, op, total / 4, out);
+  } else {
+    hipLaunchKernelGGL(tta_view_row_kernel<false>, dim3(tta_blocks(total)), dim3(TTA_THREADS), 0, s, x, H, W, op, total, out);
+  }
+  pp_prof_end(s);
+  return pp_launch_status("tta_view");
+}
+
+extern "C" int pp_tta_accumulate(const float* logits, int N, int K, int H, int W, int op, int first, float* acc, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PP_CHECK_ARG(logits && acc, "tta_accumulate: null pointer");
+  PP_CHECK_ARG(N >= 1 && H >= 1 && W >= 1, "tta_accumulate: bad shape N=%d H=%d W=%d", N, H, W);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK, "tta_accumulate: K=%d (1..%d)", K, PP_MAXK);
+  PP_CHECK_ARG(op >= 0 && op <= 7, "tta_accumulate: op=%d (0..7: bit 0 flips W, bit 1 flips H, bit 2 transposes)", op);
+  PP_CHECK_ARG((long long)N * K * H * W < 0x80000000LL, "tta_accumulate: N*K*H*W must be below 2^31");
+  const long long px = (long long)N * H * W;
+  pp_prof_begin(PP_K_MISC, 0.0, (first ? 8.0 : 12.0) * (double)px * K, s);
+  if (op & 4) {
+    const int tiles_x = pp_cdiv(H, TTA_TILE), tiles_y = pp_cdiv(W, TTA_TILE);      // of the view: W rows of H pixels
+    const long long ntiles = (long long)N * tiles_x * tiles_y;
+    const dim3 grid((unsigned)(ntiles < TTA_MAX_BLOCKS ? ntiles : TTA_MAX_BLOCKS));
+    pp_by_class_bound(K, [&](auto mk) {
+      hipLaunchKernelGGL(tta_acc_tile_kernel<decltype(mk)::value>, grid, dim3(TTA_THREADS), 0, s, logits, K, H, W, op, first, tiles_x, tiles_y,
+                         ntiles, acc);
+    });
+  } else if (W % 4 == 0 && tta_al16(logits) && tta_al16(acc)) {
+    pp_by_class_bound(K, [&](auto mk) {
+      hipLaunchKernelGGL((tta_acc_row_kernel<decltype(mk)::value, true>), dim3(tta_blocks(px / 4)), dim3(TTA_THREADS), 0, s, logits, K, H, W, op,
+                         first, px / 4, acc);
+    });
+  } else {
+    pp_by_class_bound(K, [&](auto mk) {
+      hipLaunchKernelGGL((tta_acc_row_kernel<decltype(mk)::value, false>), dim3(tta_blocks(px)), dim3(TTA_THREADS), 0, s, logits, K, H, W, op,
+                         first, px, acc);
+    });
+  }
+  pp_prof_end(s);
+  return pp_launch_status("tta_accumulate");
+}
+
+extern "C" int pp_tta_finalize(float* acc, int N, int K, int H, int W, int views, int64_t* cls, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PP_CHECK_ARG(acc, "tta_finalize: null pointer");
+  PP_CHECK_ARG(N >= 1 && H >= 1 && W >= 1, "tta_finalize: bad shape N=%d H=%d W=%d", N, H, W);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK, "tta_finalize: K=%d (1..%d)", K, PP_MAXK);
+  PP_CHECK_ARG(views == 1 || views == 2 || views == 4 || views == 8, "tta_finalize: views=%d (1, 2, 4 or 8)", views);
+  PP_CHECK_ARG((long long)N * K * H * W < 0x80000000LL, "tta_finalize: N*K*H*W must be below 2^31");
+  const long long px = (long long)N * H * W;
+  const int HW = H * W;
+  const float scale = 1.f / (float)views;
+  pp_prof_begin(PP_K_MISC, 0.0, (8.0 * K + (cls ? 8.0 : 0.0)) * (double)px, s);
+  if (HW % 4 == 0 && tta_al16(acc) && (!cls || tta_al16(cls)))
+    hipLaunchKernelGGL(tta_finalize_kernel<true>, dim3(tta_blocks(px / 4)), dim3(TTA_THREADS), 0, s, acc, K, HW, scale, px / 4, (long long*)cls);
+  else
+    hipLaunchKernelGGL(tta_finalize_kernel<false>, dim3(tta_blocks(px)), dim3(TTA_THREADS), 0, s, acc, K, HW, scale, px, (long long*)cls);
+  pp_prof_end(s);
+  return pp_launch_status("tta_finalize");
 }

@@ -66,6 +66,10 @@ parser.add_argument('--keep_largest_cc', action='store_true', default=False,
                          'eval_data.npz gains ncomp and removed')
 parser.add_argument('--cc_connectivity', type=int, default=1, choices=[1, 2],
                     help='neighbourhood of --keep_largest_cc: 1 = 4-neighbourhood (what HD95 uses), 2 = 8-neighbourhood')
+parser.add_argument('--tta', type=str, default='none', choices=['none', 'flips', 'd4'],
+                    help='test-time augmentation: score the mean soft-max over the views of each slice, mapped back on the device '
+                         '(flips = identity + the three mirror images, d4 = all eight flips and quarter turns; transposed views of a '
+                         'non-square slice run at the swapped size); eval_data.npz gains tta_changed')
 
 
 def load_backbone(model, state_dict):
@@ -84,24 +88,40 @@ def load_backbone(model, state_dict):
     return model
 
 
-def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False, cc_connectivity=1):
+def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False, cc_connectivity=1, tta='none', extra=None):
     """-> (dicearr, hd95arr), both (slices, classes) float32 with NaN where the reference skips a class.  With keep_largest_cc the
     arg-max is filtered on the device first (utils.postprocess.keep_largest_components) and both metrics score the filtered map;
     then -> (dicearr, hd95arr, ncomp, removed): ncomp (slices, classes) int32 = components per class before filtering, removed
-    (slices,) int64 = pixels set to background."""
+    (slices,) int64 = pixels set to background.  With tta 'flips' / 'd4' the probabilities and the class map are the mean over
+    the views (utils.tta.tta_predict) wherever the logits and their arg-max are used otherwise; the returned values keep their
+    number and meaning, and a dict passed as `extra` receives tta_changed: (slices,) int64 = pixels whose class differs from
+    the identity view's arg-max."""
     from .data import expand_compact
     from .utils.metrics import batch_dice_counts, batch_hd95
     from .utils.postprocess import keep_largest_components
-    dice_rows, hd_rows, ncomp_rows, removed_rows = [], [], [], []
+    from .utils.tta import tta_ops, tta_predict
+    use_tta = len(tta_ops(tta)) > 1
+    dice_rows, hd_rows, ncomp_rows, removed_rows, changed_rows = [], [], [], [], []
     model.eval()
     for groups in loader:
         for batch in (groups if isinstance(groups, list) else [groups]):   # same-shape groups (data.collate_by_shape)
             batch = expand_compact(batch, num_classes, device)          # uint8 class maps -> one-hot planes, on the device
             image, label = batch['image'], batch['label']
             with torch.no_grad():
-                logits = model(image)['segmentation/logits']
+                if use_tta:
+                    single = []                                            # the arg-max of the identity view, which runs first
+
+                    def forward(x):
+                        z = model(x)['segmentation/logits']
+                        if not single:
+                            single.append(z.argmax(1))
+                        return z
+                    logits, tta_cls = tta_predict(forward, image, tta)      # mean probabilities and their first-maximum arg-max
+                    changed_rows.extend((tta_cls != single[0]).flatten(1).sum(1).tolist())
+                else:
+                    logits = model(image)['segmentation/logits']
             if keep_largest_cc:
-                raw = logits.argmax(1)
+                raw = tta_cls if use_tta else logits.argmax(1)
                 pred, stats = keep_largest_components(raw, num_classes, cc_connectivity, return_stats=True)
                 ncomp_rows.extend(stats[..., 0].tolist())
                 removed_rows.extend((pred != raw).flatten(1).sum(1).tolist())
@@ -115,7 +135,10 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
                 dice = 2.0 * inter / np.maximum(ps + ts, 1e-8)             # inference.py:211-213 (no smoothing term here)
             dice[(ps == 0) & (ts == 0)] = np.nan                           # :208-209
             dice_rows.extend(dice.tolist())
-            hd_rows.extend(batch_hd95(pred if keep_largest_cc else logits.argmax(1), label.argmax(1), num_classes, spacing).tolist())
+            hard = pred if keep_largest_cc else (tta_cls if use_tta else logits.argmax(1))
+            hd_rows.extend(batch_hd95(hard, label.argmax(1), num_classes, spacing).tolist())
+    if use_tta and extra is not None:
+        extra['tta_changed'] = np.array(changed_rows, np.int64)
     if keep_largest_cc:
         return (np.array(dice_rows, np.float32), np.array(hd_rows, np.float32),
                 np.array(ncomp_rows, np.int32).reshape(-1, num_classes), np.array(removed_rows, np.int64))
@@ -145,14 +168,21 @@ def main_interface(args):
                                          multiprocessing_context=loader_context(args.num_workers))
     logging.info('Length {}'.format(len(loader)))
     load_backbone(model, torch.load(args.checkpoint_file, map_location=device))
+    tta = getattr(args, 'tta', 'none')
+    extra = {}                                             # tta_changed with --tta flips / d4; stays empty otherwise
     if args.keep_largest_cc:
-        dicearr, hd95arr, ncomp, removed = evaluate(model, loader, num_classes, spacing, device, True, args.cc_connectivity)
-        np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, ncomp=ncomp, removed=removed)
+        dicearr, hd95arr, ncomp, removed = evaluate(model, loader, num_classes, spacing, device, True, args.cc_connectivity, tta, extra)
+        np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, ncomp=ncomp, removed=removed, **extra)
         logging.info('Largest-component filter (connectivity {}): {} pixels set to background, {} of {} slices changed'.format(
             args.cc_connectivity, int(removed.sum()), int((removed > 0).sum()), len(removed)))
     else:
-        dicearr, hd95arr = evaluate(model, loader, num_classes, spacing, device)
-        np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr)
+        dicearr, hd95arr = evaluate(model, loader, num_classes, spacing, device, tta=tta, extra=extra)
+        np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, **extra)
+    if tta != 'none':
+        from .utils.tta import tta_ops
+        changed = extra['tta_changed']
+        logging.info('Test-time augmentation ({}, {} views): {} pixels differ from the identity view, {} of {} slices changed'.format(
+            tta, len(tta_ops(tta)), int(changed.sum()), int((changed > 0).sum()), len(changed)))
     meter_dice = [AvgMeter() for _ in range(num_classes)]
     meter_hd95 = [AvgMeter() for _ in range(num_classes)]
     for drow, hrow in zip(dicearr, hd95arr):

@@ -1,2 +1,3 @@
 from .utils import AvgMeter, cosine_lr_decay, gaussian_ramp_up, linear_lr_decay, poly_lr_decay  # noqa: F401
 from .postprocess import keep_largest_components, label_components  # noqa: F401
+from .tta import TTA_MODES, tta_ops, tta_predict, tta_view  # noqa: F401

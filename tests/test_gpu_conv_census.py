@@ -26,8 +26,6 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from oracle import pacing_oracle as O  # noqa: E402
-
 TOL = 1e-4            # outputs, data and weight gradients (max-norm relative to the reference)
 TOL_SUMS = 1e-5       # BatchNorm partial sums (test_conv_bn_fused_epilogues)
 ATOL_SUM = 4e-6       # check_act (tests/test_gpu_h16.py): fp32 summation-order noise, relative to the largest output
@@ -48,118 +46,12 @@ def _is_conv_launch(name):
     return family and bool(args) and args[-1] is ctypes.c_void_p          # a launch takes a stream; shape queries do not
 
 
-def _shape_of(name, args):
-    """The launch with pointers replaced by 'p' / None (null), buffer sizes by 'sz', a lazy input by ('lazy', ld, groups)."""
-    from pacingpseudo_amd._lib import _PROTOS, lazy_p
-    out = []
-    for t, a in zip(_PROTOS[name][1], args):
-        if t is lazy_p:
-            out.append(None if a is None else ('lazy', a._obj.ld, a._obj.groups))
-        elif t is ctypes.c_void_p or t is ctypes.POINTER(ctypes.c_int):
-            out.append(None if a is None else 'p')
-        elif t is ctypes.c_size_t:
-            out.append('sz')
-        else:
-            out.append(float(a) if isinstance(a, float) else int(a))
-    return tuple(out)
-
-
-class _Recorder:
-    """Stands in for a plan's entry-point table: every attribute lookup reaches __getattr__ (nothing is cached here -- _Lib and
-    _H16Lib cache their wrappers on themselves), convolution launches are recorded and forwarded unchanged."""
-
-    def __init__(self, inner, storage, sink):
-        self._inner, self._storage, self._sink = inner, storage, sink
-
-    def __getattr__(self, name):
-        fn = getattr(self._inner, name)
-        if not _is_conv_launch(name):
-            return fn
-
-        def call(*a):
-            self._sink((self._storage, name, _shape_of(name, a)))
-            return fn(*a)
-        return call
-
-
-def _configs():
-    """label -> (storage, size, classes, output stride, variant)"""
-    c = {'256/os8': ('fp32', 256, 5, 8, ''), '224/os8/4cls': ('fp32', 224, 4, 8, ''), '224/os8/2cls': ('fp32', 224, 2, 8, '')}
-    for s in (256, 224):
-        for os_ in (16, 32):
-            c[f'{s}/os{os_}'] = ('fp32', s, 5 if s == 256 else 4, os_, '')
-    c['256/strided'] = ('fp32', 256, 5, 8, 'strided')
-    c['256/groupnorm'] = ('fp32', 256, 5, 8, 'gn')
-    for kind in ('fp16', 'bf16'):
-        c[f'256/{kind}'] = (kind, 256, 5, 8, '')
-        c[f'224/{kind}'] = (kind, 224, 4, 8, '')
-    return c
-
-
-def _run_config(label, name, storage, size, classes, os_, variant):
-    from tests.test_gpu_step import build_model
-    # output stride 32 pools encoder stage 6 below stage 5: no auxiliary path there (as the golden case 'stride32')
-    over = dict(do_aux_path=False, do_memory=False) if os_ == 32 else {}
-    args = O.full_flags(num_classes=classes, ignored_index=classes, output_stride=os_, **over)
-    args.storage = storage
-    if variant == 'strided':
-        args.is_stride_conv = args.is_trans_conv = True
-    torch.manual_seed(1)
-    if variant == 'gn':
-        from tests.test_gpu_groupnorm import build_gn_model
-        model = build_gn_model(args)
-    else:
-        model = build_model(args)
-    batch = {k: v.cuda() for k, v in O.synthetic_batch(2, size, size, num_classes=classes, seed=7, keep=0.03).items() if k != 'label'}
-    for bn_eval in (False, True):
-        label[0] = f'{name}/{"eval" if bn_eval else "train"}-BN'
-        model.train()
-        if bn_eval:
-            model.eval()
-        model.zero_grad(set_to_none=True)
-        out = model(batch, mode='train', step=0)
-        loss = sum(out[k] * wt for k, wt in O.loss_weights(args, 0).items())
-        loss.backward()
-        torch.cuda.synchronize()
-    del model, out, loss
-
-
-def _run_inference():
-    from pacingpseudo_amd.models import UNet
-    args = O.full_flags(num_classes=4)
-    torch.manual_seed(1)
-    net = UNet(input_ch=1, init_ch=args.init_ch, max_ch=args.max_ch, num_classes=4, output_stride=8).cuda().eval()
-    with torch.no_grad():
-        net(torch.randn(1, 1, 256, 272, device='cuda'))
-    torch.cuda.synchronize()
-    del net
-
-
 @pytest.fixture(scope='module')
 def census():
-    """{(storage, entry, launch shape): set of configuration labels}, over every configuration (cached for the module)."""
-    from pacingpseudo_amd import engine as E
-    rec = defaultdict(set)
-    real = E.lib_for
-    label = ['']
-
-    def patched(storage):
-        s = {4: 'fp32', 2: 'fp16'}.get(storage, storage)
-        return _Recorder(real(storage), s, lambda key: rec[key].add(label[0]))
-    E.lib_for = patched
-    try:
-        for name, cfg in _configs().items():
-            try:
-                _run_config(label, name, *cfg)
-            except Exception as e:
-                raise RuntimeError(f'census configuration {label[0]} failed: {e}') from e
-            torch.cuda.empty_cache()
-        label[0] = '256x272/inference'
-        _run_inference()
-        torch.cuda.empty_cache()
-    finally:
-        E.lib_for = real
-    return dict(rec)
+    """{(storage, entry, launch shape): set of configuration labels}: the convolution family of the shared recording
+    (tests/_launch_census.py runs the configurations once per process)."""
+    from tests._launch_census import record
+    return {key: cfgs for key, cfgs in record().items() if _is_conv_launch(key[1])}
 
 
 # ------------------------------------------------------------------------------------------------------------------ operands
@@ -748,15 +640,19 @@ def _act_ratio(h, f, storage):
     return float(((h64 - f64).abs() / bound).max())
 
 
-def replay(key):
-    """[(label, error / tolerance)] of one recorded launch; raises KeyError naming an entry without an adapter."""
+def replay(key, adapters=None, table=None):
+    """[(label, error / tolerance)] of one recorded launch; raises KeyError naming an entry without an adapter.  adapters: another
+    family's table of adapters (tests/test_gpu_stream_census.py); table: a stand-in for the fp32 entry-point table."""
     storage, name, a = key
-    if name not in ADAPTERS:
+    adapters = ADAPTERS if adapters is None else adapters
+    if name not in adapters:
         raise KeyError(name)
     from pacingpseudo_amd._lib import lib, lib_for
+    if table is not None:
+        lib = table
     out = []
     r32 = _Run(lib, torch.float32, True)
-    ADAPTERS[name]((storage, name, a), r32)
+    adapters[name]((storage, name, a), r32)
     torch.cuda.synchronize()
     for label, got, ref, tol, _ in r32.res:
         tag = 'fp32 twin ' if storage != 'fp32' else ''
@@ -766,7 +662,7 @@ def replay(key):
             out.append((tag + label, _rel(got, ref) / tol))
     if storage != 'fp32':
         r16 = _Run(lib_for(storage), MANT[storage][2], False)
-        ADAPTERS[name]((storage, name, a), r16)
+        adapters[name]((storage, name, a), r16)
         torch.cuda.synchronize()
         twin = {lab: got for lab, got, _, _, _ in r32.res}
         twin_ref = {lab: ref for lab, _, ref, _, _ in r32.res if ref is not None}

@@ -582,6 +582,24 @@ int pp_tta_view(const float* x, int planes, int H, int W, int op, float* out, vo
 int pp_tta_accumulate(const float* logits, int N, int K, int H, int W, int op, int first, float* acc, void* stream);
 int pp_tta_finalize(float* acc, int N, int K, int H, int W, int views, int64_t* cls, void* stream);
 
+/* Surface metrics from the distance sets of pp_hd95_surface_distances, reduced on the device (the reference's _compute_hd,
+ * inference.py:239-258, and medpy's assd / a surface Dice from the same sets).  dist / counts exactly as
+ * pp_hd95_surface_distances leaves them: dist [items][2][cap] floats, counts [items][4] ints.  Only
+ * dist[i][0][:min(counts[i][0], cap)] (the set A, na entries) and dist[i][1][:min(counts[i][1], cap)] (B, nb entries) are read;
+ * they must hold non-negative finite floats.  With n = na + nb and S the sorted multiset union of A and B,
+ *   out[i] = {max(S), sum(A), sum(B), |{a <= tolerance}|, |{b <= tolerance}|, S[j], S[min(j + 1, n - 1)], n},
+ *   j = floor(v), v = (double)(n - 1) * (percentile / 100.0)       (numpy.percentile's virtual index, method 'linear').
+ * The maximum and the two order statistics are bit-exact elements of S (an exact radix select on the bit patterns), `<=` is taken
+ * in fp32 against the fp32 tolerance, counts and n are exact as doubles, the sums are added in double in a fixed order (strided
+ * per-thread partials, then a fixed tree): the same bits in every run.  An item with n == 0 writes eight zeros and reads nothing
+ * of dist.  The caller forms  HD = out[0],  ASSD = (out[1] / na + out[2] / nb) / 2,  surface Dice = (out[3] + out[4]) / n,
+ * percentile distance = out[5] + (out[6] - out[5]) * (v - j).
+ * One launch of one block per item, fixed by `items`: no workspace, no host synchronisation, no global atomics (capturable).
+ * Refused with a status and pp_last_error() before any launch: null pointers, items < 1, cap < 1, percentile outside (0, 100] or
+ * not finite, tolerance negative or not finite, items * 2 * cap >= 2^31. */
+int pp_surface_reduce(const float* dist, const int* counts, int items, int cap, double percentile, float tolerance,
+                      double* out, void* stream);
+
 /* ---- optimiser (torch.optim.Adam(lr, weight_decay) at train_chaos.py:219) ------------------------------- */
 int pp_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                  float eps, float weight_decay, int step, void* stream);

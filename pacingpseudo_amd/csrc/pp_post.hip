@@ -1,7 +1,8 @@
 // Post-processing of hard class maps on the device: connected-component labelling and the keep-largest-component filter of an
 // evaluation pipeline (include/pacingpseudo_hip.h; DESIGN.md section 7, "Largest-component filter").  The reference scores its raw
 // arg-max (inference.py:159-190); class maps are integers, so there is one build of this file in every storage mode.  The second
-// half of the file holds the test-time-augmentation kernels (views, soft-max accumulation, finalize) on the fp32 logits.
+// half of the file holds the test-time-augmentation kernels (views, soft-max accumulation, finalize) on the fp32 logits, the end
+// the reduction of the surface-distance sets to the numbers HD, ASSD, surface Dice and a percentile distance are made of.
 //
 // Two pixels of one image are connected when they are neighbours (4- or 8-neighbourhood) and hold the same value.  The label of a
 // pixel is the smallest row-major index of its component, so the result is unique.  Structure: a union-find forest over pixel
@@ -632,4 +633,163 @@ extern "C" int pp_tta_finalize(float* acc, int N, int K, int H, int W, int views
     hipLaunchKernelGGL(tta_finalize_kernel<false>, dim3(tta_blocks(px)), dim3(TTA_THREADS), 0, s, acc, K, HW, scale, px, (long long*)cls);
   pp_prof_end(s);
   return pp_launch_status("tta_finalize");
+}
+
+// ================================================================================================================================
+// Surface-distance reduction (include/pacingpseudo_hip.h; DESIGN.md section 7, "Surface metrics").  pp_hd95_surface_distances leaves
+// two directed distance sets A and B per (slice, class) item; HD, ASSD, the surface Dice and a percentile distance are functions of
+// eight numbers per item: max(S), sum(A), sum(B), |{a <= tol}|, |{b <= tol}|, S[j], S[min(j + 1, n - 1)], n with S = sort(A ++ B).
+//   surface_reduce_kernel   one block of 256 threads per item, no workspace, nothing written but the 64 bytes of out[item]
+// Distances are non-negative finite floats, so their bit patterns order as unsigned integers: S[j] comes from a most-significant-
+// digit radix select -- four passes over the item's two segments, each a 256-bin histogram of one byte of the elements that still
+// match the prefix found so far (integer LDS atomics), a block-wide scan of the bins, and the bin that holds rank j becomes the next
+// byte of the prefix.  `below` = the elements strictly smaller than every value of the prefix; after the last pass the prefix is the
+// bit pattern of S[j] and its bin holds the copies of that value, so S[j + 1] = S[j] when below + copies >= j + 2 and otherwise the
+// minimum of the elements above S[j], which one more pass finds.  The first pass also takes the maximum (as bits), the within-
+// tolerance counts (fp32 `<=`) and the two sums: per-thread strided partials in double, then a fixed halving tree through LDS.
+// Integer atomics only and a fixed summation order: the same bits in every run.  The launch depends on `items` alone.
+#define SR_THREADS 256
+#define SR_WAVES (SR_THREADS / 64)
+
+struct SrItem {
+  const unsigned* a;      // the bit patterns of the first set
+  const unsigned* b;
+  int na, n;
+  __device__ __forceinline__ unsigned at(int e) const { return e < na ? a[e] : b[e - na]; }
+};
+
+// Rank `rank` (counted among the elements the histogram holds) falls into the bin t with excl(t) <= rank < incl(t).  That thread
+// publishes {t, excl, hist[t]}; everybody returns them.  Two barriers inside, and one in front so that the histogram is complete.
+__device__ __forceinline__ void sr_select_bin(const unsigned* s_hist, unsigned* s_wave, unsigned* s_pick, unsigned rank, unsigned& bin,
+                                              unsigned& excl_out, unsigned& copies) {
+  __syncthreads();
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const unsigned h = s_hist[t];
+  unsigned incl = h;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned up = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += up;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  unsigned base = 0;
+#pragma unroll
+  for (int w = 0; w < SR_WAVES; ++w)
+    if (w < wave) base += s_wave[w];
+  incl += base;
+  const unsigned excl = incl - h;
+  if (excl <= rank && rank < incl) { s_pick[0] = (unsigned)t; s_pick[1] = excl; s_pick[2] = h; }      // h > 0: exactly one thread
+  __syncthreads();
+  bin = s_pick[0];
+  excl_out = s_pick[1];
+  copies = s_pick[2];
+}
+
+__global__ __launch_bounds__(SR_THREADS) void surface_reduce_kernel(const float* __restrict__ dist, const int* __restrict__ counts, int cap,
+                                                                    double quantile, float tolerance, double* __restrict__ out) {
+  __shared__ unsigned s_hist[SR_THREADS];
+  __shared__ double s_sum[2][SR_THREADS];
+  __shared__ unsigned s_wave[SR_WAVES];
+  __shared__ unsigned s_pick[3];
+  __shared__ unsigned s_misc[4];                                   // max bits, count a, count b, min above S[j]
+  const int item = blockIdx.x, t = threadIdx.x;
+  double* o = out + (size_t)item * 8;
+  SrItem it;
+  it.na = min(max(counts[(size_t)item * 4], 0), cap);
+  const int nb = min(max(counts[(size_t)item * 4 + 1], 0), cap);
+  it.n = it.na + nb;
+  it.a = reinterpret_cast<const unsigned*>(dist) + (size_t)item * 2 * cap;
+  it.b = it.a + cap;
+  const int n = it.n;
+  if (n == 0) {                                                    // uniform over the block
+    if (t < 8) o[t] = 0.0;
+    return;
+  }
+  const double v = (double)(n - 1) * quantile;                     // numpy.percentile's virtual index; quantile <= 1, so v <= n - 1
+  const int j = min(max((int)floor(v), 0), n - 1);
+
+  // ---- pass 0: the top byte, and everything that needs every element once ----
+  s_hist[t] = 0;
+  if (t < 4) s_misc[t] = t == 3 ? 0xFFFFFFFFu : 0u;
+  __syncthreads();
+  {
+    double sa = 0.0, sb = 0.0;
+    unsigned mx = 0, ca = 0, cb = 0;
+    for (int e = t; e < n; e += SR_THREADS) {
+      const unsigned u = it.at(e);
+      const float f = __uint_as_float(u);
+      atomicAdd(&s_hist[u >> 24], 1u);
+      mx = max(mx, u);
+      if (e < it.na) { sa += (double)f; ca += f <= tolerance; }
+      else { sb += (double)f; cb += f <= tolerance; }
+    }
+    atomicMax(&s_misc[0], mx);
+    if (ca) atomicAdd(&s_misc[1], ca);
+    if (cb) atomicAdd(&s_misc[2], cb);
+    s_sum[0][t] = sa;
+    s_sum[1][t] = sb;
+  }
+  unsigned prefix = 0, below = 0, bin, excl, copies;
+  sr_select_bin(s_hist, s_wave, s_pick, (unsigned)j, bin, excl, copies);          // its first barrier also publishes s_sum and s_misc
+  prefix = bin;
+  below = excl;
+  for (int half = SR_THREADS / 2; half > 0; half >>= 1) {          // the fixed tree: element t += element t + half
+    if (t < half) {
+      s_sum[0][t] += s_sum[0][t + half];
+      s_sum[1][t] += s_sum[1][t + half];
+    }
+    __syncthreads();
+  }
+
+  // ---- passes 1 .. 3: the next byte of the elements under the prefix ----
+  for (int shift = 16; shift >= 0; shift -= 8) {
+    s_hist[t] = 0;                                                 // every thread has read its bin (the barriers of the select)
+    __syncthreads();
+    for (int e = t; e < n; e += SR_THREADS) {
+      const unsigned u = it.at(e);
+      if ((u >> (shift + 8)) == prefix) atomicAdd(&s_hist[(u >> shift) & 255u], 1u);
+    }
+    sr_select_bin(s_hist, s_wave, s_pick, (unsigned)j - below, bin, excl, copies);
+    prefix = (prefix << 8) | bin;
+    below += excl;
+  }
+
+  // ---- the upper neighbour: S[j] again when the run of equal values reaches rank j + 1 (or j is the last rank) ----
+  unsigned upper = prefix;
+  if (j + 1 < n && below + copies < (unsigned)j + 2u) {            // uniform over the block
+    unsigned mn = 0xFFFFFFFFu;
+    for (int e = t; e < n; e += SR_THREADS) {
+      const unsigned u = it.at(e);
+      if (u > prefix) mn = min(mn, u);
+    }
+    atomicMin(&s_misc[3], mn);
+    __syncthreads();
+    upper = s_misc[3];
+  }
+  if (t == 0) {
+    o[0] = (double)__uint_as_float(s_misc[0]);
+    o[1] = s_sum[0][0];
+    o[2] = s_sum[1][0];
+    o[3] = (double)s_misc[1];
+    o[4] = (double)s_misc[2];
+    o[5] = (double)__uint_as_float(prefix);
+    o[6] = (double)__uint_as_float(upper);
+    o[7] = (double)n;
+  }
+}
+
+extern "C" int pp_surface_reduce(const float* dist, const int* counts, int items, int cap, double percentile, float tolerance, double* out,
+                                 void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PP_CHECK_ARG(dist && counts && out, "surface_reduce: null pointer");
+  PP_CHECK_ARG(items >= 1 && cap >= 1, "surface_reduce: bad shape items=%d cap=%d", items, cap);
+  PP_CHECK_ARG(percentile > 0.0 && percentile <= 100.0, "surface_reduce: percentile=%g (0 < percentile <= 100)", percentile);
+  PP_CHECK_ARG(tolerance >= 0.f && tolerance <= 3.4028234e38f, "surface_reduce: tolerance=%g (finite, >= 0)", (double)tolerance);
+  PP_CHECK_ARG((unsigned long long)items * 2ull * (unsigned long long)cap < 0x80000000ull, "surface_reduce: items*2*cap must be below 2^31");
+  // traffic: at most six passes over the live prefixes, which the host does not know: the bound for full sets
+  pp_prof_begin(PP_K_LOSS, 0.0, 6.0 * 8.0 * (double)items * cap, s);
+  hipLaunchKernelGGL(surface_reduce_kernel, dim3(items), dim3(SR_THREADS), 0, s, dist, counts, cap, percentile / 100.0, tolerance, out);
+  pp_prof_end(s);
+  return pp_launch_status("surface_reduce");
 }

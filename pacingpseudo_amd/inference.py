@@ -72,6 +72,24 @@ parser.add_argument('--tta', type=str, default='none', choices=['none', 'flips',
                          'non-square slice run at the swapped size); eval_data.npz gains tta_changed')
 
 
+def _tolerance_mm(text):
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'{text!r} is not a number')
+    if not (np.isfinite(value) and value >= 0.0):
+        raise argparse.ArgumentTypeError(f'{text!r}: a finite distance in millimetres, >= 0')
+    return value
+
+
+parser.add_argument('--surface_metrics', action='store_true', default=False,
+                    help='score the Hausdorff distance (the reference\'s _compute_hd), the average symmetric surface distance and the '
+                         'surface Dice at --nsd_tolerance beside HD95, all four reduced on the device from one pair of surface-distance '
+                         'sets per slice and class; eval_data.npz gains hdarr, assdarr and nsdarr')
+parser.add_argument('--nsd_tolerance', type=_tolerance_mm, default=2.0, metavar='MM',
+                    help='tolerance of the surface Dice of --surface_metrics in millimetres: the share of surface pixels within MM of the other surface')
+
+
 def load_backbone(model, state_dict):
     """inference.py:138-146: a full-model checkpoint is reduced to its `backbone.` entries."""
     from .models.unet import check_checkpoint_norm
@@ -88,20 +106,25 @@ def load_backbone(model, state_dict):
     return model
 
 
-def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False, cc_connectivity=1, tta='none', extra=None):
+def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False, cc_connectivity=1, tta='none', extra=None,
+             surface_metrics=False, nsd_tolerance=2.0):
     """-> (dicearr, hd95arr), both (slices, classes) float32 with NaN where the reference skips a class.  With keep_largest_cc the
     arg-max is filtered on the device first (utils.postprocess.keep_largest_components) and both metrics score the filtered map;
     then -> (dicearr, hd95arr, ncomp, removed): ncomp (slices, classes) int32 = components per class before filtering, removed
     (slices,) int64 = pixels set to background.  With tta 'flips' / 'd4' the probabilities and the class map are the mean over
     the views (utils.tta.tta_predict) wherever the logits and their arg-max are used otherwise; the returned values keep their
     number and meaning, and a dict passed as `extra` receives tta_changed: (slices,) int64 = pixels whose class differs from
-    the identity view's arg-max."""
+    the identity view's arg-max.  With surface_metrics the same hard map is scored by one utils.metrics.batch_surface_metrics call
+    per batch instead of batch_hd95: hd95arr is its percentile distance, and `extra` receives hdarr, assdarr and nsdarr (Hausdorff
+    distance, average symmetric surface distance, surface Dice at nsd_tolerance mm), each (slices, classes) float32 with NaN as in
+    hd95arr."""
     from .data import expand_compact
-    from .utils.metrics import batch_dice_counts, batch_hd95
+    from .utils.metrics import batch_dice_counts, batch_hd95, batch_surface_metrics
     from .utils.postprocess import keep_largest_components
     from .utils.tta import tta_ops, tta_predict
     use_tta = len(tta_ops(tta)) > 1
     dice_rows, hd_rows, ncomp_rows, removed_rows, changed_rows = [], [], [], [], []
+    surf_rows = {'hd': [], 'assd': [], 'nsd': []}
     model.eval()
     for groups in loader:
         for batch in (groups if isinstance(groups, list) else [groups]):   # same-shape groups (data.collate_by_shape)
@@ -136,9 +159,18 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
             dice[(ps == 0) & (ts == 0)] = np.nan                           # :208-209
             dice_rows.extend(dice.tolist())
             hard = pred if keep_largest_cc else (tta_cls if use_tta else logits.argmax(1))
-            hd_rows.extend(batch_hd95(hard, label.argmax(1), num_classes, spacing).tolist())
+            if surface_metrics:
+                sm = batch_surface_metrics(hard, label.argmax(1), num_classes, spacing, tolerance=nsd_tolerance)
+                hd_rows.extend(sm['hdp'].tolist())
+                for key, rows in surf_rows.items():
+                    rows.extend(sm[key].tolist())
+            else:
+                hd_rows.extend(batch_hd95(hard, label.argmax(1), num_classes, spacing).tolist())
     if use_tta and extra is not None:
         extra['tta_changed'] = np.array(changed_rows, np.int64)
+    if surface_metrics and extra is not None:
+        for key, rows in surf_rows.items():
+            extra[key + 'arr'] = np.array(rows, np.float32).reshape(-1, num_classes)
     if keep_largest_cc:
         return (np.array(dice_rows, np.float32), np.array(hd_rows, np.float32),
                 np.array(ncomp_rows, np.int32).reshape(-1, num_classes), np.array(removed_rows, np.int64))
@@ -169,14 +201,15 @@ def main_interface(args):
     logging.info('Length {}'.format(len(loader)))
     load_backbone(model, torch.load(args.checkpoint_file, map_location=device))
     tta = getattr(args, 'tta', 'none')
-    extra = {}                                             # tta_changed with --tta flips / d4; stays empty otherwise
+    extra = {}                                             # tta_changed with --tta flips / d4, hdarr / assdarr / nsdarr with --surface_metrics
+    surface = dict(surface_metrics=True, nsd_tolerance=args.nsd_tolerance) if getattr(args, 'surface_metrics', False) else {}
     if args.keep_largest_cc:
-        dicearr, hd95arr, ncomp, removed = evaluate(model, loader, num_classes, spacing, device, True, args.cc_connectivity, tta, extra)
+        dicearr, hd95arr, ncomp, removed = evaluate(model, loader, num_classes, spacing, device, True, args.cc_connectivity, tta, extra, **surface)
         np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, ncomp=ncomp, removed=removed, **extra)
         logging.info('Largest-component filter (connectivity {}): {} pixels set to background, {} of {} slices changed'.format(
             args.cc_connectivity, int(removed.sum()), int((removed > 0).sum()), len(removed)))
     else:
-        dicearr, hd95arr = evaluate(model, loader, num_classes, spacing, device, tta=tta, extra=extra)
+        dicearr, hd95arr = evaluate(model, loader, num_classes, spacing, device, tta=tta, extra=extra, **surface)
         np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, **extra)
     if tta != 'none':
         from .utils.tta import tta_ops
@@ -196,6 +229,17 @@ def main_interface(args):
     foldavgdice = np.mean([meter_dice[_].avg for _ in range(1, num_classes)])
     foldavghd95 = np.mean([meter_hd95[_].avg for _ in range(1, num_classes)])
     logging.info('Fold {}, overall Dice: {:.4f}, overall HD95: {:.2f}'.format(args.fold, foldavgdice, foldavghd95))
+    if surface:
+        means = []
+        for key in ('hdarr', 'assdarr', 'nsdarr'):
+            meters = [AvgMeter() for _ in range(num_classes)]
+            for row in extra[key]:
+                for cls in range(num_classes):
+                    if not np.isnan(row[cls]):
+                        meters[cls].update(float(row[cls]))
+            means.append(np.mean([meters[_].avg for _ in range(1, num_classes)]))
+        logging.info('Fold {}, overall HD: {:.2f}, overall ASSD: {:.2f}, overall NSD at {:g} mm: {:.4f}'.format(
+            args.fold, means[0], means[1], args.nsd_tolerance, means[2]))
     logging.info('Shape of the Dice array: {}'.format(dicearr.shape))
     logging.info('Shape of the HD95 array: {}'.format(hd95arr.shape))
     return dicearr, hd95arr
@@ -232,7 +276,9 @@ def main(argv=None):
     fh.setFormatter(logging.Formatter('[%(asctime)s.%(msecs)03d] %(message)s', datefmt='%H:%M:%S'))
     log.addHandler(fh)
     log.addHandler(logging.StreamHandler(sys.stdout))
-    logging.info(''.join(f'{k}={v}\n' for k, v in args._get_kwargs()))
+    # without --surface_metrics the log is what it was before the flag existed: its two entries are left out of the dump
+    shown = [(k, v) for k, v in args._get_kwargs() if args.surface_metrics or k not in ('surface_metrics', 'nsd_tolerance')]
+    logging.info(''.join(f'{k}={v}\n' for k, v in shown))
     if not args.synthetic:
         from .train import split_dir                              # the same table the trainers read their fold lists from
         ds, mod = {'acdc': ('acdc', ''), 'lvsc': ('lvsc', ''), 'chaost1': ('chaos', 't1'), 'chaost2': ('chaos', 't2')}[args.dataset]

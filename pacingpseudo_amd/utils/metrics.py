@@ -113,3 +113,70 @@ def compute_95hd(pred_hard, label, num_classes, spacing):
     p = torch.as_tensor(np.asarray(pred_hard), device=dev)[None]
     t = torch.as_tensor(np.asarray(label), device=dev)[None]
     return list(batch_hd95(p, t, num_classes, spacing)[0])
+
+
+def surface_metrics_from_reduction(counts: np.ndarray, out: np.ndarray, pixels: int, percentile: float = 95.0) -> dict:
+    """The host half of ``batch_surface_metrics``, numpy only: ``counts`` (items, 4) = {|surface pred|, |surface label|, |pred|,
+    |label|} of pp_hd95_surface_distances and ``out`` (items, 8) of pp_surface_reduce = {max, sum A, sum B, #(a <= tol),
+    #(b <= tol), S[j], S[min(j + 1, n - 1)], n}  ->  dict of (items,) float64 arrays
+      hd   = max,   assd = (sum A / na + sum B / nb) / 2   (medpy's assd: the mean of the two directed means),
+      nsd  = (#a + #b) / n,   hdp = S[j] + (S[j + 1] - S[j]) * (v - j),  v = (n - 1) * (percentile / 100), j = floor(v)
+    (numpy.percentile's linear rule).  NaN where the prediction or the label is empty or fills all ``pixels`` of the image
+    (inference.py:232, :253)."""
+    counts = np.asarray(counts).reshape(-1, 4).astype(np.int64)
+    out = np.asarray(out, np.float64).reshape(-1, 8)
+    if not 0.0 < float(percentile) <= 100.0:
+        raise ValueError(f'percentile = {percentile!r}: 0 < percentile <= 100')
+    ta, tb = counts[:, 2], counts[:, 3]
+    valid = (ta > 0) & (tb > 0) & (ta < pixels) & (tb < pixels)
+    na, nb = np.minimum(counts[:, 0], pixels).astype(np.float64), np.minimum(counts[:, 1], pixels).astype(np.float64)
+    n = out[:, 7]
+    v = (n - 1.0) * (float(percentile) / 100.0)
+    j = np.floor(v)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        res = dict(hd=out[:, 0].copy(),
+                   hdp=out[:, 5] + (out[:, 6] - out[:, 5]) * (v - j),
+                   assd=(out[:, 1] / na + out[:, 2] / nb) / 2.0,
+                   nsd=(out[:, 3] + out[:, 4]) / n)
+    for a in res.values():
+        a[~valid] = np.nan
+    return res
+
+
+def batch_surface_metrics(pred_hard: torch.Tensor, label: torch.Tensor, num_classes: int, spacing=(1.0, 1.0), tolerance: float = 2.0,
+                          percentile: float = 95.0) -> dict:
+    """Hausdorff distance, percentile Hausdorff distance (HD95 by default), average symmetric surface distance and surface Dice at
+    ``tolerance`` (in the unit of ``spacing``) per (sample, class) of hard class maps (N,H,W): dict of (N,K) float64 arrays
+    ``hd``, ``hdp``, ``assd``, ``nsd``.  ``hd`` is the reference's ``inference.py:_compute_hd`` (``medpy.metric.binary.hd``), ``hdp``
+    what ``batch_hd95`` returns, ``assd`` medpy's ``assd``.  The distance sets of pp_hd95_surface_distances stay on the device:
+    pp_surface_reduce turns them into eight numbers per item, and only those and the counts are copied back.  NaN where prediction
+    or label is empty or fills the image, as ``batch_hd95``."""
+    p = pred_hard.contiguous().to(torch.int64)
+    t = label.contiguous().to(torch.int64)
+    assert p.shape == t.shape and p.dim() == 3 and p.is_cuda and t.is_cuda
+    N, H, W = p.shape
+    K = int(num_classes)
+    tolerance, percentile = float(tolerance), float(percentile)
+    if not (np.isfinite(tolerance) and tolerance >= 0.0):
+        raise ValueError(f'tolerance = {tolerance!r}: a finite distance >= 0')
+    if not 0.0 < percentile <= 100.0:
+        raise ValueError(f'percentile = {percentile!r}: 0 < percentile <= 100')
+    sy, sx = (float(spacing), float(spacing)) if np.isscalar(spacing) else (float(spacing[0]), float(spacing[1]))
+    dist = torch.empty((N * K, 2, H * W), device=p.device, dtype=torch.float32)
+    counts = torch.empty((N * K, 4), device=p.device, dtype=torch.int32)
+    out = torch.empty((N * K, 8), device=p.device, dtype=torch.float64)
+    nws = lib.pp_hd95_workspace(N, K, H, W)
+    ws = torch.empty(nws, device=p.device, dtype=torch.uint8)
+    lib.pp_hd95_surface_distances(p.data_ptr(), t.data_ptr(), N, K, H, W, sy, sx, dist.data_ptr(), counts.data_ptr(),
+                                  ws.data_ptr(), nws, stream_ptr())
+    lib.pp_surface_reduce(dist.data_ptr(), counts.data_ptr(), N * K, H * W, percentile, tolerance, out.data_ptr(), stream_ptr())
+    res = surface_metrics_from_reduction(counts.cpu().numpy(), out.cpu().numpy(), H * W, percentile)
+    return {k: a.reshape(N, K) for k, a in res.items()}
+
+
+def compute_hd(pred_hard, label, num_classes, spacing):
+    """Per-class Hausdorff distance of one sample (inference.py:239-258): pred_hard / label (H,W) class maps."""
+    dev = torch.device('cuda', torch.cuda.current_device())
+    p = torch.as_tensor(np.asarray(pred_hard), device=dev)[None]
+    t = torch.as_tensor(np.asarray(label), device=dev)[None]
+    return list(batch_surface_metrics(p, t, num_classes, spacing)['hd'][0])

@@ -110,6 +110,23 @@ int pp_conv3x3_bwd_data(const float* dz, int ld_dz, int O, const float* wb, floa
                         int H, int W, int dil, int accumulate, void* stream);
 /* ... and wrt its weight, written in the nn.Conv2d layout: dw[o][c][ky][kx] (+)= sum_p dz[p][o] * x[p+off][c] */
 size_t pp_conv3x3_bwd_weight_workspace(int O, int Cpad, int B, int H, int W);
+/* (no reference counterpart) which launch plan pp_conv3x3_bwd_weight (f16x3 = 0) or pp_conv3x3_bwd_weight_f16x3 given a dz_amax
+ * (f16x3 = 1) runs for a shape with fp32 storage: a pure host query through the launchers' own plan functions, quoted by the
+ * tests to show which state of a plan a case exercised.  (The halo paths depend on the calling thread's pp_set_wgrad_cus budget;
+ * the 16-bit storage builds have no wgrad9 kernel and run the generic plan where this says PP_WGRAD_PATH_WGRAD9.)
+ * Returns PP_WGRAD_PATH_*; out (nullable) receives 6 ints: [0] partial slabs the finalize sums, [1] units per split, [2] units in
+ * the last split, [3] units in all, [4] splits that got a unit, [5] pixels in the last unit.  A unit is a chunk of 128 / 64 / 32
+ * pixels (tile 32 / 64 / 128), a 64-pixel row segment (wgrad9), a wave's pixel run (c4: a split is a block of four waves), a
+ * 4 x 32 pixel tile (halo: a split is a tile walker; [1] the tiles of walker 0, [2] those of the last walker that has any). */
+#define PP_WGRAD_PATH_C4 1        /* Cpad == 4 first layer */
+#define PP_WGRAD_PATH_WGRAD9 2    /* nine taps per staged row segment (fp32, dilation 1, W % 64 == 0, O <= 64, C <= 192) */
+#define PP_WGRAD_PATH_TILE32 3    /* generic split-K kernel, 32 / 64 / 128 channel tiles */
+#define PP_WGRAD_PATH_TILE64 4
+#define PP_WGRAD_PATH_TILE128 5
+#define PP_WGRAD_PATH_HALO 6      /* split-fp16 halo-tile walkers, one (32 x 32) channel pair per block */
+#define PP_WGRAD_PATH_HALO_2X1 7  /* ... two pairs per block: two output blocks share the x patch */
+#define PP_WGRAD_PATH_HALO_1X2 8  /* ... two input blocks share the dz tile (the last group half empty for 96 / 160 channels) */
+int pp_conv3x3_bwd_weight_plan(int O, int Cpad, int B, int H, int W, int dil, int f16x3, int* out);
 int pp_conv3x3_bwd_weight(const float* dz, int ld_dz, int O, const float* x, int ld_x, int Cpad, int I_true, int B,
                           int H, int W, int dil, float* dw_oihw, int accumulate, float* workspace,
                           size_t workspace_bytes, void* stream);
@@ -170,6 +187,9 @@ int pp_conv3x3_wino_bwd_data_f16x3(const float* dz, int ld_dz, int O, const void
 size_t pp_conv3x3_wino_bwd_weight_workspace(int O, int C, int B, int H, int W, int dil);
 /* reduction splits the weight-gradient GEMM of this shape runs with (shape-only; quoted by the parity tests) */
 int pp_conv3x3_wino_bwd_weight_splits(int O, int C, int B, int H, int W, int dil);
+/* ... and the rest of that plan; returns the splits, out (nullable) receives 6 ints: [0] rows of a GEMM block (64 / 128),
+ * [1] 32-tile chunks per split, [2] chunks in the last split, [3] chunks in all, [4] tiles in the last chunk, [5] tiles in all */
+int pp_conv3x3_wino_bwd_weight_plan(int O, int C, int B, int H, int W, int dil, int* out);
 /* v_cached (nullable): the v_keep of the forward call on the same x; when given, x is not read again */
 int pp_conv3x3_wino_bwd_weight(const float* dz, int ld_dz, int O, const float* x, int ld_x, int C, int B, int H, int W,
                                int dil, float* dw_oihw, int accumulate, const float* v_cached, void* workspace,
@@ -286,6 +306,9 @@ int pp_conv3x3_fwd_bn_lazy(const float* in, int ld_in, int C, const void* wf, co
                            int B, int H, int W, int dil, int f16x3, const float* in_amax, int bn_mode, const float* scale,
                            const float* shift, float slope, int groups, double* stats, size_t stats_bytes, int* rows_out,
                            const pp_lazy_in* lazy_in, void* stream);
+/* (16-bit storage builds, _h16 / _bf16: the lazy weight gradient stages y = lrelu(z * scale + shift) as fp16 and never stores it,
+ * so in bf16 storage it is NOT bit-identical to the entry fed the stored y; the engine's 16-bit plans do not take this form
+ * (engine.LAZY_HALO_H16) and the launch census does not cover it in 16-bit storage -- fp32 storage only.) */
 int pp_conv3x3_bwd_weight_f16x3_lazy(const float* dz, int ld_dz, int O, const float* x, int ld_x, int Cpad, int I_true, int B,
                                      int H, int W, int dil, float* dw_oihw, int accumulate, float* workspace,
                                      size_t workspace_bytes, const float* dz_amax, const pp_lazy_in* lazy_x, void* stream);
@@ -438,6 +461,9 @@ int pp_convtranspose_fwd(const float* x, int ld_x, int Cin, const float* w, floa
 int pp_convtranspose_bwd_data(const float* dout, int ld_dout, int Cout, const float* w, float* dx, int ld_dx, int Cin, int k,
                               int N, int H, int W, int accumulate, void* stream);
 size_t pp_convtranspose_bwd_weight_workspace(int Cin, int Cout, int k, int N, int H, int W);
+/* reduction splits of pp_convtranspose_bwd_weight for N*H*W input pixels (shape-only; quoted by the tests); out (nullable)
+ * receives [0] pixels per split, [1] pixels in the last split */
+int pp_convtranspose_bwd_weight_splits(int N, int H, int W, int* out);
 int pp_convtranspose_bwd_weight(const float* dout, int ld_dout, int Cout, const float* x, int ld_x, int Cin, int k, int N, int H,
                                 int W, float* dw, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 

@@ -52,6 +52,7 @@ _PROTOS = {
     'pp_conv3x3_fwd': (i32, [vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     'pp_conv3x3_bwd_data': (i32, [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     'pp_conv3x3_bwd_weight_workspace': (sz, [i32, i32, i32, i32, i32]),
+    'pp_conv3x3_bwd_weight_plan': (i32, [i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
     'pp_conv3x3_bwd_weight': (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, sz, vp]),
     'pp_pack_conv3x3_weights_f16x3': (i32, [vp, i32, i32, i32, vp, vp, vp]),
     'pp_conv3x3_fwd_f16x3': (i32, [vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
@@ -68,6 +69,7 @@ _PROTOS = {
     'pp_conv3x3_wino_bwd_data_f16x3': (i32, [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp]),
     'pp_conv3x3_wino_bwd_weight_workspace': (sz, [i32, i32, i32, i32, i32, i32]),
     'pp_conv3x3_wino_bwd_weight_splits': (i32, [i32, i32, i32, i32, i32, i32]),
+    'pp_conv3x3_wino_bwd_weight_plan': (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
     'pp_conv3x3_wino_bwd_weight': (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
     'pp_conv3x3_wino_bwd_weight_f16x3': (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, sz, vp, vp]),
     'pp_bn_workspace': (sz, [i32, i32, i32]),
@@ -138,6 +140,7 @@ _PROTOS = {
     'pp_convtranspose_fwd': (i32, [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     'pp_convtranspose_bwd_data': (i32, [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     'pp_convtranspose_bwd_weight_workspace': (sz, [i32, i32, i32, i32, i32, i32]),
+    'pp_convtranspose_bwd_weight_splits': (i32, [i32, i32, i32, C.POINTER(i32)]),
     'pp_convtranspose_bwd_weight': (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, sz, vp]),
     'pp_set_matrix_products': (i32, [i32]),
     'pp_get_matrix_products': (i32, []),
@@ -272,7 +275,7 @@ class _Lib:
             raise AttributeError(name)
         fn = getattr(self.load(), name)
         res = _PROTOS[name][0]
-        if res is not i32 or name in ('pp_version', 'pp_conv3x3_wino_tile', 'pp_conv3x3_wino_bwd_weight_splits', 'pp_conv3x3_lazy_ok', 'pp_conv3x3_lazy_ok_h16', 'pp_conv3x3_lazy_ok_bf16', 'pp_range_push', 'pp_range_pop', 'pp_get_matrix_products', 'pp_get_wgrad_cus', 'pp_grad_sumsq_rows'):      # sizes / queries / range depth: no status code
+        if res is not i32 or name in ('pp_version', 'pp_conv3x3_wino_tile', 'pp_conv3x3_wino_bwd_weight_splits', 'pp_conv3x3_wino_bwd_weight_plan', 'pp_conv3x3_bwd_weight_plan', 'pp_convtranspose_bwd_weight_splits', 'pp_conv3x3_lazy_ok', 'pp_conv3x3_lazy_ok_h16', 'pp_conv3x3_lazy_ok_bf16', 'pp_range_push', 'pp_range_pop', 'pp_get_matrix_products', 'pp_get_wgrad_cus', 'pp_grad_sumsq_rows'):      # sizes / queries / range depth: no status code
             return fn
 
         def checked(*a):

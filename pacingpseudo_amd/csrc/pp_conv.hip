@@ -2694,6 +2694,30 @@ static int wgrad_h16_blocks(int O, int C, int B, int H, int W, int cus = 0) {   
   (void)B; (void)H; (void)W;
   return wgrad_h16_walkers((O / 32) * (C / 32), cus);
 }
+// The launch of the split-fp16 halo weight gradient: (32 x 32) channel pairs per block (obk output x cbk input blocks), channel
+// groups per tile walker, tile walkers, partial slabs the finalize sums, tiles.
+// two pairs per block (four would need 11 prefetched float4 per thread next to 144 accumulator registers: spills).
+// Sharing the x patch (204 pixels) between two output blocks saves more staging than sharing the dz tile (128).
+// (96 / 160 input channels, round 5: two-pair blocks with a half-empty last group -- 32 outputs x 96 inputs at 256^2 ran as three
+// one-pair blocks per tile, each staging the dz tile again for 27 MFMAs per wave)
+struct WgradH16Plan { int obk, cbk, per_walker, walkers, slabs, n_tiles; };
+static WgradH16Plan wgrad_h16_plan(int O, int C, int B, int H, int W, int cus = 0) {
+  constexpr int mp = 1, odd = 1;
+  WgradH16Plan q;
+  q.obk = (mp && O % 64 == 0) ? 2 : 1;
+  q.cbk = (mp && q.obk == 1 && (C % 64 == 0 || (odd && C > 32))) ? 2 : 1;
+  q.n_tiles = B * (H / HT_ROWS) * (W / HT_COLS);
+  if (q.obk * q.cbk > 1) {                         // several (32 x 32) pairs per block: the tile is staged once for all of them
+    q.per_walker = (O / (32 * q.obk)) * ((C / 32 + q.cbk - 1) / q.cbk);
+    q.walkers = wgrad_h16_walkers(q.per_walker, cus);
+    q.slabs = q.walkers;                           // <= 4 * wgrad_h16_blocks: the workspace bound covers it
+  } else {
+    q.per_walker = (O / 32) * (C / 32);
+    q.walkers = wgrad_h16_blocks(O, C, B, H, W, cus);
+    q.slabs = q.walkers * 4;                       // each wave pair of a one-pair block writes its own partial
+  }
+  return q;
+}
 
 struct WgradPlan { int tile; int bk; int o_tiles, c_tiles, splits, chunks_per_split, n_chunks; };
 
@@ -2734,6 +2758,45 @@ extern "C" size_t pp_conv3x3_bwd_weight_workspace(int O, int Cpad, int B, int H,
     if (n16 > need) need = n16;
   }
   return need;
+}
+
+// Which launch plan pp_conv3x3_bwd_weight (f16x3 = 0) or pp_conv3x3_bwd_weight_f16x3 with a dz_amax (f16x3 = 1) runs for a shape
+// with fp32 storage, by the same *_applicable / *_plan functions the launchers call (a pure function of the shape and, for the
+// halo paths, of the calling thread's CU budget): tests quote it to show which state of a plan they exercised.  The 16-bit
+// storage builds have no wgrad9 kernel: they run the generic plan where this says PP_WGRAD_PATH_WGRAD9.
+// Returns PP_WGRAD_PATH_*; out (nullable) receives 6 ints:
+//   [0] partial slabs the finalize sums          [1] units per split             [2] units in the last split
+//   [3] units in all                             [4] splits that got a unit      [5] pixels in the last unit
+// A unit is a chunk of bk pixels (generic), a 64-pixel row segment (wgrad9), a wave's pixel run (c4; a split is a block of four
+// waves), a 4 x 32 pixel tile (halo; a split is a tile walker, [1] the tiles of walker 0, [2] of the last walker that has any).
+extern "C" int pp_conv3x3_bwd_weight_plan(int O, int Cpad, int B, int H, int W, int dil, int f16x3, int* out) {
+  const int P = B * H * W;
+  int path, v[6];
+  if (f16x3 && wgrad_h16_applicable(O, Cpad, H, W, dil)) {
+    const WgradH16Plan q = wgrad_h16_plan(O, Cpad, B, H, W);
+    path = q.obk == 2 ? PP_WGRAD_PATH_HALO_2X1 : (q.cbk == 2 ? PP_WGRAD_PATH_HALO_1X2 : PP_WGRAD_PATH_HALO);
+    const int live = q.n_tiles < q.walkers ? q.n_tiles : q.walkers;
+    v[0] = q.slabs; v[1] = pp_cdiv(q.n_tiles, q.walkers); v[2] = (q.n_tiles - (live - 1) + q.walkers - 1) / q.walkers;
+    v[3] = q.n_tiles; v[4] = live; v[5] = HT_ROWS * HT_COLS;
+  } else if (wgrad_c4_applicable(O, Cpad, W)) {
+    const WgradC4Plan q = wgrad_c4_plan(P);
+    const int waves = pp_cdiv(P, q.px_per_wave);
+    path = PP_WGRAD_PATH_C4;
+    v[0] = q.blocks; v[1] = 4; v[2] = waves - (q.blocks - 1) * 4; v[3] = waves; v[4] = q.blocks; v[5] = P - (waves - 1) * q.px_per_wave;
+  } else if (wgrad9_applicable(O, Cpad, H, W, dil)) {
+    const Wgrad9Plan q = wgrad9_plan(O, Cpad, P);
+    path = PP_WGRAD_PATH_WGRAD9;
+    v[0] = q.splits; v[1] = q.segs_per_split; v[2] = q.n_segs - (q.splits - 1) * q.segs_per_split; v[3] = q.n_segs; v[4] = q.splits;
+    v[5] = W9_SEG;
+  } else {
+    const WgradPlan q = wgrad_plan(O, Cpad, P);
+    path = q.tile == 128 ? PP_WGRAD_PATH_TILE128 : (q.tile == 64 ? PP_WGRAD_PATH_TILE64 : PP_WGRAD_PATH_TILE32);
+    v[0] = q.splits; v[1] = q.chunks_per_split; v[2] = q.n_chunks - (q.splits - 1) * q.chunks_per_split; v[3] = q.n_chunks;
+    v[4] = q.splits; v[5] = P - (q.n_chunks - 1) * q.bk;
+  }
+  if (out)
+    for (int i = 0; i < 6; ++i) out[i] = v[i];
+  return path;
 }
 #endif  // !PP_ACT_16
 
@@ -2852,33 +2915,23 @@ static int bwd_weight_f16x3_impl(const pp_act* dz, int ld_dz, int O, const pp_ac
   const int P = B * H * W;
   PP_CHECK_ARG((long long)P * ld_x < 0x3fffffffLL && (long long)P * ld_dz < 0x3fffffffLL,
                "wgrad_f16x3: tensor exceeds the 4 GiB buffer-descriptor range");
-  const int gx = wgrad_h16_blocks(O, Cpad, B, H, W);
-  const size_t need = (size_t)gx * 4 * O * 9 * Cpad * sizeof(float);
+  const WgradH16Plan hp = wgrad_h16_plan(O, Cpad, B, H, W);        // the one plan of this launch: grid, walkers, partial slabs
+  const size_t need = (size_t)hp.slabs * O * 9 * Cpad * sizeof(float);
   if (workspace_bytes < need) {
     pp_set_error("wgrad_f16x3: workspace too small (%zu < %zu)", workspace_bytes, need);
     return PP_ERR_WORKSPACE;
   }
-  WgradH16Args a{dz, ld_dz, O, x, ld_x, Cpad, workspace, P, H, W, Cpad / 32, W / HT_COLS, H / HT_ROWS,
-                 B * (H / HT_ROWS) * (W / HT_COLS),
+  WgradH16Args a{dz, ld_dz, O, x, ld_x, Cpad, workspace, P, H, W, Cpad / 32, W / HT_COLS, H / HT_ROWS, hp.n_tiles,
                  (unsigned)(((long long)(P - 1) * ld_dz + O) * PP_ACT_BYTES), (unsigned)(((long long)(P - 1) * ld_x + Cpad) * PP_ACT_BYTES), 0, 0};
   a.lazy = lazy;
   const bool lz = lazy.coef != nullptr;
   const size_t lds = (size_t)2 * (WH_DZ_PIX + HT_PIX) * WH_RS * sizeof(_Float16) + (lz ? 2 * 96 * sizeof(float) : 0);
   pp_prof_begin2(PP_K_CONV_WGRAD_F16X3, 6.0 * P * (double)O * 9.0 * Cpad, 2.0 * P * (double)O * 9.0 * Cpad,
                  4.0 * ((double)P * (O + Cpad) + 9.0 * O * Cpad), s);
-  constexpr int mp = 1;
-  // two pairs per block (four would need 11 prefetched float4 per thread next to 144 accumulator registers: spills).
-  // Sharing the x patch (204 pixels) between two output blocks saves more staging than sharing the dz tile (128).
-  // (96 / 160 input channels, round 5: two-pair blocks with a half-empty last group -- 32 outputs x 96 inputs at 256^2 ran as three
-  // one-pair blocks per tile, each staging the dz tile again for 27 MFMAs per wave)
-  constexpr int odd = 1;
-  const int obk = (mp && O % 64 == 0) ? 2 : 1, cbk = (mp && obk == 1 && (Cpad % 64 == 0 || (odd && Cpad > 32))) ? 2 : 1;
-  int slabs = gx * 4;
+  const int obk = hp.obk, cbk = hp.cbk, slabs = hp.slabs;
+  a.walkers = hp.walkers; a.per_walker = hp.per_walker;
   if (obk * cbk > 1) {                             // several (32 x 32) pairs per block: the tile is staged once for all of them
-    const int groups = (O / (32 * obk)) * ((Cpad / 32 + cbk - 1) / cbk);
-    const int gmp = wgrad_h16_walkers(groups);
-    slabs = gmp;                                   // <= gx * 4: the workspace bound above covers it
-    a.walkers = gmp; a.per_walker = groups;
+    const int groups = hp.per_walker, gmp = hp.walkers;
     const size_t lmp = (size_t)2 * (obk * WH_DZ_PIX + cbk * HT_PIX) * WH_RS * sizeof(_Float16) + (lz ? (size_t)2 * 96 * cbk * sizeof(float) : 0);
 #define WGMP_LAUNCH(OB, CB, LZ)                                                                                              \
     do {                                                                                                                       \
@@ -2889,9 +2942,8 @@ static int bwd_weight_f16x3_impl(const pp_act* dz, int ld_dz, int O, const pp_ac
     else { if (lz) WGMP_LAUNCH(1, 2, true); else WGMP_LAUNCH(1, 2, false); }
 #undef WGMP_LAUNCH
   } else {
-    a.walkers = gx; a.per_walker = (O / 32) * (Cpad / 32);
-    if (lz) hipLaunchKernelGGL(conv3x3_wgrad_halo_f16x3_kernel<true>, dim3(gx * a.per_walker), dim3(WH_THREADS), lds, s, a, dz_amax);
-    else hipLaunchKernelGGL(conv3x3_wgrad_halo_f16x3_kernel<false>, dim3(gx * a.per_walker), dim3(WH_THREADS), lds, s, a, dz_amax);
+    if (lz) hipLaunchKernelGGL(conv3x3_wgrad_halo_f16x3_kernel<true>, dim3(hp.walkers * hp.per_walker), dim3(WH_THREADS), lds, s, a, dz_amax);
+    else hipLaunchKernelGGL(conv3x3_wgrad_halo_f16x3_kernel<false>, dim3(hp.walkers * hp.per_walker), dim3(WH_THREADS), lds, s, a, dz_amax);
   }
   pp_prof_end(s);
   if (int rc = pp_launch_status("conv3x3_wgrad_halo_f16x3")) return rc;

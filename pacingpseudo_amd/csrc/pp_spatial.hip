@@ -1209,9 +1209,18 @@ static int ct_check(const CtArgs& a) {
   return 0;
 }
 static int ct_splits(int P) { int s = pp_cdiv(P, 4096); return s < 1 ? 1 : (s > 64 ? 64 : s); }
+static int ct_p_per_split(int P) { return pp_cdiv(P, ct_splits(P)); }
 
 extern "C" size_t pp_convtranspose_bwd_weight_workspace(int Cin, int Cout, int k, int N, int H, int W) {
   return (size_t)ct_splits(N * H * W) * Cin * Cout * k * k * sizeof(float) + 256;
+}
+
+// Reduction splits pp_convtranspose_bwd_weight runs with for N*H*W input pixels (a pure function of the shape, quoted by the
+// tests); out (nullable) receives [0] pixels per split, [1] pixels in the last split.
+extern "C" int pp_convtranspose_bwd_weight_splits(int N, int H, int W, int* out) {
+  const int P = N * H * W, splits = ct_splits(P), per = ct_p_per_split(P);
+  if (out) { out[0] = per; out[1] = P - (splits - 1) * per; }
+  return splits;
 }
 
 extern "C" int pp_convtranspose_fwd(const float* x, int ld_x, int Cin, const float* w, float* out, int ld_out, int Cout, int k, int N,
@@ -1242,7 +1251,7 @@ extern "C" int pp_convtranspose_bwd_weight(const float* dout, int ld_g, int Cout
     pp_set_error("convtranspose_bwd_weight: workspace too small");
     return PP_ERR_WORKSPACE;
   }
-  a.p_per_split = pp_cdiv(P, splits);
+  a.p_per_split = ct_p_per_split(P);
   const int J = Cout * k * k;
   hipLaunchKernelGGL(convtranspose_gemm_kernel<2>, dim3(pp_cdiv(Cin, 64), pp_cdiv(J, 64), splits), dim3(256), 0, (hipStream_t)stream, a);
   const long long n = (long long)Cin * J;

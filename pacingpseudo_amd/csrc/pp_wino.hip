@@ -2089,6 +2089,17 @@ extern "C" int pp_conv3x3_wino_bwd_weight_splits(int O, int C, int B, int H, int
   const WinoGeom g = wino_geom(B, H, W, dil);
   return wino_wg_plan(O, C, g.T, g.nb).splits;
 }
+// ... and the rest of that plan: out (nullable) receives [0] rows of a GEMM block (64 / 128), [1] 32-tile chunks per split,
+// [2] chunks in the last split, [3] chunks in all, [4] tiles in the last chunk, [5] Winograd tiles in all.  Returns the splits.
+extern "C" int pp_conv3x3_wino_bwd_weight_plan(int O, int C, int B, int H, int W, int dil, int* out) {
+  const WinoGeom g = wino_geom(B, H, W, dil);
+  const WinoWgPlan p = wino_wg_plan(O, C, g.T, g.nb);
+  if (out) {
+    out[0] = p.bm; out[1] = p.chunks_per_split; out[2] = p.n_chunks - (p.splits - 1) * p.chunks_per_split; out[3] = p.n_chunks;
+    out[4] = g.T - (p.n_chunks - 1) * 32; out[5] = g.T;
+  }
+  return p.splits;
+}
 #endif  // !PP_ACT_16
 
 static int wino_bwd_weight_impl(const act_t* dz, int ld_dz, int O, const act_t* x, int ld_x, int C, int B,

@@ -7,6 +7,7 @@ _lib._PROTOS whose last argument is the stream (shape and workspace queries are 
 the launch shape is the argument list with pointers replaced by 'p' / None (null), buffer sizes by 'sz' and a lazy input by
 ('lazy', ld, groups) -- together with the configurations that made it.  The configurations run once per process (record() is
 cached): tests/test_gpu_conv_census.py replays the convolution family of the record, tests/test_gpu_stream_census.py the rest.
+record_batches() is a second recording of the same kind at other batch sizes and of the Control plan (batch_configs()).
 """
 import ctypes
 import functools
@@ -77,11 +78,14 @@ def _configs():
     return c
 
 
-def _run_config(label, name, storage, size, classes, os_, variant):
+def _run_config(label, name, storage, size, classes, os_, variant, batch=2):
     from tests.test_gpu_step import build_model
     # output stride 32 pools encoder stage 6 below stage 5: no auxiliary path there (as the golden case 'stride32')
     over = dict(do_aux_path=False, do_memory=False) if os_ == 32 else {}
-    args = O.full_flags(num_classes=classes, ignored_index=classes, output_stride=os_, **over)
+    if variant == 'control':        # the Control plan of test_full_width_model_against_oracle: one backbone pass, no optional branch
+        args = O.default_args(num_classes=classes, ignored_index=classes, output_stride=os_)
+    else:
+        args = O.full_flags(num_classes=classes, ignored_index=classes, output_stride=os_, **over)
     args.storage = storage
     if variant == 'strided':
         args.is_stride_conv = args.is_trans_conv = True
@@ -95,7 +99,7 @@ def _run_config(label, name, storage, size, classes, os_, variant):
         from tests._bucket_probe import NoopComm
         model.engine.comm = NoopComm()
         model.engine.sync_bn = True
-    batch = {k: v.cuda() for k, v in O.synthetic_batch(2, size, size, num_classes=classes, seed=7, keep=0.03).items() if k != 'label'}
+    batch = {k: v.cuda() for k, v in O.synthetic_batch(batch, size, size, num_classes=classes, seed=7, keep=0.03).items() if k != 'label'}
     for bn_eval in (False, True):
         label[0] = f'{name}/{"eval" if bn_eval else "train"}-BN'
         model.train()
@@ -120,9 +124,7 @@ def _run_inference():
     del net
 
 
-@functools.lru_cache(maxsize=None)
-def record():
-    """{(storage, entry, launch shape): set of configuration labels}, over every configuration (cached for the process)."""
+def _record(configs, inference):
     from pacingpseudo_amd import engine as E
     rec = defaultdict(set)
     real, real_lib = E.lib_for, E.lib
@@ -134,15 +136,41 @@ def record():
     E.lib_for = patched
     E.lib = _Recorder(real_lib, 'fp32', lambda key: rec[key].add(label[0]))
     try:
-        for name, cfg in _configs().items():
+        for name, cfg in configs.items():
             try:
                 _run_config(label, name, *cfg)
             except Exception as e:
                 raise RuntimeError(f'census configuration {label[0]} failed: {e}') from e
             torch.cuda.empty_cache()
-        label[0] = '256x272/inference'
-        _run_inference()
-        torch.cuda.empty_cache()
+        if inference:
+            label[0] = '256x272/inference'
+            _run_inference()
+            torch.cuda.empty_cache()
     finally:
         E.lib_for, E.lib = real, real_lib
     return dict(rec)
+
+
+@functools.lru_cache(maxsize=None)
+def record():
+    """{(storage, entry, launch shape): set of configuration labels}, over every configuration (cached for the process)."""
+    return _record(_configs(), True)
+
+
+BATCH_IMAGE_SIZE = 128        # the smallest square size of the batch recordings: every stage of the full-flags model exists (Dice phantoms)
+
+
+def batch_configs():
+    """label -> (storage, size, classes, output stride, variant, batch): batches that are no power of two, the reference's default
+    batch of 12 and the Control plan, on small images.  The launch plans of the convolution family are functions of B * H * W and
+    of tile counts; record() runs every configuration at batch 2."""
+    s = BATCH_IMAGE_SIZE
+    return {f'{s}/b3': ('fp32', s, 5, 8, '', 3), f'{s}/b12': ('fp32', s, 5, 8, '', 12),
+            f'{s}/b3/fp16': ('fp16', s, 5, 8, '', 3), f'{s}/b3/bf16': ('bf16', s, 5, 8, '', 3),
+            f'{s}/b8/control': ('fp32', s, 5, 8, 'control', 8)}
+
+
+@functools.lru_cache(maxsize=None)
+def record_batches():
+    """As record(), over batch_configs(): {(storage, entry, launch shape): set of labels '<configuration>/<train|eval>-BN'}."""
+    return _record(batch_configs(), False)

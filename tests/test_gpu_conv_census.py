@@ -8,10 +8,15 @@ padding columns:
   * fp32 storage: against conv2d / conv_transpose2d / their gradients in float64 (outputs, data and weight gradients 1e-4,
     BatchNorm partial sums 1e-5); lazy-input forms against the lazy tensor evaluated in float64 and, bit for bit, against the
     ordinary entry point fed the materialised tensor (the harness of test_direct_convolution_with_lazy_input); the first layer's
-    folded weight gradient through the harness of test_first_layer_bn_backward_with_folded_weight_gradient.
+    folded weight gradient against float64 autograd at the tolerances of test_first_layer_bn_backward_with_folded_weight_gradient,
+    on operands moved off the LeakyReLU kink (_wgrad_c1).
   * 16-bit storage: the _h16 / _bf16 entry against its fp32 twin on operands representable in the 16-bit type (check_act's bound,
     with the output's own magnitude as the intermediate a kernel may store in 16 bits first; fp32 results such as weight gradients
     at 1e-4), and that fp32 twin against float64 at the same shape.
+A second recording (tests/_launch_census.py::record_batches) runs batch 3 and 12, 16-bit storage at batch 3 and the Control plan on
+128-pixel images, one test case per configuration; an edge table feeds hand-made launches to the same adapters at the states of
+the launch plans (asserted through the library's plan queries), and a planted-mistake test shows the gate fails when an entry
+point is called wrongly.
 A recorded launch without a replay adapter fails the census by name.  Outside the census: the stand-alone AuxPath.forward (it calls
 the library directly, not through a plan) and --precision fp16 (fp16-grade by design, tested on its own).
 """
@@ -159,12 +164,14 @@ def _pack_direct(w, O_, I, f16):
     return wf, wb
 
 
-def _pack_wino(w, O_, I, tile, f16):
+def _pack_wino(w, O_, I, tile, f16, K=None):
+    """U of the geometry's tile, packed through the entry-point table K of the run (a stand-in table can pack wrongly)."""
     from pacingpseudo_amd._lib import lib, stream_ptr
+    K = lib if K is None else K
     n = (tile + 2) ** 2
     uf, ub = torch.zeros(n, O_, I, device=_dev()), torch.zeros(n, I, O_, device=_dev())
-    (lib.pp_wino_pack_weights_f16x3 if f16 else lib.pp_wino_pack_weights)(w.data_ptr(), O_, I, tile, uf.data_ptr(), ub.data_ptr(),
-                                                                          stream_ptr())
+    (K.pp_wino_pack_weights_f16x3 if f16 else K.pp_wino_pack_weights)(w.data_ptr(), O_, I, tile, uf.data_ptr(), ub.data_ptr(),
+                                                                      stream_ptr())
     return uf, ub
 
 
@@ -227,7 +234,7 @@ def _wino_fwd(key, run):
     w = ops.randn(N, C, 3, 3, scale=1 / math.sqrt(9 * C)).to(_dev())
     b = ops.randn(N).to(_dev())
     prior = ops.r(ops.randn(B, H, W, N)) if acc else None
-    U, _ = _pack_wino(w, N, C, lib.pp_conv3x3_wino_tile(H, W, dil), f16)
+    U, _ = _pack_wino(w, N, C, lib.pp_conv3x3_wino_tile(H, W, dil), f16, run.K)
     nws = lib.pp_conv3x3_wino_workspace(C, N, B, H, W, dil)
     ws = _ws(nws)
     vk = torch.empty(lib.pp_conv3x3_wino_vkeep_elems(C, B, H, W, dil), device=_dev()) if vkeep else None
@@ -262,7 +269,7 @@ def _bn_fwd(key, run):
     from pacingpseudo_amd._lib import lib
     if wino:
         tile = lib.pp_conv3x3_wino_tile(H, W, dil)
-        U, _ = _pack_wino(w, N, C, tile, f16)
+        U, _ = _pack_wino(w, N, C, tile, f16, run.K)
         nws = lib.pp_conv3x3_wino_workspace(C, N, B, H, W, dil)
         ws = _ws(nws)
         vk = torch.empty(lib.pp_conv3x3_wino_vkeep_elems(C, B, H, W, dil), device=_dev()) if vkeep else None
@@ -326,7 +333,7 @@ def _bwd_data(key, run):
     am = _amax(dz[..., :O_]) if (f16 and a[-2]) else None
     from pacingpseudo_amd._lib import lib
     if wino:
-        _, Ub = _pack_wino(w, O_, I, lib.pp_conv3x3_wino_tile(H, W, dil), f16)
+        _, Ub = _pack_wino(w, O_, I, lib.pp_conv3x3_wino_tile(H, W, dil), f16, run.K)
         nws = lib.pp_conv3x3_wino_workspace(O_, I, B, H, W, dil)
         ws = _ws(nws)
         args = (dz.data_ptr(), ld_dz, O_, Ub.data_ptr(), dx.data_ptr(), ld_dx, I, B, H, W, dil, acc, ws.data_ptr(), nws)
@@ -382,7 +389,7 @@ def _bwd_weight(key, run):
             if vcached:
                 tile = lib.pp_conv3x3_wino_tile(H, W, dil)
                 vk = torch.empty(lib.pp_conv3x3_wino_vkeep_elems(C, B, H, W, dil), device=_dev())
-                uf, _ = _pack_wino(ops.randn(O_, C, 3, 3).to(_dev()), O_, C, tile, f16)
+                uf, _ = _pack_wino(ops.randn(O_, C, 3, 3).to(_dev()), O_, C, tile, f16, run.K)
                 tmp = run.out(B, H, W, O_, O_)
                 fwd = run.K.pp_conv3x3_wino_fwd_f16x3 if f16 else run.K.pp_conv3x3_wino_fwd
                 fwd(src.data_ptr(), ld_x, C, uf.data_ptr(), None, tmp.data_ptr(), O_, O_, B, H, W, dil, 0, vk.data_ptr(), ws.data_ptr(),
@@ -539,8 +546,15 @@ def _convtranspose(key, run):
 
 def _wgrad_c1(key, run):
     """pp_bn_lrelu_bwd[_eval]_wgrad_c1 (first layer: BatchNorm + LeakyReLU backward with the weight gradient folded in).
-    fp32 twin: the harness of test_first_layer_bn_backward_with_folded_weight_gradient at the recorded geometry.  16-bit entry:
-    against that twin on identical representable operands and coefficient rows (its results are fp32)."""
+    fp32 twin: dW, dgamma, dbeta (and, where it is not 0 by construction, the conv-bias gradient) against float64 autograd of
+    batch_norm + leaky_relu per statistics group and conv2d_weight of its dz, at the tolerances of
+    test_first_layer_bn_backward_with_folded_weight_gradient; the one-pass eval form reads (dy, y) and recovers xhat from y: with
+    fp32 storage it is held to the same autograd from z (dgamma at 5 x TOL, that test's figure), only the fp32 twin of a 16-bit
+    launch, which is handed a y rounded to 16 bits, to the float64 value of that recovery on the y of the call.
+    That test's own operands serve its small shapes only: over 10^7 elements one pre-activation lies within fp32 rounding of the
+    LeakyReLU kink, float64 takes the other branch there and a single such element moves dW by 2e-4 of its largest entry (seen at
+    24 x 128 x 128); so, as in the stream census, the few z whose pre-activation is within 1e-4 of the kink are moved off it.
+    16-bit entry: against the twin on identical representable operands and coefficient rows (its results are fp32)."""
     storage, name, a = key
     ev = 'eval' in name
     if ev:
@@ -550,12 +564,6 @@ def _wgrad_c1(key, run):
         _, ld_dy, _, ld_z, _, _, _, _, _, training, _, ld_x, H, W, _, acc_dw, _, _, _, acc_p, C, ppg, groups = a[:23]
         P = ppg * groups
     B = P // (groups * H * W)
-    if run.dt == torch.float32:
-        if run.want_ref:
-            from tests.test_gpu_round5 import test_first_layer_bn_backward_with_folded_weight_gradient as harness
-            harness(C, B, H, W, groups, bool(training), 'fp32')
-            run.res.append(('fp32 harness (test_first_layer_bn_backward_with_folded_weight_gradient)', None, True, None, False))
-        return
     from pacingpseudo_amd._lib import lib
     ops = _Ops(key)
     N = B * groups
@@ -569,18 +577,27 @@ def _wgrad_c1(key, run):
     rm, rv = ops.randn(C) * 0.1, torch.rand(C, generator=ops.g) + 0.5
     coef = torch.empty(4, groups, C, device=_dev())
     mean, invstd, scale, shift = (coef[i].data_ptr() for i in range(4))
-    gd, bd, rmd, rvd = (t.to(_dev()) for t in (gamma, beta, rm, rv))
+    gd, bd = (t.to(_dev()) for t in (gamma, beta))
     nbt = torch.zeros((), dtype=torch.int64, device=_dev())
     nws = max(lib.pp_bn_lrelu_bwd_wgrad_c1_workspace(C, P // groups, groups), lib.pp_bn_lrelu_bwd_wgrad_c1_workspace(C, P, 1),
               lib.pp_bn_workspace(C, P // groups, groups))
     ws = _ws(nws)
+
+    def rows(zt):           # the coefficient rows the kernels are handed, from the library itself
+        rmd, rvd = rm.to(_dev()), rv.to(_dev())
+        if training:
+            lib.pp_bn_train_stats(zt.data_ptr(), ld_z, C, P // groups, groups, 1e-5, 0.1, gd.data_ptr(), bd.data_ptr(), rmd.data_ptr(),
+                                  rvd.data_ptr(), nbt.data_ptr(), mean, invstd, scale, shift, ws.data_ptr(), nws, run.st)
+        else:
+            lib.pp_bn_eval_coeffs(C, groups, 1e-5, gd.data_ptr(), bd.data_ptr(), rmd.data_ptr(), rvd.data_ptr(), mean, invstd, scale,
+                                  shift, run.st)
+        torch.cuda.synchronize()
     z32 = z.to(_dev())
-    if training:
-        lib.pp_bn_train_stats(z32.data_ptr(), ld_z, C, P // groups, groups, 1e-5, 0.1, gd.data_ptr(), bd.data_ptr(), rmd.data_ptr(),
-                              rvd.data_ptr(), nbt.data_ptr(), mean, invstd, scale, shift, ws.data_ptr(), nws, run.st)
-    else:
-        lib.pp_bn_eval_coeffs(C, groups, 1e-5, gd.data_ptr(), bd.data_ptr(), rmd.data_ptr(), rvd.data_ptr(), mean, invstd, scale,
-                              shift, run.st)
+    rows(z32)
+    v = z32[..., :C].double().reshape(groups, -1, C)
+    near = ((v * coef[2].double()[:, None] + coef[3].double()[:, None]).abs() < 1e-4).reshape(N, H, W, C)
+    z32[..., :C] = torch.where(near, ops.r((z32[..., :C] + 0.125).cpu()).to(_dev()), z32[..., :C])
+    rows(z32)               # (train mode: the rows move by ~1e-6, the margin stays)
     if ev:          # the one-pass eval form reads the stored output y = lrelu(z * scale + shift)
         pre = z32[..., :C] * coef[2] + coef[3]
         zsrc = z32.clone()
@@ -589,7 +606,7 @@ def _wgrad_c1(key, run):
         zsrc = z32
     res = []
     pdw, pp = ops.randn(C, 1, 3, 3) * ops.gs, ops.randn(3, C) * ops.gs
-    for K, dt in ((lib, torch.float32), (run.K, run.dt)):
+    for K, dt in ((run.K, run.dt),) if run.dt == torch.float32 else ((lib, torch.float32), (run.K, run.dt)):
         xd, zd, dyd = (t.to(_dev()).to(dt).contiguous() for t in (x, zsrc, dy))
         dw = (pdw if acc_dw else torch.full((C, 1, 3, 3), 5.0)).to(_dev())
         dg, db, dbc = ((pp[i] if acc_p else torch.full((C,), 9.0)).to(_dev()) for i in range(3))
@@ -603,8 +620,36 @@ def _wgrad_c1(key, run):
                                        acc_p, C, ppg, groups, 0.01, ws.data_ptr(), nws, run.st)
         torch.cuda.synchronize()
         res.append((dw, dg, db, dbc))
-    for label, h, f in zip(('dw', 'dgamma', 'dbeta', 'dbias'), res[1], res[0]):
-        run.res.append((label + ' vs fp32 twin', h, f.double(), TOL, False))
+    labels = ('dw', 'dgamma', 'dbeta', 'dbias')
+    if run.dt != torch.float32:
+        for label, h, f in zip(labels, res[1], res[0]):
+            run.res.append((label + ' vs fp32 twin', h, f.double(), TOL, False))
+        return
+    refs = [None] * 4
+    if run.want_ref and ev and storage != 'fp32':         # the twin of a 16-bit launch is handed a ROUNDED y: the same operation on (dy, y)
+        y64, dy64 = zsrc[..., :C].double(), dy[..., :C].double().to(_dev())
+        gg = torch.where(y64 > 0, dy64, dy64 * 0.01)
+        xhat = (torch.where(y64 > 0, y64, y64 / 0.01) - bd.double()) / gd.double()
+        dz = (gg * coef[2, 0].double()).permute(0, 3, 1, 2)
+        with _cudnn_off():
+            refs[0] = torch.nn.grad.conv2d_weight(_n64(x, 1), (C, 1, 3, 3), dz, 1, 1, 1) + (pdw.double().to(_dev()) if acc_dw else 0)
+        prior = pp.double().to(_dev()) if acc_p else torch.zeros(3, C, dtype=torch.float64, device=_dev())
+        refs[1], refs[2], refs[3] = (gg * xhat).sum((0, 1, 2)) + prior[0], gg.sum((0, 1, 2)) + prior[1], dz.sum((0, 2, 3)) + prior[2]
+    elif run.want_ref:
+        zr = _n64(z32, C).requires_grad_(True)
+        g64, b64 = gd.double().requires_grad_(True), bd.double().requires_grad_(True)
+        rm64, rv64 = rm.double().to(_dev()), rv.double().to(_dev())
+        ys = [F.leaky_relu(F.batch_norm(zr[gi * B:(gi + 1) * B], rm64.clone(), rv64.clone(), g64, b64, bool(training), 0.1, 1e-5), 0.01)
+              for gi in range(groups)]
+        torch.cat(ys).backward(_n64(dy, C))
+        with _cudnn_off():
+            refs[0] = torch.nn.grad.conv2d_weight(_n64(x, 1), (C, 1, 3, 3), zr.grad, 1, 1, 1) + (pdw.double().to(_dev()) if acc_dw else 0)
+        prior = pp.double().to(_dev()) if acc_p else torch.zeros(3, C, dtype=torch.float64, device=_dev())
+        refs[1], refs[2], refs[3] = g64.grad + prior[0], b64.grad + prior[1], zr.grad.sum((0, 2, 3)) + prior[2]
+    for label, got, ref in zip(labels, res[0], refs):
+        if label == 'dbias' and training:         # the sum of a train-mode dz is 0: nothing to be relative to
+            continue
+        run.check(label, got, ref, tol=5 * TOL if (ev and label == 'dgamma') else TOL, act=False)
 
 
 ADAPTERS = {
@@ -720,15 +765,11 @@ def test_census_holds_what_the_dispatch_promises(census):
     assert has('256x272/inference', 'fp32', ('pp_conv3x3_wino_fwd', 'pp_conv3x3_wino_fwd_bn'), at(32, 34, 1, 2))
 
 
-def test_every_recorded_convolution_launch_matches_float64(census):
-    """Replay every distinct launch; list every failing one, worst first, with the configurations that produced it."""
-    per_cfg = defaultdict(int)
-    for cfgs in census.values():
-        for c in cfgs:
-            per_cfg[c] += 1
+def _report(keys, cfgs_of):
+    """Replay `keys`; print the worst error / tolerance per entry point; return (failures, entry points without an adapter)."""
     worst = defaultdict(float)
     failures, missing = [], set()
-    for key in sorted(census, key=repr):
+    for key in keys:
         try:
             res = replay(key)
         except KeyError as e:
@@ -739,12 +780,431 @@ def test_every_recorded_convolution_launch_matches_float64(census):
         for label, ratio in res:
             worst[entry] = max(worst[entry], ratio)
             if not ratio <= 1.0:
-                failures.append((ratio, entry, label, key[2], sorted(census[key])))
+                failures.append((ratio, entry, label, key[2], cfgs_of(key)))
+    for e in sorted(worst):
+        print(f'  worst error / tolerance  {e:42s} {worst[e]:.3g}')
+    failures.sort(key=lambda f: -f[0] if f[0] == f[0] else -math.inf)
+    return failures, missing
+
+
+def test_every_recorded_convolution_launch_matches_float64(census):
+    """Replay every distinct launch; list every failing one, worst first, with the configurations that produced it."""
+    per_cfg = defaultdict(int)
+    for cfgs in census.values():
+        for c in cfgs:
+            per_cfg[c] += 1
     print(f'\nconvolution census: {len(census)} distinct launches')
     for c in sorted(per_cfg):
         print(f'  {c:28s} {per_cfg[c]:4d} distinct launches')
-    for e in sorted(worst):
-        print(f'  worst error / tolerance  {e:42s} {worst[e]:.3g}')
+    failures, missing = _report(sorted(census, key=repr), lambda key: sorted(census[key]))
     assert not missing, f'recorded launches of entry points without a replay adapter: {sorted(missing)}'
-    failures.sort(key=lambda f: -f[0] if f[0] == f[0] else -math.inf)
     assert not failures, '\n'.join(f'{r:.3g} x tol  {e}  {lab}  args={a}  from {cfgs}' for r, e, lab, a, cfgs in failures)
+
+
+# ---------------------------------------------------------------------------------- other batch sizes and the Control plan
+def _of_config(rec, cfg):
+    """The launches of one configuration of record_batches() (labels are '<configuration>/<train|eval>-BN')."""
+    return {key: cfgs for key, cfgs in rec.items() if any(c.rsplit('/', 1)[0] == cfg for c in cfgs)}
+
+
+def _batch_config_names():
+    from tests._launch_census import batch_configs
+    return sorted(batch_configs())
+
+
+@pytest.mark.parametrize('cfg', _batch_config_names())
+def test_batch_recording_matches_float64(cfg):
+    """The launch plans of the family are functions of B * H * W and of tile counts, and the census above records every
+    configuration at batch 2: here batch 3 and 12 (6 and 24 images through the two-view pass), 16-bit storage at batch 3 and the
+    Control plan (one backbone pass, one statistics group) at batch 8, every launch through the same replay and tolerances."""
+    from tests._launch_census import batch_configs, record_batches
+    storage, size, _, _, variant, batch = batch_configs()[cfg]
+    every = _of_config(record_batches(), cfg)
+    mine = {key: cfgs for key, cfgs in every.items() if _is_conv_launch(key[1])}
+    conv3 = [(n, a) for (_, n, a) in mine if n.startswith('pp_conv3x3_')]
+    images = {_geom(n, a)[0] for n, a in conv3}
+    groups = {a[20] if 'wino' in n else a[18] for n, a in conv3 if n.startswith(('pp_conv3x3_fwd_bn', 'pp_conv3x3_wino_fwd_bn'))}
+    print(f'\n{cfg}: {len(mine)} distinct convolution launches, images {sorted(images)}, statistics groups {sorted(groups)}')
+    # not vacuous: the image counts this batch size gives, the weight-gradient families, the BatchNorm backward beside them
+    if variant == 'control':
+        assert batch in images and 2 * batch not in images and groups == {1}, (images, groups)
+    else:
+        assert 2 * batch in images and 2 in groups, (images, groups)
+    for prefix in ('pp_conv3x3_bwd_weight', 'pp_conv3x3_wino_bwd_weight'):
+        assert any(n.startswith(prefix) for n, _ in conv3), prefix
+    assert any(key[1].startswith('pp_bn_lrelu_bwd') for key in every)
+    assert all(key[0] == storage for key in mine if key[1].startswith('pp_conv3x3_')), cfg
+    failures, missing = _report(sorted(mine, key=repr), lambda key: sorted(mine[key]))
+    assert not missing, f'recorded launches of entry points without a replay adapter: {sorted(missing)}'
+    assert not failures, '\n'.join(f'{r:.3g} x tol  {e}  {lab}  args={a}  from {cfgs}' for r, e, lab, a, cfgs in failures)
+
+
+# ------------------------------------------------------------------------------------------------- launch plans at their edges
+# Hand-made launch shapes through the same adapters, at the sizes where the launch plans of the family change state: the number
+# of reduction splits, an uneven last split, a partial last chunk / segment / wave, tile walkers that get no tile.  Every
+# weight-gradient row names the state it is there for and asserts it through the library's plan queries first
+# (pp_conv3x3_bwd_weight_plan, pp_conv3x3_wino_bwd_weight_plan, pp_convtranspose_bwd_weight_splits: the launchers' own plan
+# functions), so that a row whose plan drifted fails instead of testing something else.  Forward, BatchNorm-epilogue and data-gradient
+# rows are generated from the geometries of ALL 3x3 weight-gradient rows, in the family convop.select picks, and assert that it
+# does.  Operands are a few thousand pixels (the largest tensor of a row stays below 64 MB; the workspace is whatever the library's
+# own query asks for).
+SLOPE = 0.01
+C4, W9, T32, T64, T128, HALO, HALO21, HALO12 = 1, 2, 3, 4, 5, 6, 7, 8          # PP_WGRAD_PATH_* of include/pacingpseudo_hip.h
+SLABS, PER, LAST, UNITS, LIVE, LAST_PX = range(6)                              # out[] of pp_conv3x3_bwd_weight_plan
+W_BM, W_PER, W_LAST, W_CHUNKS, W_LAST_TILES, W_TILES = range(6)                # out[] of pp_conv3x3_wino_bwd_weight_plan
+MIN_CUS = 8             # the smallest budget pp_set_wgrad_cus accepts
+
+
+def _k_wgrad(name, O_, C, I, B, H, W, dil, acc, lazy_groups=1):
+    a = ('p', O_ + 8, O_, 'p', C + 16, C, I, B, H, W, dil, 'p', acc, 'p', 'sz')
+    if 'f16x3' in name:
+        a += ('p',)
+    if name.endswith('_lazy'):
+        a += (('lazy', C + 8, lazy_groups),)
+    return (name, a + ('p',))
+
+
+def _k_wino_wgrad(name, O_, C, B, H, W, dil, acc, vcached):
+    a = ('p', O_ + 8, O_, 'p', C + 16, C, B, H, W, dil, 'p', acc, 'p' if vcached else None, 'p', 'sz')
+    return (name, a + (('p', 'p') if name.endswith('_f16x3') else ('p',)))
+
+
+def _k_fwd(family, O_, C, B, H, W, dil, acc=0, bias=1):
+    head = ('p', C + 16, C, 'p', 'p' if bias else None, 'p', O_ + 8, O_, B, H, W, dil, acc)
+    if family == 'fp32':
+        return ('pp_conv3x3_fwd', head + ('p',))
+    if family == 'f16x3':
+        return ('pp_conv3x3_fwd_f16x3', head + (None, 'p'))             # (ConvOp.fwd passes no in_amax)
+    return ('pp_conv3x3_wino_fwd_f16x3' if family == 'wino-split' else 'pp_conv3x3_wino_fwd', head + ('p', 'p', 'sz', 'p'))
+
+
+def _k_fwd_bn(family, O_, C, B, H, W, dil, mode, groups=1):
+    head = ('p', C + 16, C, 'p', 'p', 'p', O_ + 8, O_, B, H, W, dil)
+    bn = (mode, None if mode == 1 else 'p', None if mode == 1 else 'p', SLOPE, groups, 'p' if mode == 1 else None, 'sz', 'p')
+    if family in ('fp32', 'f16x3'):
+        return ('pp_conv3x3_fwd_bn', head + (int(family == 'f16x3'), None) + bn + ('p',))
+    return ('pp_conv3x3_wino_fwd_bn', head + (int(family == 'wino-split'), 'p', 'p', 'sz') + bn + ('p',))
+
+
+def _k_bwd_data(family, O_, C, B, H, W, dil, acc):
+    head = ('p', O_ + 8, O_, 'p', 'p', C + 16, C, B, H, W, dil, acc)
+    if family == 'fp32':
+        return ('pp_conv3x3_bwd_data', head + ('p',))
+    if family == 'f16x3':
+        return ('pp_conv3x3_bwd_data_f16x3', head + ('p', 'p'))
+    if family == 'wino':
+        return ('pp_conv3x3_wino_bwd_data', head + ('p', 'sz', 'p'))
+    return ('pp_conv3x3_wino_bwd_data_f16x3', head + ('p', 'sz', 'p', 'p'))
+
+
+def _k_ct(name, Cin, Cout, k, N, H, W, acc=0):
+    ld_x, ld_o = Cin + 4, Cout + 4
+    if name == 'pp_convtranspose_fwd':
+        return (name, ('p', ld_x, Cin, 'p', 'p', ld_o, Cout, k, N, H, W, 'p'))
+    if name == 'pp_convtranspose_bwd_data':
+        return (name, ('p', ld_o, Cout, 'p', 'p', ld_x, Cin, k, N, H, W, acc, 'p'))
+    return (name, ('p', ld_o, Cout, 'p', ld_x, Cin, k, N, H, W, 'p', acc, 'p', 'sz', 'p'))
+
+
+def _family(O_, C, I, H, W, dil):
+    """convop.select's kernel family of a layer (O, C, I = true input channels) at (H, W, dil) with fp32 storage."""
+    if I == C and C >= 256 and O_ >= 64 and H % (2 * dil) == 0 and W % (2 * dil) == 0:
+        return 'wino-split' if (H % (4 * dil) == 0 and W % (4 * dil) == 0 and C % 8 == 0 and O_ % 8 == 0) else 'wino'
+    return 'f16x3' if (I == C and C % 4 == 0 and O_ % 4 == 0 and O_ >= 32) else 'fp32'
+
+
+# Winograd geometries (O, C, B, H, W, dil) -> (tile, splits, {plan field: value}); 256 input channels: where convop.select
+# takes the Winograd family
+WINO_EDGES = {
+    'tile4-bm64-one-split-one-partial-chunk-B1': ((64, 256, 1, 16, 16, 1), 4, 1, {W_BM: 64, W_CHUNKS: 1, W_LAST_TILES: 16}),
+    'tile2-dil2-odd-7x7-tiles-bm64-O192-uneven-split-B3': ((192, 256, 3, 28, 28, 2), 2, 2,
+                                                             {W_BM: 64, W_PER: 10, W_LAST: 9, W_CHUNKS: 19, W_LAST_TILES: 12}),
+    'tile2-dil2-sub-image-6x10-bm128-one-split-B5': ((128, 256, 5, 12, 20, 2), 2, 1, {W_BM: 128, W_CHUNKS: 10, W_LAST_TILES: 12}),
+    'tile4-bm128-uneven-split-partial-chunk-B5': ((128, 256, 5, 44, 44, 1), 4, 2,
+                                                    {W_BM: 128, W_PER: 10, W_LAST: 9, W_CHUNKS: 19, W_LAST_TILES: 29, W_TILES: 605}),
+    'tile4-bm128-two-row-tiles-C264-partial-channel-tile': ((256, 264, 1, 16, 16, 1), 4, 1, {W_BM: 128, W_CHUNKS: 1}),
+    'tile4-dil2-odd-7x7-tiles-bm64-uneven-split-B3': ((64, 256, 3, 56, 56, 2), 4, 2, {W_BM: 64, W_PER: 10, W_LAST: 9, W_LAST_TILES: 12}),
+    'tile4-bm64-O192-uneven-split-half-chunk-B5': ((192, 256, 5, 48, 48, 1), 4, 2,
+                                                     {W_BM: 64, W_PER: 12, W_LAST: 11, W_CHUNKS: 23, W_LAST_TILES: 16}),
+}
+G0 = (3, 20, 28)        # P = 1680: no multiple of any chunk length, W % 32 != 0 (neither wgrad9 nor the halo kernels)
+# ConvTranspose input geometries (N, H, W) -> (splits, pixels per split, pixels in the last split)
+CT_EDGES = {'P4096-one-split': ((1, 64, 64), (1, 4096, 4096)), 'P4097-two-uneven-splits': ((1, 17, 241), (2, 2049, 2048)),
+            'P258064-at-the-64-split-cap-uneven': ((1, 508, 508), (64, 4033, 3985))}
+
+
+def _edge_cases():
+    """[(tag, launch)], {tag: expectation}: ('direct', f16x3, path, {field: value}) / ('wino', geometry, tile, splits, {field:
+    value}) / ('ct', geometry, (splits, per, last)) for weight-gradient rows, ('family', kind, O, C, I, H, W, dil) or ('tile', (H, W, dil),
+    tile) for the rest."""
+    cases, expect, geos = [], {}, {}
+
+    def add(tag, launch, exp):
+        assert tag not in expect, tag
+        cases.append((tag, launch))
+        expect[tag] = exp
+        name, a = launch
+        if name.startswith('pp_conv3x3_wino_bwd_weight'):          # (O, C, I, B, H, W, dil) of every 3x3 weight-gradient row
+            geos[(a[2], a[5], a[5]) + tuple(a[6:10])] = None
+        elif name.startswith('pp_conv3x3_bwd_weight'):
+            geos[(a[2], a[5], a[6]) + tuple(a[7:11])] = None
+    # -- generic direct weight gradient (wgrad_plan)
+    generic = [(32, 32, T32, {PER: 4, LAST: 2, UNITS: 14}), (64, 64, T64, {PER: 7, LAST: 6, UNITS: 27}),
+               (128, 128, T128, {PER: 14, LAST: 11, UNITS: 53}), (64, 96, T32, {PER: 4, LAST: 2, UNITS: 14}),
+               (192, 64, T64, {PER: 7, LAST: 6, UNITS: 27})]
+    for O_, C, path, st in generic:
+        for dil in (1, 2):
+            for acc in ((0, 1) if O_ == C == 32 else (dil - 1,)):
+                add(f'wgrad/tile{(32, 64, 128)[path - T32]}/O{O_}-C{C}/4-splits-uneven-last-16px-chunk/dil{dil}/acc{acc}',
+                    _k_wgrad('pp_conv3x3_bwd_weight', O_, C, C, *G0, dil, acc), ('direct', 0, path, {**st, SLABS: 4, LAST_PX: 16}))
+    add('wgrad/tile32/one-split-partial-last-chunk', _k_wgrad('pp_conv3x3_bwd_weight', 32, 32, 32, 3, 6, 10, 1, 0),
+        ('direct', 0, T32, {SLABS: 1, UNITS: 2, LAST_PX: 52}))
+    add('wgrad/tile32/I_true5-of-Cpad8', _k_wgrad('pp_conv3x3_bwd_weight', 32, 8, 5, *G0, 1, 0), ('direct', 0, T32, {SLABS: 4, LAST_PX: 16}))
+    # -- wgrad9: 64-pixel row segments
+    for (B, H, W), st, what in (((1, 2, 64), {SLABS: 1, UNITS: 2}, 'one-split'),
+                                ((5, 7, 64), {SLABS: 3, PER: 12, LAST: 11, UNITS: 35}, '3-splits-last-11-boundaries-inside-images'),
+                                ((3, 5, 128), {SLABS: 2, PER: 15, LAST: 15, UNITS: 30}, 'two-segments-per-row')):
+        for i, (O_, C) in enumerate(((4, 40), (36, 4), (36, 40), (64, 192))):
+            add(f'wgrad9/{B}x{H}x{W}-{what}/O{O_}-C{C}/acc{i & 1}', _k_wgrad('pp_conv3x3_bwd_weight', O_, C, C, B, H, W, 1, i & 1),
+                ('direct', 0, W9, st))
+    # -- the first layer's four instantiations (Cpad == 4, one input channel)
+    for (B, H, W), st, what in (((1, 4, 4), {SLABS: 1, UNITS: 1, LAST_PX: 16}, 'one-wave-three-idle'),
+                                ((1, 2, 12), {SLABS: 1, UNITS: 2, LAST_PX: 8}, 'two-waves-last-partial'),
+                                ((3, 10, 12), {SLABS: 1, UNITS: 4, LAST_PX: 72}, 'four-waves-last-partial'),
+                                ((3, 6, 16), {SLABS: 1, UNITS: 4, LAST_PX: 48}, 'four-waves-W16-the-16-bit-forward-takes'),
+                                ((5, 18, 20), {SLABS: 2, UNITS: 8, LAST: 4, LAST_PX: 120}, 'two-blocks-eight-waves-last-partial')):
+        for i, O_ in enumerate((16, 32, 48, 64)):
+            add(f'wgrad_c4/{B}x{H}x{W}-{what}/O{O_}/acc{i & 1}', _k_wgrad('pp_conv3x3_bwd_weight', O_, 4, 1, B, H, W, 1, i & 1),
+                ('direct', 0, C4, st))
+    # -- split-fp16 halo walkers, under the default CU budget and the smallest
+    halo = [(32, 32, HALO, 'one-pair'), (64, 32, HALO21, 'two-pair-2x1'), (32, 64, HALO12, 'two-pair-1x2'),
+            (32, 96, HALO12, 'two-pair-1x2-half-empty-C96'), (32, 160, HALO12, 'two-pair-1x2-half-empty-C160')]
+    for (B, H, W), units in (((1, 4, 32), 1), ((3, 12, 96), 27)):
+        for O_, C, path, what in halo:
+            for cus in ('default', 'min'):
+                if cus == 'default':       # every tile its own walker, the other walkers write zeros
+                    st = {UNITS: units, LIVE: units, PER: 1, LAST: 1}
+                else:                       # eight walkers: one tile for walker 0 alone, or 27 tiles as 4, 4, 4, 3 ...
+                    st = {UNITS: units, LIVE: min(units, 8), PER: (units + 7) // 8, LAST: 1 if units == 1 else 3, SLABS: 32 if path == HALO else 8}
+                for name in ('pp_conv3x3_bwd_weight_f16x3', 'pp_conv3x3_bwd_weight_f16x3_lazy'):
+                    acc = int(cus == 'min')
+                    add(f'{name[11:]}/{what}/{B}x{H}x{W}-{units}-tiles/cus-{cus}/acc{acc}', _k_wgrad(name, O_, C, C, B, H, W, 1, acc),
+                        ('direct', 1, path, st))
+    add('bwd_weight_f16x3/H-not-a-multiple-of-4-falls-back-to-fp32-kernels', _k_wgrad('pp_conv3x3_bwd_weight_f16x3', 32, 32, 32, 3, 10, 96, 1, 0),
+        ('direct', 1, T32, {SLABS: 6, PER: 4, LAST: 3, UNITS: 23}))
+    # -- Winograd weight gradient: fp32 on every geometry, the split-fp16 twin on the F(4x4) ones; kept V and own V
+    for what, (g, tile, splits, st) in WINO_EDGES.items():
+        for name in ('pp_conv3x3_wino_bwd_weight',) + (('pp_conv3x3_wino_bwd_weight_f16x3',) if tile == 4 else ()):
+            for vc in (0, 1):
+                add(f'{name[11:]}/{what}/{"kept" if vc else "own"}-V/acc{1 - vc}', _k_wino_wgrad(name, *g, 1 - vc, vc), ('wino', g, tile, splits, st))
+    # -- ConvTranspose weight gradient (ct_splits), with the forward and data gradient of the same geometry
+    for what, (g, plan) in CT_EDGES.items():
+        ch = (4, 4) if plan[0] == 64 else (36, 20)           # the cap row: the narrowest channels that keep the rows aligned
+        for acc in ((0,) if plan[0] == 64 else (0, 1)):
+            add(f'convtranspose_bwd_weight/{what}/acc{acc}', _k_ct('pp_convtranspose_bwd_weight', *ch, 2, *g, acc), ('ct', g, plan))
+        if plan[0] != 64:
+            add(f'convtranspose_fwd/{what}', _k_ct('pp_convtranspose_fwd', *ch, 2, *g), None)
+            add(f'convtranspose_bwd_data/{what}', _k_ct('pp_convtranspose_bwd_data', *ch, 2, *g, 1), None)
+    # -- forward, BatchNorm epilogues and data gradient at EVERY geometry of the weight-gradient rows above, in the family
+    # convop.select picks for it (restated in _family so that the table needs no library while it is collected; every row
+    # asserts that convop.select agrees).  What an entry's argument check refuses is listed in REJECTED, nothing is left out.
+    same = [(_family(*g[:3], *g[4:]),) + g for g in geos]
+    for fam, O_, C, I, B, H, W, dil in same:
+        geo = f'{fam}/O{O_}-C{C}/{B}x{H}x{W}/dil{dil}'
+        exp = ('family', fam, O_, C, I, H, W, dil)
+        add(f'fwd/{geo}', _k_fwd(fam, O_, C, B, H, W, dil), exp)
+        add(f'fwd_bn/{geo}/train-statistics', _k_fwd_bn(fam, O_, C, B, H, W, dil, 1), exp)
+        add(f'fwd_bn/{geo}/eval-epilogue', _k_fwd_bn(fam, O_, C, B, H, W, dil, 2), exp)
+        if I == C:          # (the first layer has no data gradient)
+            for acc in (0, 1):
+                add(f'bwd_data/{geo}/acc{acc}', _k_bwd_data(fam, O_, C, B, H, W, dil, acc), exp)
+    # -- the fp32 Winograd GEMM at an F(4x4) geometry (what convop.select takes there with the split-fp16 GEMMs switched off)
+    for what, g in (('1x16x16/dil1', (64, 256, 1, 16, 16, 1)), ('5x44x44/dil1', (128, 256, 5, 44, 44, 1))):
+        add(f'fwd/wino-fp32-gemm-tile4/O{g[0]}-C{g[1]}/{what}', _k_fwd('wino', *g), ('tile', g[3:], 4))
+        add(f'bwd_data/wino-fp32-gemm-tile4/O{g[0]}-C{g[1]}/{what}/acc1', _k_bwd_data('wino', *g, 1), ('tile', g[3:], 4))
+    # -- shapes an entry's argument check refuses (REJECTED): a dilation-2 image whose half is odd has no Winograd form
+    add('fwd/wino/O64-C256/3x6x10/dil2-rejected', _k_fwd('wino', 64, 256, 3, 6, 10, 2), None)
+    add('bwd_data/wino/O64-C256/3x6x10/dil2-rejected', _k_bwd_data('wino', 64, 256, 3, 6, 10, 2, 0), None)
+    return cases, expect
+
+
+EDGES, EDGE_EXPECT = _edge_cases()
+# (tag, storage) -> error code of the entry's argument check (PP_ERR_ARG = -1, PP_ERR_UNSUPPORTED = -2); no weight-gradient row
+# may be here.  The 16-bit builds of pp_conv3x3_fwd[_bn] have the first-layer kernel only, which wants W % 16 == 0.
+REJECTED = {('fwd/wino/O64-C256/3x6x10/dil2-rejected', 'fp32'): -1, ('bwd_data/wino/O64-C256/3x6x10/dil2-rejected', 'fp32'): -1}
+REJECTED.update({(t, s): -2 for s in ('fp16', 'bf16')
+                 for t in ('fwd/fp32/O16-C4/5x18x20/dil1', 'fwd_bn/fp32/O16-C4/5x18x20/dil1/train-statistics')})
+# one row per path in fp16 and bf16 storage as well (the twin logic of replay()); 16-bit storage has neither the fp32 Winograd
+# forms nor ConvTranspose, and runs the generic plan where fp32 storage runs wgrad9.  The lazy weight-gradient rows stay fp32:
+# 16-bit plans do not take that form (engine.LAZY_HALO_H16), and the twin logic has no reference for it -- the kernel stages
+# y = lrelu(z * scale + shift) as fp16 without ever storing it, the twin's float64 reference sees y unrounded (measured on the
+# 3x12x96 two-pair row: dw 1.7e-4 / 2.3e-4 of the largest gradient in fp16 / bf16 storage, the size of that rounding).
+H16_ROWS = (
+    'wgrad/tile32/O32-C32/4-splits-uneven-last-16px-chunk/dil2/acc1', 'wgrad/tile64/O64-C64/4-splits-uneven-last-16px-chunk/dil1/acc0',
+    'wgrad/tile128/O128-C128/4-splits-uneven-last-16px-chunk/dil2/acc1', 'wgrad9/5x7x64-3-splits-last-11-boundaries-inside-images/O36-C40/acc0',
+    'wgrad_c4/5x18x20-two-blocks-eight-waves-last-partial/O48/acc0', 'bwd_weight_f16x3/one-pair/3x12x96-27-tiles/cus-min/acc1',
+    'bwd_weight_f16x3/two-pair-2x1/3x12x96-27-tiles/cus-default/acc0', 'bwd_weight_f16x3/two-pair-1x2-half-empty-C96/3x12x96-27-tiles/cus-min/acc1',
+    'bwd_weight_f16x3/H-not-a-multiple-of-4-falls-back-to-fp32-kernels',
+    'wino_bwd_weight_f16x3/tile4-bm128-uneven-split-partial-chunk-B5/kept-V/acc0', 'wino_bwd_weight_f16x3/tile4-dil2-odd-7x7-tiles-bm64-uneven-split-B3/own-V/acc1',
+    'fwd/f16x3/O64-C96/3x20x28/dil2', 'fwd_bn/f16x3/O32-C160/3x12x96/dil1/train-statistics', 'fwd_bn/f16x3/O32-C160/3x12x96/dil1/eval-epilogue',
+    'bwd_data/f16x3/O192-C64/3x20x28/dil2/acc1', 'fwd/fp32/O16-C4/5x18x20/dil1', 'fwd_bn/fp32/O16-C4/5x18x20/dil1/train-statistics',
+    'fwd/fp32/O48-C4/3x6x16/dil1', 'fwd_bn/fp32/O48-C4/3x6x16/dil1/train-statistics', 'fwd_bn/fp32/O48-C4/3x6x16/dil1/eval-epilogue',
+    'fwd/wino-split/O128-C256/5x44x44/dil1', 'fwd_bn/wino-split/O64-C256/3x56x56/dil2/train-statistics', 'bwd_data/wino-split/O128-C256/5x44x44/dil1/acc1',
+)
+_EDGE_OF = dict(EDGES)
+EDGE_PARAMS = [(t, l, 'fp32') for t, l in EDGES] + [(t, _EDGE_OF[t], s) for t in H16_ROWS for s in ('fp16', 'bf16')]
+
+
+def _assert_plan(tag, launch, storage):
+    """The state the row's tag names, through the library's plan queries (host-only)."""
+    from types import SimpleNamespace
+    from pacingpseudo_amd import convop
+    from pacingpseudo_amd._lib import lib
+    exp = EDGE_EXPECT[tag]
+    name, a = launch
+    if exp is None:
+        return
+    if exp[0] == 'direct':
+        _, f16x3, path, st = exp
+        O_, C, B, H, W, dil = a[2], a[5], a[7], a[8], a[9], a[10]
+        out = (ctypes.c_int * 6)()
+        got = lib.pp_conv3x3_bwd_weight_plan(O_, C, B, H, W, dil, f16x3, out)
+        assert got == path, f'{tag}: path {got}, expected {path} (plan {list(out)})'
+        assert all(out[i] == v for i, v in st.items()), f'{tag}: plan {list(out)}, expected {st}'
+        if path in (HALO, HALO21, HALO12) and 'cus-default' in tag:
+            walkers = out[SLABS] // 4 if path == HALO else out[SLABS]         # a one-pair walker leaves four slabs
+            assert walkers > out[LIVE], f'{tag}: every one of {walkers} walkers has a tile ({list(out)})'      # idle walkers exist
+    elif exp[0] == 'wino':
+        _, g, tile, splits, st = exp
+        assert (a[2], a[5]) + tuple(a[6:10]) == g
+        out = (ctypes.c_int * 6)()
+        assert lib.pp_conv3x3_wino_tile(*g[3:]) == tile, tag
+        assert lib.pp_conv3x3_wino_bwd_weight_plan(*g, out) == splits == lib.pp_conv3x3_wino_bwd_weight_splits(*g), f'{tag}: {list(out)}'
+        assert all(out[i] == v for i, v in st.items()), f'{tag}: plan {list(out)}, expected {st}'
+    elif exp[0] == 'ct':
+        _, g, plan = exp
+        assert tuple(a[7:10]) == g
+        out = (ctypes.c_int * 2)()
+        assert (lib.pp_convtranspose_bwd_weight_splits(*g, out), out[0], out[1]) == plan, f'{tag}: {list(out)}'
+    elif exp[0] == 'tile':
+        assert lib.pp_conv3x3_wino_tile(*exp[1]) == exp[2], tag
+    else:
+        _, fam, O_, C, I, H, W, dil = exp
+        L = SimpleNamespace(name=tag, cin=I, cin_pad=C, cout=O_, dil=dil, stride=1)
+        sel = convop.select(L, H, W, storage != 'fp32')
+        kind = {'wino': 'wino-split' if sel.split else 'wino'}.get(sel.kind, sel.kind)
+        assert kind == fam, f'{tag}: convop.select takes {sel}, the row is written for {fam}'
+
+
+def test_edge_table_is_well_formed():
+    """REJECTED is explicit and holds no weight-gradient row; every other row has its expectation; every 16-bit row exists."""
+    for tag, storage in REJECTED:
+        assert (tag, _EDGE_OF[tag], storage) in EDGE_PARAMS and 'bwd_weight' not in _EDGE_OF[tag][0] and 'wgrad' not in tag, tag
+    for tag, (name, _) in EDGES:
+        assert name in ADAPTERS, name
+        assert (EDGE_EXPECT[tag] is not None) or (tag, 'fp32') in REJECTED or name in ('pp_convtranspose_fwd', 'pp_convtranspose_bwd_data'), tag
+        if 'bwd_weight' in name:
+            assert EDGE_EXPECT[tag][0] in ('direct', 'wino', 'ct'), tag
+
+
+@pytest.mark.parametrize('tag,launch,storage', EDGE_PARAMS, ids=[f'{t}-{s}' for t, _, s in EDGE_PARAMS])
+def test_edge_launch_matches_float64(tag, launch, storage):
+    """One hand-made launch at a state of its plan, asserted through the plan queries, then replayed against float64 (fp32
+    storage) or the fp32 twin (16-bit storage) at the tolerances of the census."""
+    from pacingpseudo_amd._lib import HipLibraryError, lib
+    prev = lib.pp_get_wgrad_cus()
+    try:
+        if 'cus-min' in tag:
+            lib.pp_set_wgrad_cus(MIN_CUS)
+        _assert_plan(tag, launch, storage)
+        if (tag, storage) in REJECTED:
+            with pytest.raises(HipLibraryError) as e:
+                replay((storage,) + launch)
+            assert f'rc={REJECTED[(tag, storage)]})' in str(e.value), str(e.value)
+            return
+        res = replay((storage,) + launch)
+    finally:
+        lib.pp_set_wgrad_cus(prev)
+    bad = [(lab, r) for lab, r in res if not r <= 1.0]
+    print(f'{tag} [{storage}] {launch[0]}: worst error / tolerance {max(r for _, r in res):.3g}')
+    assert not bad, f'{tag} [{storage}] args={launch[1]}: ' + ', '.join(f'{lab} {r:.3g} x tol' for lab, r in bad)
+
+
+# ------------------------------------------------------------------------------------------------------ the gate bites
+class _Planted:
+    """An entry-point table that calls ONE entry point wrongly (`wrong(fn, args)` makes the call), everything else unchanged."""
+
+    def __init__(self, inner, name, wrong):
+        self._inner, self._name, self._wrong = inner, name, wrong
+
+    def __getattr__(self, n):
+        fn = getattr(self._inner, n)
+        if n != self._name:
+            return fn
+        return lambda *a: self._wrong(fn, list(a))
+
+
+def _set(i, value):
+    def wrong(fn, a):
+        a[i] = value
+        return fn(*a)
+    return wrong
+
+
+def _i_true_is_cpad(fn, a):
+    """pp_conv3x3_bwd_weight with I_true = Cpad: the gradient in the (O, Cpad, 3, 3) layout.  It goes to a buffer of that size;
+    the caller's (O, I, 3, 3) buffer receives what it would have held (the leading O * I * 9 floats): nothing is written outside."""
+    from pacingpseudo_amd._lib import lib
+    O_, Cpad, I = a[2], a[5], a[6]
+    big = torch.zeros(O_ * Cpad * 9, device=_dev())
+    dw, a[6], a[11] = a[11], Cpad, big.data_ptr()
+    rc = fn(*a)
+    n = O_ * I * 9
+    lib.pp_copy_slab(big.data_ptr(), n, dw, n, n, 1, 0, a[-1])
+    torch.cuda.synchronize()
+    return rc
+
+
+def _other_x(fn, a):
+    """the Winograd forward that fills the kept V, run on another tensor of the same extent"""
+    B, H, W = a[8], a[9], a[10]
+    other = torch.randn(B * H * W * a[1], generator=torch.Generator().manual_seed(5)).to(_dev())
+    a[0] = other.data_ptr()
+    rc = fn(*a)
+    torch.cuda.synchronize()
+    return rc
+
+
+def _stale_amax(fn, a):
+    """max |dz| of an earlier, 2^8 times smaller dz: the split-fp16 operands leave the fp16 range"""
+    from pacingpseudo_amd._lib import lib
+    lib.pp_scale(a[-2], 1, 2.0 ** -8, a[-1])
+    rc = fn(*a)
+    lib.pp_scale(a[-2], 1, 2.0 ** 8, a[-1])
+    return rc
+
+
+PLANTS = {
+    # tag of an edge row, entry point called wrongly, how, labels that must leave the tolerance; every planted call stays inside
+    # the buffers the adapter allocated
+    'accumulate-flipped': ('wgrad/tile32/O32-C32/4-splits-uneven-last-16px-chunk/dil1/acc1', 'pp_conv3x3_bwd_weight', _set(12, 0), ('dw',)),
+    'dilation-2-run-as-1': ('fwd/f16x3/O32-C32/3x20x28/dil2', 'pp_conv3x3_fwd_f16x3', _set(11, 1), ('y',)),
+    'I_true-passed-as-Cpad': ('wgrad_c4/5x18x20-two-blocks-eight-waves-last-partial/O16/acc0', 'pp_conv3x3_bwd_weight', _i_true_is_cpad, ('dw',)),
+    'kept-V-of-another-x': ('wino_bwd_weight/tile4-bm64-one-split-one-partial-chunk-B1/kept-V/acc0', 'pp_conv3x3_wino_fwd', _other_x, ('dw',)),
+    'dz_amax-stale-by-2^8': ('bwd_weight_f16x3/one-pair/3x12x96-27-tiles/cus-default/acc0', 'pp_conv3x3_bwd_weight_f16x3', _stale_amax, ('dw',)),
+    'weight-pack-of-the-other-tile': ('fwd/wino-fp32-gemm-tile4/O64-C256/1x16x16/dil1', 'pp_wino_pack_weights', _set(3, 2), ('y',)),
+}
+
+
+@pytest.mark.parametrize('plant', sorted(PLANTS))
+def test_planted_mistake_fails_the_replay(plant):
+    """The same replay with an entry-point table that makes one mistake must leave the tolerance on the named label (NaN counts,
+    as it does in the gate); with the honest table the same launch passes."""
+    from pacingpseudo_amd._lib import lib
+    tag, entry, wrong, must_fail = PLANTS[plant]
+    key = ('fp32',) + _EDGE_OF[tag]
+    honest = dict(replay(key))
+    assert all(r <= 1.0 for r in honest.values()), honest
+    planted = dict(replay(key, table=_Planted(lib, entry, wrong)))
+    for label in must_fail:
+        assert not planted[label] <= 1.0, (plant, label, planted)

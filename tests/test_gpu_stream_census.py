@@ -1115,6 +1115,30 @@ def test_every_recorded_stream_launch_matches_float64(census):
     assert not failures, '\n'.join(f'{r:.3g} x tol  {e}  {lab}  args={a}  from {cfgs}' for r, e, lab, a, cfgs in failures)
 
 
+def _batch_config_names():
+    from tests._launch_census import batch_configs
+    return sorted(batch_configs())
+
+
+@pytest.mark.parametrize('cfg', _batch_config_names())
+def test_batch_recording_matches_float64(cfg):
+    """The other half of test_batch_recording_matches_float64 of the convolution census: the norm, spatial and loss launches of the
+    batch recordings (batch 3 and 12, 16-bit storage at batch 3, the Control plan at batch 8) through the same replay."""
+    from tests._launch_census import batch_configs, record_batches
+    from tests.test_gpu_conv_census import _of_config
+    variant = batch_configs()[cfg][4]
+    mine = {key: cfgs for key, cfgs in _of_config(record_batches(), cfg).items() if not _is_conv_launch(key[1])}
+    at = {'pp_bn_lrelu_bwd': 18, 'pp_bn_lrelu_bwd_amax': 18, 'pp_bn_lrelu_bwd_pool': 22}       # where the statistics groups stand
+    groups = {a[at[n]] for (_, n, a) in mine if n in at}
+    print(f'\n{cfg}: {len(mine)} distinct stream launches, statistics groups of the train-mode BatchNorm backward {sorted(groups)}')
+    # not vacuous: the BatchNorm backward is there, in two statistics groups (weak and strong view) or, in the Control plan, one
+    assert any(n.startswith('pp_bn_lrelu_bwd') for (_, n, _) in mine), sorted({k[1] for k in mine})
+    assert (groups == {1}) if variant == 'control' else (2 in groups), (cfg, groups)
+    failures, missing = _report(sorted(mine, key=repr), lambda key: sorted(mine[key]))
+    assert not missing, f'recorded launches of entry points neither census owns: {sorted(missing)}'
+    assert not failures, '\n'.join(f'{r:.3g} x tol  {e}  {lab}  args={a}  from {cfgs}' for r, e, lab, a, cfgs in failures)
+
+
 # ------------------------------------------------------------------------------------------------- launches the network never makes
 def _bil(name, C, N, Hi, Wi, Ho, Wo, acc=0):
     if name == 'pp_bilinear_fwd':

@@ -626,6 +626,27 @@ int pp_tta_finalize(float* acc, int N, int K, int H, int W, int views, int64_t* 
 int pp_surface_reduce(const float* dist, const int* counts, int items, int cap, double percentile, float tolerance,
                       double* out, void* stream);
 
+/* Mean-field CRF refinement of a soft-max at inference, with an image-dependent pairwise term (this implementation's addition: the
+ * reference scores its raw arg-max, inference.py:159-190).  logits (N,K,H,W), image (N,C,H,W), fp32.  With
+ * j = i + (dy, dx) * dilation, dy, dx in [-radius, radius] \ (0, 0), j inside the image (a pixel outside adds nothing, also not to
+ * the normalisers), dy and dx counted in window steps as in pp_crf_loss_fwd:
+ *   kb_ij = exp(-(dy^2 + dx^2) / (2 sigma_xy^2)) * exp(-|x_i - x_j|^2 / (2 sigma_rgb^2)),  ks_ij = exp(-(dy^2 + dx^2) / (2 sigma_smooth^2))
+ *   Q^0 = softmax(logits),  u = log_softmax(logits),  Sb_i = sum_j kb_ij,  Ss_i = sum_j ks_ij
+ *   Q^{t+1}_i = softmax_c(u_ic + w_bilateral (sum_j kb_ij Q^t_jc) / (Sb_i + 1e-6) + w_smooth (sum_j ks_ij Q^t_jc) / (Ss_i + 1e-6))
+ * (Potts compatibility, normalised messages: the weights are in logit units; every pixel updates from Q^t.)  prob (N,K,H,W)
+ * receives Q^iterations; cls (N,H,W), unless null, the first-maximum arg-max of prob as it is stored.  One launch per iteration,
+ * ping-pong between prob and the workspace (pp_crf_refine_workspace(N, K, H, W) bytes, required for every iteration count; it need
+ * not be cleared) so that the result lands in prob whatever the parity; Q^0 is never stored.  No atomics and no dependence on the
+ * launch grid: the same bits in every run, and per slice the same bits whatever the batch around it.  No host synchronisation.
+ * Refused with a status and pp_last_error() before anything is enqueued: null logits / image / prob / workspace, N > 65535,
+ * H > 262140, K outside 1 .. 32, C outside 1 .. 4, K H W >= 2^31, iterations outside 1 .. 64, radius outside 1 .. 8, dilation outside
+ * 1 .. 4, radius * dilation > 16, a sigma that is not positive and finite, a weight that is negative or not finite, a workspace that
+ * is too small, prob / workspace / cls overlapping each other or (prob, workspace) an input. */
+size_t pp_crf_refine_workspace(int N, int K, int H, int W);
+int pp_crf_refine(const float* logits, const float* image, int N, int K, int C, int H, int W, int iterations, int radius,
+                  int dilation, float sigma_xy, float sigma_rgb, float sigma_smooth, float w_bilateral, float w_smooth,
+                  float* prob, int64_t* cls, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser (torch.optim.Adam(lr, weight_decay) at train_chaos.py:219) ------------------------------- */
 int pp_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                  float eps, float weight_decay, int step, void* stream);

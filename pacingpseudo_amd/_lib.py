@@ -182,6 +182,8 @@ _PROTOS = {
     'pp_tta_accumulate': (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     'pp_tta_finalize': (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
     'pp_surface_reduce': (i32, [vp, vp, i32, i32, C.c_double, f32, vp, vp]),
+    'pp_crf_refine_workspace': (sz, [i32, i32, i32, i32]),
+    'pp_crf_refine': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, sz, vp]),
     'pp_adam_step': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp]),
     'pp_sgd_momentum_step': (i32, [vp, vp, vp, i64, f32, f32, f32, i32, vp]),
     'pp_channel_scale': (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),

@@ -1,8 +1,9 @@
 // Post-processing of hard class maps on the device: connected-component labelling and the keep-largest-component filter of an
 // evaluation pipeline (include/pacingpseudo_hip.h; DESIGN.md section 7, "Largest-component filter").  The reference scores its raw
 // arg-max (inference.py:159-190); class maps are integers, so there is one build of this file in every storage mode.  The second
-// half of the file holds the test-time-augmentation kernels (views, soft-max accumulation, finalize) on the fp32 logits, the end
-// the reduction of the surface-distance sets to the numbers HD, ASSD, surface Dice and a percentile distance are made of.
+// half of the file holds the test-time-augmentation kernels (views, soft-max accumulation, finalize) on the fp32 logits, then
+// the reduction of the surface-distance sets to the numbers HD, ASSD, surface Dice and a percentile distance are made of, the end
+// the mean-field CRF refinement of the soft-max (one launch per iteration on the fp32 logits and the image).
 //
 // Two pixels of one image are connected when they are neighbours (4- or 8-neighbourhood) and hold the same value.  The label of a
 // pixel is the smallest row-major index of its component, so the result is unique.  Structure: a union-find forest over pixel
@@ -792,4 +793,280 @@ extern "C" int pp_surface_reduce(const float* dist, const int* counts, int items
   hipLaunchKernelGGL(surface_reduce_kernel, dim3(items), dim3(SR_THREADS), 0, s, dist, counts, cap, percentile / 100.0, tolerance, out);
   pp_prof_end(s);
   return pp_launch_status("surface_reduce");
+}
+
+// ================================================================================================================================
+// Mean-field CRF refinement of a soft-max with an image-dependent pairwise term (include/pacingpseudo_hip.h; DESIGN.md section 7,
+// "CRF refinement").  With j = i + (dy, dx) * d, dy, dx in [-r, r] \ (0, 0), j inside the image:
+//   kb_ij = exp(-(dy^2 + dx^2) / (2 sxy^2)) * exp(-|x_i - x_j|^2 / (2 srgb^2)),  ks_ij = exp(-(dy^2 + dx^2) / (2 ssm^2))
+//   Q^{t+1}_i = softmax_c(u_ic + wb (sum_j kb_ij Q^t_jc) / (sum_j kb_ij + 1e-6) + ws (sum_j ks_ij Q^t_jc) / (sum_j ks_ij + 1e-6))
+// with Q^0 = softmax(logits) and u = log_softmax(logits); the soft-max does not see a per-pixel shift, so the kernel adds the
+// message to the logits themselves.
+//   crf_refine_kernel   one launch per iteration: Q^t (iteration 0: the logits) -> Q^{t+1}; the last launch also writes cls
+// The tile, the halo and the LDS layout are crf_fwd_kernel's (pp_loss.hip): a block of four waves owns a 64 x 4 tile, one pixel per
+// lane, and stages tile + halo r*d pixel-major with an odd row length: a chunk of KC classes of Q^t (iteration 0: the soft-max of
+// the logits with the full-K normaliser, formed while staging, so Q^0 never reaches memory), the image channels and a 1 / 0 plane
+// "inside the image" (an outside j adds nothing, also not to the normalisers).  Every lane walks the (2r+1)^2 offsets ONCE for both
+// kernels: the intensity factor is one exp2 of the staged channel differences, the two position factors are products of the 1-D
+// Gaussians of a table that arrives with the launch arguments (uniform over the wave: scalar loads), and Gb[c], Gs[c], Sb, Ss stay
+// in registers.  K <= KC: the lane forms the soft-max of its K values in registers and writes Q^{t+1}.  K > KC runs in class chunks
+// (restage, walk again, k recomputed: the same additions in the same order, so Sb and Ss are the same bits in every chunk): the lane
+// writes logit + message per chunk to the output and normalises over all K at the end from the addresses it wrote itself.
+// Each output element is written by one lane from values of its own slice, added in the order of the walk, and a staged zero leaves
+// an accumulator as it is: no atomics, no dependence on the grid -- the same bits in every run and, per slice, in every batch.
+// The limits below are pp_crf_loss_fwd's (pp_loss.hip: CRF_*).
+#define CRR_TW 64
+#define CRR_TH 4
+#define CRR_THREADS (CRR_TW * CRR_TH)
+#define CRR_MAXR 8
+#define CRR_MAXD 4
+#define CRR_MAXHALO 16
+#define CRR_MAXC 4
+#define CRR_KC 8                         // largest class chunk
+#define CRR_MAXITER 64
+#define CRR_LDS_MAX (160 * 1024 - 256)
+#define CRR_EPS 1e-6f
+
+struct CrrTable {                        // 1-D position factors of the offsets -r .. r at index dy + r: bilateral (sigma_xy), smoothness
+  float b[2 * CRR_MAXR + 1];
+  float s[2 * CRR_MAXR + 1];
+};
+
+static inline size_t crr_lds_bytes(int P, int halo) {
+  return (size_t)(CRR_TW + 2 * halo) * (CRR_TH + 2 * halo) * P * sizeof(float);
+}
+
+__device__ __forceinline__ void crr_softmax_norm(const float* __restrict__ zq, int K, int HW, float& mx, float& inv) {
+  mx = -INFINITY;
+  for (int k = 0; k < K; ++k) mx = fmaxf(mx, zq[(size_t)k * HW]);
+  float s = 0.f;
+  for (int k = 0; k < K; ++k) s += expf(zq[(size_t)k * HW] - mx);
+  inv = 1.f / s;
+}
+
+// z: logits [N][K][H][W]; qin: Q^t, null in iteration 0; qout: Q^{t+1} (never qin or z); cls: null but in the last launch
+template <int KC, int CT>                // CT: image channels (1 or 3), 0: any count up to CRR_MAXC at run time
+__global__ __launch_bounds__(CRR_THREADS) void crf_refine_kernel(
+    const float* __restrict__ z, const float* __restrict__ qin, const float* __restrict__ img, int K, int C, int H, int W, int r, int d,
+    float a_rgb, float wb, float ws, int nchunks, CrrTable tab, float* __restrict__ qout, long long* __restrict__ cls) {
+  extern __shared__ float crr_lds[];
+  constexpr int NC = CT ? CT : CRR_MAXC, P = (KC + NC + 1) | 1;      // floats per staged pixel: [0, KC) q, [KC, KC + NC) x, [KC + NC] inside
+  const int R = r * d, LW = CRR_TW + 2 * R, LH = CRR_TH + 2 * R, HW = H * W;
+  const int n = blockIdx.z, x0 = blockIdx.x * CRR_TW, y0 = blockIdx.y * CRR_TH;
+  const float* zn = z + (size_t)n * K * HW;
+  const float* qn = qin ? qin + (size_t)n * K * HW : nullptr;
+  const float* xn = img + (size_t)n * C * HW;
+  const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
+  const int gx = x0 + lx, gy = y0 + ly, q = gy * W + gx;
+  const bool inside = gx < W && gy < H;
+  float* on = qout + (size_t)n * K * HW + q;                         // dereferenced by inside lanes only
+  const float* ci = crr_lds + ((ly + R) * LW + lx + R) * P;          // this lane's own pixel
+  for (int ch = 0; ch < nchunks; ++ch) {
+    const int c0 = ch * KC;
+    if (ch) __syncthreads();                                         // every lane is through with the previous chunk
+    for (int s = threadIdx.x; s < LW * LH; s += CRR_THREADS) {
+      const int sy = s / LW, sx = s - sy * LW;
+      const int py = y0 - R + sy, px = x0 - R + sx;
+      float* o = crr_lds + s * P;
+      if (px >= 0 && px < W && py >= 0 && py < H) {
+        const int sq = py * W + px;
+        if (qn) {
+#pragma unroll
+          for (int c = 0; c < KC; ++c) o[c] = c0 + c < K ? qn[(size_t)(c0 + c) * HW + sq] : 0.f;
+        } else if (nchunks == 1) {                                   // K <= KC: one load per logit
+          float v[KC];
+          float mx = -INFINITY;
+#pragma unroll
+          for (int c = 0; c < KC; ++c) { v[c] = c < K ? zn[(size_t)c * HW + sq] : -INFINITY; mx = fmaxf(mx, v[c]); }
+          float sum = 0.f;
+#pragma unroll
+          for (int c = 0; c < KC; ++c) { v[c] = c < K ? expf(v[c] - mx) : 0.f; sum += v[c]; }
+          const float inv = 1.f / sum;
+#pragma unroll
+          for (int c = 0; c < KC; ++c) o[c] = v[c] * inv;
+        } else {
+          float mx, inv;
+          crr_softmax_norm(zn + sq, K, HW, mx, inv);
+#pragma unroll
+          for (int c = 0; c < KC; ++c) o[c] = c0 + c < K ? expf(zn[(size_t)(c0 + c) * HW + sq] - mx) * inv : 0.f;
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) o[KC + c] = c < C ? xn[(size_t)c * HW + sq] : 0.f;
+        o[KC + NC] = 1.f;
+      } else {
+#pragma unroll
+        for (int c = 0; c < KC + NC + 1; ++c) o[c] = 0.f;
+      }
+    }
+    __syncthreads();
+    float xi[NC], Gb[KC], Gs[KC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) xi[c] = ci[KC + c];
+#pragma unroll
+    for (int c = 0; c < KC; ++c) { Gb[c] = 0.f; Gs[c] = 0.f; }
+    float Sb = 0.f, Ss = 0.f;
+    for (int dy = -r; dy <= r; ++dy) {
+      const float* row = ci + dy * d * LW * P;
+      const float tb = tab.b[dy + r], ts = tab.s[dy + r];
+#pragma unroll 2
+      for (int dx = -r; dx <= r; ++dx) {
+        const float* cj = row + dx * d * P;
+        float e = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { const float t = xi[c] - cj[KC + c]; e = __builtin_fmaf(t * t, a_rgb, e); }
+        const float mj = cj[KC + NC] * ((dy | dx) ? 1.f : 0.f);      // (0, 0) is no neighbour: its plane value times a uniform 0
+        const float kb = __builtin_amdgcn_exp2f(e) * (mj * (tb * tab.b[dx + r]));
+        const float ks = mj * (ts * tab.s[dx + r]);
+        Sb += kb;
+        Ss += ks;
+#pragma unroll
+        for (int c = 0; c < KC; ++c) {
+          Gb[c] = __builtin_fmaf(kb, cj[c], Gb[c]);
+          Gs[c] = __builtin_fmaf(ks, cj[c], Gs[c]);
+        }
+      }
+    }
+    const float fb = wb / (Sb + CRR_EPS), fs = ws / (Ss + CRR_EPS);
+    if (inside) {
+      if (nchunks == 1) {
+        float v[KC];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < KC; ++c) {
+          v[c] = c < K ? zn[(size_t)c * HW + q] + __builtin_fmaf(Gb[c], fb, Gs[c] * fs) : -INFINITY;
+          mx = fmaxf(mx, v[c]);
+        }
+        float sum = 0.f;
+#pragma unroll
+        for (int c = 0; c < KC; ++c) { v[c] = c < K ? expf(v[c] - mx) : 0.f; sum += v[c]; }
+        const float inv = 1.f / sum;
+        float best = -1.f;
+        int arg = 0;
+#pragma unroll
+        for (int c = 0; c < KC; ++c)
+          if (c < K) {
+            const float p = v[c] * inv;
+            on[(size_t)c * HW] = p;
+            if (p > best) { best = p; arg = c; }                     // the first maximum of the values as they are stored
+          }
+        if (cls) cls[(size_t)n * HW + q] = arg;
+      } else {
+#pragma unroll
+        for (int c = 0; c < KC; ++c)
+          if (c0 + c < K) on[(size_t)(c0 + c) * HW] = zn[(size_t)(c0 + c) * HW + q] + __builtin_fmaf(Gb[c], fb, Gs[c] * fs);
+      }
+    }
+  }
+  if (inside && nchunks > 1) {
+    // same lane, same addresses as the stores above: logit + message of all K classes -> their soft-max
+    float mx = -INFINITY;
+    for (int k = 0; k < K; ++k) mx = fmaxf(mx, on[(size_t)k * HW]);
+    float sum = 0.f;
+    for (int k = 0; k < K; ++k) sum += expf(on[(size_t)k * HW] - mx);
+    const float inv = 1.f / sum;
+    float best = -1.f;
+    int arg = 0;
+    for (int k = 0; k < K; ++k) {
+      const float p = expf(on[(size_t)k * HW] - mx) * inv;
+      on[(size_t)k * HW] = p;
+      if (p > best) { best = p; arg = k; }
+    }
+    if (cls) cls[(size_t)n * HW + q] = arg;
+  }
+}
+
+struct CrrCall {
+  const float* logits; const float* image; int N, K, C, H, W, iterations, radius, dilation;
+  float a_rgb, wb, ws; int nchunks; size_t lds; CrrTable tab; float* prob; long long* cls; float* work; hipStream_t s;
+};
+
+// Ping-pong between prob and the workspace so that the last launch (t = T - 1) writes prob: launch t writes prob when T - 1 - t is even.
+template <int KC, int CT>
+static void crr_run(const CrrCall& a) {
+  auto kern = crf_refine_kernel<KC, CT>;
+  pp_max_lds(reinterpret_cast<const void*>(kern), CRR_LDS_MAX);
+  const dim3 grid(pp_cdiv(a.W, CRR_TW), pp_cdiv(a.H, CRR_TH), a.N);
+  const float* src = nullptr;
+  for (int t = 0; t < a.iterations; ++t) {
+    float* dst = ((a.iterations - 1 - t) & 1) ? a.work : a.prob;
+    hipLaunchKernelGGL(kern, grid, dim3(CRR_THREADS), a.lds, a.s, a.logits, src, a.image, a.K, a.C, a.H, a.W, a.radius, a.dilation, a.a_rgb,
+                       a.wb, a.ws, a.nchunks, a.tab, dst, t == a.iterations - 1 ? a.cls : nullptr);
+    src = dst;
+  }
+}
+template <int KC>
+static void crr_by_channels(const CrrCall& a) {
+  if (a.C == 1) crr_run<KC, 1>(a);
+  else if (a.C == 3) crr_run<KC, 3>(a);
+  else crr_run<KC, 0>(a);
+}
+
+extern "C" size_t pp_crf_refine_workspace(int N, int K, int H, int W) {
+  if (N < 1 || K < 1 || H < 1 || W < 1) return 0;
+  return (size_t)N * K * H * W * sizeof(float);
+}
+
+static inline bool crr_disjoint(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+  return p + na <= q || q + nb <= p;
+}
+
+extern "C" int pp_crf_refine(const float* logits, const float* image, int N, int K, int C, int H, int W, int iterations, int radius,
+                             int dilation, float sigma_xy, float sigma_rgb, float sigma_smooth, float w_bilateral, float w_smooth,
+                             float* prob, int64_t* cls, void* workspace, size_t workspace_bytes, void* stream) {
+  PP_CHECK_ARG(logits && image && prob && workspace, "crf_refine: null pointer");
+  // (N and the rows of tiles are grid.z and grid.y: 65535 each)
+  PP_CHECK_ARG(N >= 1 && N <= 65535 && H >= 1 && H <= 65535 * CRR_TH && W >= 1, "crf_refine: N=%d (1..65535) H=%d (1..%d) W=%d", N, H,
+               65535 * CRR_TH, W);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && C >= 1 && C <= CRR_MAXC, "crf_refine: K=%d (1..%d) C=%d (1..%d)", K, PP_MAXK, C, CRR_MAXC);
+  PP_CHECK_ARG((long long)H * W * K < 0x7fffffffLL, "crf_refine: K*H*W must be below 2^31");
+  PP_CHECK_ARG(iterations >= 1 && iterations <= CRR_MAXITER, "crf_refine: iterations=%d (1..%d)", iterations, CRR_MAXITER);
+  PP_CHECK_ARG(radius >= 1 && radius <= CRR_MAXR && dilation >= 1 && dilation <= CRR_MAXD && radius * dilation <= CRR_MAXHALO,
+               "crf_refine: radius=%d (1..%d) dilation=%d (1..%d), radius * dilation <= %d", radius, CRR_MAXR, dilation, CRR_MAXD, CRR_MAXHALO);
+  PP_CHECK_ARG(sigma_xy > 0.f && sigma_rgb > 0.f && sigma_smooth > 0.f && sigma_xy < INFINITY && sigma_rgb < INFINITY && sigma_smooth < INFINITY,
+               "crf_refine: sigma_xy=%g sigma_rgb=%g sigma_smooth=%g (> 0, finite)", (double)sigma_xy, (double)sigma_rgb, (double)sigma_smooth);
+  PP_CHECK_ARG(w_bilateral >= 0.f && w_smooth >= 0.f && w_bilateral < INFINITY && w_smooth < INFINITY,
+               "crf_refine: w_bilateral=%g w_smooth=%g (>= 0, finite)", (double)w_bilateral, (double)w_smooth);
+  const size_t need = pp_crf_refine_workspace(N, K, H, W), img_bytes = (size_t)N * C * H * W * sizeof(float);
+  if (workspace_bytes < need) {
+    pp_set_error("crf_refine: workspace too small (%zu < %zu)", workspace_bytes, need);
+    return PP_ERR_WORKSPACE;
+  }
+  PP_CHECK_ARG(((uintptr_t)workspace & 3) == 0, "crf_refine: workspace must be 4-byte aligned");
+  PP_CHECK_ARG(crr_disjoint(prob, need, logits, need) && crr_disjoint(prob, need, image, img_bytes) && crr_disjoint(prob, need, workspace, need) &&
+                   crr_disjoint(workspace, need, logits, need) && crr_disjoint(workspace, need, image, img_bytes),
+               "crf_refine: prob and workspace must not overlap each other, logits or image");
+  PP_CHECK_ARG(!cls || (crr_disjoint(cls, (size_t)N * H * W * sizeof(int64_t), prob, need) &&
+                        crr_disjoint(cls, (size_t)N * H * W * sizeof(int64_t), workspace, need)),
+               "crf_refine: cls must not overlap prob or workspace");
+  CrrCall a;
+  a.logits = logits; a.image = image; a.N = N; a.K = K; a.C = C; a.H = H; a.W = W; a.iterations = iterations; a.radius = radius; a.dilation = dilation;
+  a.wb = w_bilateral; a.ws = w_smooth; a.prob = prob; a.cls = (long long*)cls; a.work = (float*)workspace; a.s = (hipStream_t)stream;
+  const int halo = radius * dilation, NC = (C == 1 || C == 3) ? C : CRR_MAXC;
+  // class chunks: as few as the LDS bound allows, of equal width (K = 9 -> 5 + 4, not 8 + 1)
+  int nchunks = pp_cdiv(K, CRR_KC), KC = pp_cdiv(K, nchunks);
+  while (crr_lds_bytes((KC + NC + 1) | 1, halo) > CRR_LDS_MAX) { ++nchunks; KC = pp_cdiv(K, nchunks); }
+  a.nchunks = pp_cdiv(K, KC);
+  a.lds = crr_lds_bytes((KC + NC + 1) | 1, halo);
+  a.a_rgb = (float)(-1.4426950408889634 / (2.0 * (double)sigma_rgb * sigma_rgb));
+  for (int i = 0; i < 2 * CRR_MAXR + 1; ++i) {
+    const double o = (double)(i - radius) * (i - radius);
+    const bool used = i <= 2 * radius;
+    a.tab.b[i] = used ? (float)exp(-o / (2.0 * (double)sigma_xy * sigma_xy)) : 0.f;
+    a.tab.s[i] = used ? (float)exp(-o / (2.0 * (double)sigma_smooth * sigma_smooth)) : 0.f;
+  }
+  const double px = (double)N * H * W, nb = (2.0 * radius + 1.0) * (2.0 * radius + 1.0) - 1.0;
+  pp_prof_begin(PP_K_MISC, iterations * px * nb * a.nchunks * (4.0 * KC + 3.0 * C + 8.0), iterations * px * (12.0 * K + 4.0 * C) + 8.0 * px, a.s);
+  switch (KC) {
+    case 1: crr_by_channels<1>(a); break;
+    case 2: crr_by_channels<2>(a); break;
+    case 3: crr_by_channels<3>(a); break;
+    case 4: crr_by_channels<4>(a); break;
+    case 5: crr_by_channels<5>(a); break;
+    case 6: crr_by_channels<6>(a); break;
+    case 7: crr_by_channels<7>(a); break;
+    default: crr_by_channels<8>(a); break;
+  }
+  pp_prof_end(a.s);
+  return pp_launch_status("crf_refine");
 }

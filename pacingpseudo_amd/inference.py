@@ -90,6 +90,41 @@ parser.add_argument('--nsd_tolerance', type=_tolerance_mm, default=2.0, metavar=
                     help='tolerance of the surface Dice of --surface_metrics in millimetres: the share of surface pixels within MM of the other surface')
 
 
+# mean-field CRF refinement of the (TTA-averaged) soft-max before the arg-max (utils/crf_refine.py); the window and
+# the two sigmas of the bilateral kernel carry the training driver's names and defaults (--do_loss_crf)
+parser.add_argument('--crf_refine', type=int, default=0, metavar='T',
+                    help='refine the probabilities with T mean-field CRF iterations on the device before the arg-max (0 = off; 1 .. 64): '
+                         'bilateral (position x image intensity) and smoothness messages over a local window, after --tta and before '
+                         '--keep_largest_cc; eval_data.npz gains crf_changed')
+parser.add_argument('--crf_radius', type=int, default=5, help='neighbourhood radius r: offsets dy, dx in [-r, r] (1 .. 8)')
+parser.add_argument('--crf_dilation', type=int, default=1, help='spacing d of the neighbourhood offsets in pixels (1 .. 4, r * d <= 16)')
+parser.add_argument('--crf_sigma_xy', type=float, default=6.0, help='width of the position factor of the bilateral kernel, in offsets')
+parser.add_argument('--crf_sigma_rgb', type=float, default=0.1, help='width of its intensity factor, in units of the network input')
+parser.add_argument('--crf_sigma_smooth', type=float, default=1.5, help='width of the smoothness kernel, in offsets (an untuned first value)')
+parser.add_argument('--crf_w_bilateral', type=float, default=4.0, help='weight of the bilateral message, in logit units (an untuned first value)')
+parser.add_argument('--crf_w_smooth', type=float, default=1.0, help='weight of the smoothness message, in logit units (an untuned first value)')
+CRF_FLAGS = ('crf_refine', 'crf_radius', 'crf_dilation', 'crf_sigma_xy', 'crf_sigma_rgb', 'crf_sigma_smooth', 'crf_w_bilateral', 'crf_w_smooth')
+
+
+def crf_settings(args):
+    """None with --crf_refine 0, else the checked keyword arguments of utils.crf_refine (ValueError / NotImplementedError)."""
+    from .utils.crf_refine import check_crf_refine_params
+    if getattr(args, 'crf_refine', 0) == 0:
+        return None
+    return check_crf_refine_params(args.crf_refine, args.crf_radius, args.crf_dilation, args.crf_sigma_xy, args.crf_sigma_rgb,
+                                   args.crf_sigma_smooth, args.crf_w_bilateral, args.crf_w_smooth)
+
+
+def parse_args(argv=None):
+    """parser.parse_args plus the checks that span several flags (argparse errors: exit status 2), before anything is built."""
+    args = parser.parse_args(argv)
+    try:
+        crf_settings(args)
+    except (ValueError, NotImplementedError) as e:
+        parser.error(f'--crf_refine / --crf_radius / --crf_dilation / --crf_sigma_* / --crf_w_*: {e}')
+    return args
+
+
 def load_backbone(model, state_dict):
     """inference.py:138-146: a full-model checkpoint is reduced to its `backbone.` entries."""
     from .models.unet import check_checkpoint_norm
@@ -107,7 +142,7 @@ def load_backbone(model, state_dict):
 
 
 def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False, cc_connectivity=1, tta='none', extra=None,
-             surface_metrics=False, nsd_tolerance=2.0):
+             surface_metrics=False, nsd_tolerance=2.0, crf=None):
     """-> (dicearr, hd95arr), both (slices, classes) float32 with NaN where the reference skips a class.  With keep_largest_cc the
     arg-max is filtered on the device first (utils.postprocess.keep_largest_components) and both metrics score the filtered map;
     then -> (dicearr, hd95arr, ncomp, removed): ncomp (slices, classes) int32 = components per class before filtering, removed
@@ -117,13 +152,19 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
     the identity view's arg-max.  With surface_metrics the same hard map is scored by one utils.metrics.batch_surface_metrics call
     per batch instead of batch_hd95: hd95arr is its percentile distance, and `extra` receives hdarr, assdarr and nsdarr (Hausdorff
     distance, average symmetric surface distance, surface Dice at nsd_tolerance mm), each (slices, classes) float32 with NaN as in
-    hd95arr."""
+    hd95arr.  With crf = a dict of utils.crf_refine's keyword arguments (iterations, radius, ...) the logits -- with tta the log of
+    the mean probabilities, clamped at 1e-30 -- are refined against the image before anything else sees them: the refined
+    probabilities and their class map take the place of the logits and their arg-max in the filter and in every metric, and `extra`
+    receives crf_changed: (slices,) int64 = pixels whose class differs from the unrefined arg-max."""
     from .data import expand_compact
     from .utils.metrics import batch_dice_counts, batch_hd95, batch_surface_metrics
     from .utils.postprocess import keep_largest_components
     from .utils.tta import tta_ops, tta_predict
     use_tta = len(tta_ops(tta)) > 1
-    dice_rows, hd_rows, ncomp_rows, removed_rows, changed_rows = [], [], [], [], []
+    if crf is not None:
+        from .utils.crf_refine import check_crf_refine_params, crf_refine
+        crf = check_crf_refine_params(**crf)
+    dice_rows, hd_rows, ncomp_rows, removed_rows, changed_rows, crf_rows = [], [], [], [], [], []
     surf_rows = {'hd': [], 'assd': [], 'nsd': []}
     model.eval()
     for groups in loader:
@@ -143,8 +184,14 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
                     changed_rows.extend((tta_cls != single[0]).flatten(1).sum(1).tolist())
                 else:
                     logits = model(image)['segmentation/logits']
+                if crf is not None:
+                    before = tta_cls if use_tta else logits.argmax(1)
+                    logits, crf_cls = crf_refine(logits.clamp_min(1e-30).log() if use_tta else logits, image, **crf)
+                    crf_rows.extend((crf_cls != before).flatten(1).sum(1).tolist())
+            # the first-maximum arg-max the last stage left beside its probabilities; None: logits.argmax(1), taken where it is needed
+            argmax = crf_cls if crf is not None else (tta_cls if use_tta else None)
             if keep_largest_cc:
-                raw = tta_cls if use_tta else logits.argmax(1)
+                raw = argmax if argmax is not None else logits.argmax(1)
                 pred, stats = keep_largest_components(raw, num_classes, cc_connectivity, return_stats=True)
                 ncomp_rows.extend(stats[..., 0].tolist())
                 removed_rows.extend((pred != raw).flatten(1).sum(1).tolist())
@@ -158,7 +205,7 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
                 dice = 2.0 * inter / np.maximum(ps + ts, 1e-8)             # inference.py:211-213 (no smoothing term here)
             dice[(ps == 0) & (ts == 0)] = np.nan                           # :208-209
             dice_rows.extend(dice.tolist())
-            hard = pred if keep_largest_cc else (tta_cls if use_tta else logits.argmax(1))
+            hard = pred if keep_largest_cc else (argmax if argmax is not None else logits.argmax(1))
             if surface_metrics:
                 sm = batch_surface_metrics(hard, label.argmax(1), num_classes, spacing, tolerance=nsd_tolerance)
                 hd_rows.extend(sm['hdp'].tolist())
@@ -168,6 +215,8 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
                 hd_rows.extend(batch_hd95(hard, label.argmax(1), num_classes, spacing).tolist())
     if use_tta and extra is not None:
         extra['tta_changed'] = np.array(changed_rows, np.int64)
+    if crf is not None and extra is not None:
+        extra['crf_changed'] = np.array(crf_rows, np.int64)
     if surface_metrics and extra is not None:
         for key, rows in surf_rows.items():
             extra[key + 'arr'] = np.array(rows, np.float32).reshape(-1, num_classes)
@@ -201,21 +250,28 @@ def main_interface(args):
     logging.info('Length {}'.format(len(loader)))
     load_backbone(model, torch.load(args.checkpoint_file, map_location=device))
     tta = getattr(args, 'tta', 'none')
-    extra = {}                                             # tta_changed with --tta flips / d4, hdarr / assdarr / nsdarr with --surface_metrics
+    extra = {}                                             # tta_changed with --tta flips / d4, hdarr / assdarr / nsdarr with --surface_metrics, crf_changed with --crf_refine
     surface = dict(surface_metrics=True, nsd_tolerance=args.nsd_tolerance) if getattr(args, 'surface_metrics', False) else {}
+    crf = crf_settings(args)
+    refine = dict(crf=crf) if crf is not None else {}      # without the flag the evaluate call is the parent's
     if args.keep_largest_cc:
-        dicearr, hd95arr, ncomp, removed = evaluate(model, loader, num_classes, spacing, device, True, args.cc_connectivity, tta, extra, **surface)
+        dicearr, hd95arr, ncomp, removed = evaluate(model, loader, num_classes, spacing, device, True, args.cc_connectivity, tta, extra, **surface,
+                                                    **refine)
         np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, ncomp=ncomp, removed=removed, **extra)
         logging.info('Largest-component filter (connectivity {}): {} pixels set to background, {} of {} slices changed'.format(
             args.cc_connectivity, int(removed.sum()), int((removed > 0).sum()), len(removed)))
     else:
-        dicearr, hd95arr = evaluate(model, loader, num_classes, spacing, device, tta=tta, extra=extra, **surface)
+        dicearr, hd95arr = evaluate(model, loader, num_classes, spacing, device, tta=tta, extra=extra, **surface, **refine)
         np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, **extra)
     if tta != 'none':
         from .utils.tta import tta_ops
         changed = extra['tta_changed']
         logging.info('Test-time augmentation ({}, {} views): {} pixels differ from the identity view, {} of {} slices changed'.format(
             tta, len(tta_ops(tta)), int(changed.sum()), int((changed > 0).sum()), len(changed)))
+    if crf is not None:
+        changed = extra['crf_changed']
+        logging.info('CRF refinement ({} iterations, radius {} x dilation {}): {} pixels differ from the unrefined arg-max, {} of {} slices changed'.format(
+            crf['iterations'], crf['radius'], crf['dilation'], int(changed.sum()), int((changed > 0).sum()), len(changed)))
     meter_dice = [AvgMeter() for _ in range(num_classes)]
     meter_hd95 = [AvgMeter() for _ in range(num_classes)]
     for drow, hrow in zip(dicearr, hd95arr):
@@ -246,7 +302,7 @@ def main_interface(args):
 
 
 def main(argv=None):
-    args = parser.parse_args(argv)
+    args = parse_args(argv)
     if 'LOCAL_RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
     random.seed(args.seed)
@@ -277,7 +333,8 @@ def main(argv=None):
     log.addHandler(fh)
     log.addHandler(logging.StreamHandler(sys.stdout))
     # without --surface_metrics the log is what it was before the flag existed: its two entries are left out of the dump
-    shown = [(k, v) for k, v in args._get_kwargs() if args.surface_metrics or k not in ('surface_metrics', 'nsd_tolerance')]
+    shown = [(k, v) for k, v in args._get_kwargs() if (args.surface_metrics or k not in ('surface_metrics', 'nsd_tolerance'))
+             and (args.crf_refine or k not in CRF_FLAGS)]        # the same for --crf_refine and its eight entries
     logging.info(''.join(f'{k}={v}\n' for k, v in shown))
     if not args.synthetic:
         from .train import split_dir                              # the same table the trainers read their fold lists from

@@ -2,3 +2,4 @@ from .utils import AvgMeter, cosine_lr_decay, gaussian_ramp_up, linear_lr_decay,
 from .postprocess import keep_largest_components, label_components  # noqa: F401
 from .tta import TTA_MODES, tta_ops, tta_predict, tta_view  # noqa: F401
 from .metrics import batch_surface_metrics, compute_hd, surface_metrics_from_reduction  # noqa: F401
+from .crf_refine import check_crf_refine_params, crf_refine  # noqa: F401

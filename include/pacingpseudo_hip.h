@@ -571,6 +571,24 @@ int pp_crf_loss_fwd(const float* logits, const float* image, const float* valid_
 int pp_crf_loss_bwd(const float* unit_grad, const double* sums, int has_mask, const float* g_up, float grad_scale,
                     float* dlogits, long long n, void* stream);
 
+/* Normalised cut on the weak-view logits (this implementation's addition), with the kernel, offsets and
+ * accepted ranges of pp_crf_loss_fwd above:
+ *   q_ic = sum_j m_j k_ij p_jc,  d_i = sum_j m_j k_ij,  A_nc = sum_{i in n} m_i p_ic q_ic,  V_nc = sum_{i in n} m_i p_ic d_i,
+ *   NC_nc = 1 - A_nc / V_nc if V_nc > 1e-6, else 0 (an inactive class of that image: no gradient),  L = (1/D) sum_nc NC_nc, D = N K.
+ * pp_nc_loss_fwd writes assoc_vol[n][c] = {A, V} and sums[0] = sum NC_nc, sums[1] = N K (exact) in double, in a fixed order (no
+ * atomics); the loss is sums[0] / sums[1] -- data-parallel callers add `sums` over the ranks first.  With unit_grad (N,K,H,W)
+ * non-NULL a second, streaming pass leaves u_ic = p_ic (G_ic - <p_i, G_i>) there, G_ic = m_i (a_nc q_ic + b_nc d_i), a = -2 / V,
+ * b = A / V^2 (0 for an inactive class);  pp_nc_loss_bwd then ACCUMULATES
+ *   dlogits[e] += grad_scale * g_up[0] * (1 / max(sums[1], 1)) * unit_grad[e],  e < n = N K H W
+ * reading D from `sums` on the device.  The workspace (pp_nc_loss_workspace bytes, 16-byte aligned) holds the per-block
+ * partials, (a, b) and d.  No gradient flows to the image or the mask. */
+size_t pp_nc_loss_workspace(int N, int K, int H, int W);
+int pp_nc_loss_fwd(const float* logits, const float* image, const float* valid_mask, int N, int K, int C, int H, int W,
+                   int radius, int dilation, float sigma_xy, float sigma_rgb, float* unit_grad, double* assoc_vol, double* sums,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int pp_nc_loss_bwd(const float* unit_grad, const double* sums, const float* g_up, float grad_scale, float* dlogits, long long n,
+                   void* stream);
+
 /* Connected components of class maps and the keep-largest-component filter of an evaluation pipeline (this implementation's
  * addition: the reference scores its raw arg-max, inference.py:159-190).  cls: int64 class maps [N][H][W].
  * Two pixels of ONE image are connected when they are neighbours -- the 4-neighbourhood for connectivity 1, the 8-neighbourhood

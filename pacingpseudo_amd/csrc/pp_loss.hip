@@ -1140,6 +1140,48 @@ __device__ __forceinline__ void crf_softmax_norm(const float* __restrict__ zq, i
 }
 __device__ __forceinline__ float crf_prob(float z, float mx, float inv) { return expf(z - mx) * inv; }
 
+// Stage tile + halo of one class chunk [c0, c0 + KC) into LDS, P floats per pixel (CrfLayout); zeros outside the image: the staging
+// loop of crf_fwd_kernel as a function, for the normalised-cut walk further down (crf_fwd_kernel keeps its own copy in line: called
+// from there the compiler schedules that kernel differently, and its code is to stay what it was).
+template <int KC, int CT>
+__device__ __forceinline__ void crf_stage_tile(float* __restrict__ crf_lds, const float* __restrict__ zn, const float* __restrict__ xn,
+                                               const float* __restrict__ mn, int K, int C, int H, int W, int R, int LW, int LH, int x0,
+                                               int y0, int c0, int nchunks) {
+  constexpr int NC = CrfLayout<KC, CT>::NC, P = CrfLayout<KC, CT>::P;
+  const int HW = H * W;
+  for (int s = threadIdx.x; s < LW * LH; s += CRF_THREADS) {
+    const int sy = s / LW, sx = s - sy * LW;
+    const int py = y0 - R + sy, px = x0 - R + sx;
+    float* o = crf_lds + s * P;
+    if (px >= 0 && px < W && py >= 0 && py < H) {
+      const int sq = py * W + px;
+      if (nchunks == 1) {                                        // K <= KC: one load per logit
+        float v[KC];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < KC; ++c) { v[c] = c < K ? zn[(size_t)c * HW + sq] : -INFINITY; mx = fmaxf(mx, v[c]); }
+        float sum = 0.f;
+#pragma unroll
+        for (int c = 0; c < KC; ++c) { v[c] = c < K ? expf(v[c] - mx) : 0.f; sum += v[c]; }
+        const float inv = 1.f / sum;
+#pragma unroll
+        for (int c = 0; c < KC; ++c) o[c] = v[c] * inv;
+      } else {
+        float mx, inv;
+        crf_softmax_norm(zn + sq, K, HW, mx, inv);
+#pragma unroll
+        for (int c = 0; c < KC; ++c) o[c] = c0 + c < K ? crf_prob(zn[(size_t)(c0 + c) * HW + sq], mx, inv) : 0.f;
+      }
+#pragma unroll
+      for (int c = 0; c < NC; ++c) o[KC + c] = c < C ? xn[(size_t)c * HW + sq] : 0.f;
+      o[KC + NC] = mn ? mn[sq] : 1.f;
+    } else {
+#pragma unroll
+      for (int c = 0; c < KC + NC + 1; ++c) o[c] = 0.f;
+    }
+  }
+}
+
 template <int KC, int CT>
 __global__ __launch_bounds__(CRF_THREADS) void crf_fwd_kernel(
     const float* __restrict__ z, const float* __restrict__ img, const float* __restrict__ mask, int K, int C, int H, int W, int r,
@@ -1160,6 +1202,7 @@ __global__ __launch_bounds__(CRF_THREADS) void crf_fwd_kernel(
   for (int ch = 0; ch < nchunks; ++ch) {
     const int c0 = ch * KC;
     if (ch) __syncthreads();                                       // every lane is through with the previous chunk
+    // (this staging loop has a twin, crf_stage_tile above: a change of the LDS layout goes into both)
     for (int s = threadIdx.x; s < LW * LH; s += CRF_THREADS) {
       const int sy = s / LW, sx = s - sy * LW;
       const int py = y0 - R + sy, px = x0 - R + sx;
@@ -1349,6 +1392,282 @@ extern "C" int pp_crf_loss_bwd(const float* unit_grad, const double* sums, int h
                      dlogits, n, n4);
   pp_prof_end(s);
   return pp_launch_status("crf_loss_bwd");
+}
+
+// ---------------------------------------------------------------- normalised cut on the weak-view logits
+//   q_ic = sum_j m_j k_ij p_jc,  d_i = sum_j m_j k_ij   (k, offsets and dilation exactly those of the gated-CRF loss above)
+//   A_nc = sum_{i in n} m_i p_ic q_ic,  V_nc = sum_{i in n} m_i p_ic d_i,  NC_nc = 1 - A_nc / V_nc if V_nc > 1e-6, else 0
+//   L = (1/D) sum_n sum_c NC_nc,  D = N K.  k and m_i m_j are symmetric, so the derivative is a gather once A and V exist:
+//   G_ic = m_i (a_nc q_ic + b_nc d_i), a = -2 / V, b = A / V^2 (0 for an inactive class), dL/dz_ic = (1/D) p_ic (G_ic - <p_i, G_i>).
+// Pass 1 (nc_fwd_kernel) is the CRF walk -- same tile, LDS layout, one-exp2 kernel and class chunks -- that parks q in `unit` and
+// d in the workspace and leaves per-block double partials of m p q and m p d for every class.  nc_reduce_kernel adds the blocks of
+// one image in a fixed order per (n, c); nc_final_kernel forms sum NC and the count, and the fp32 pair (a, b) per (n, c), each
+// formed in double and rounded once.  Pass 2 (nc_grad_kernel) streams: soft-max again, u = p (G - <p, G>) over q in place.  No
+// atomics: the same bits run after run.
+#define NC_V_MIN 1e-6
+
+template <int KC, int CT>
+__global__ __launch_bounds__(CRF_THREADS) void nc_fwd_kernel(
+    const float* __restrict__ z, const float* __restrict__ img, const float* __restrict__ mask, int K, int C, int H, int W, int r,
+    int d, float a_xy, float a_rgb, int nchunks, float* __restrict__ qout /*(N,K,H,W) or null*/, float* __restrict__ dout /*(N,H,W)*/,
+    double* __restrict__ partial /*[blocks][K][2]*/) {
+  extern __shared__ float crf_lds[];
+  constexpr int NC = CrfLayout<KC, CT>::NC, P = CrfLayout<KC, CT>::P;
+  const int R = r * d, LW = CRF_TW + 2 * R, LH = CRF_TH + 2 * R, HW = H * W;
+  const int n = blockIdx.z, x0 = blockIdx.x * CRF_TW, y0 = blockIdx.y * CRF_TH;
+  const float* zn = z + (size_t)n * K * HW;
+  const float* xn = img + (size_t)n * C * HW;
+  const float* mn = mask ? mask + (size_t)n * HW : nullptr;
+  const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
+  const int gx = x0 + lx, gy = y0 + ly, q = gy * W + gx;
+  const bool inside = gx < W && gy < H;
+  const float* ci = crf_lds + ((ly + R) * LW + lx + R) * P;      // this lane's own pixel
+  double* pb = partial + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * K * 2;
+  double* shd = reinterpret_cast<double*>(crf_lds);               // [2 * KC][CRF_TH] wave sums, over the tile once the walk is through
+  float S = 0.f;
+  for (int ch = 0; ch < nchunks; ++ch) {
+    const int c0 = ch * KC;
+    if (ch) __syncthreads();                                       // the block sums of the previous chunk have been read
+    crf_stage_tile<KC, CT>(crf_lds, zn, xn, mn, K, C, H, W, R, LW, LH, x0, y0, c0, nchunks);
+    __syncthreads();
+    float xi[NC], G[KC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) xi[c] = ci[KC + c];
+#pragma unroll
+    for (int c = 0; c < KC; ++c) G[c] = 0.f;
+    float Sc = 0.f;
+    for (int dy = -r; dy <= r; ++dy) {
+      const float* row = ci + dy * d * LW * P;
+#pragma unroll 2
+      for (int dx = -r; dx <= r; ++dx) {
+        const float* cj = row + dx * d * P;
+        float e = (float)(dy * dy + dx * dx) * a_xy;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { const float t = xi[c] - cj[KC + c]; e = __builtin_fmaf(t * t, a_rgb, e); }
+        const float k = __builtin_amdgcn_exp2f(e) * (cj[KC + NC] * ((dy | dx) ? 1.f : 0.f));      // (0, 0) is no neighbour: its mask times a uniform 0
+        Sc += k;
+#pragma unroll
+        for (int c = 0; c < KC; ++c) G[c] = __builtin_fmaf(k, cj[c], G[c]);
+      }
+    }
+    if (ch == 0) {
+      S = Sc;                                                      // d_i: the same walk in every chunk, the first one's is kept
+      if (qout && inside) dout[(size_t)n * HW + q] = S;
+    }
+    if (qout && inside) {
+      float* qn = qout + (size_t)n * K * HW + q;
+#pragma unroll
+      for (int c = 0; c < KC; ++c) if (c0 + c < K) qn[(size_t)(c0 + c) * HW] = G[c];
+    }
+    const float mi = inside ? ci[KC + NC] : 0.f;
+    double a[KC], v[KC];
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+      const float mp = mi * ci[c];
+      a[c] = pp_wave_sum_d((double)(mp * G[c]));
+      v[c] = pp_wave_sum_d((double)(mp * S));
+    }
+    __syncthreads();                                               // every lane is through with the tile: its head holds the wave sums now
+    if (lx == 0) {
+#pragma unroll
+      for (int c = 0; c < KC; ++c) { shd[(2 * c) * CRF_TH + ly] = a[c]; shd[(2 * c + 1) * CRF_TH + ly] = v[c]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * KC && c0 + (threadIdx.x >> 1) < K) {
+      const double* w = shd + threadIdx.x * CRF_TH;
+      pb[(size_t)c0 * 2 + threadIdx.x] = ((w[0] + w[1]) + w[2]) + w[3];
+    }
+  }
+}
+
+// assoc_vol[n][c] = {A, V}: block (n, c) adds that image's blocks, thread t blocks t, t + 256, ... in order, then the butterfly
+__global__ __launch_bounds__(256) void nc_reduce_kernel(const double* __restrict__ partial, int bpi, int K, double* __restrict__ assoc_vol) {
+  __shared__ double sh[2][4];
+  const int n = blockIdx.x / K, c = blockIdx.x - n * K;
+  const double* p = partial + ((size_t)n * bpi * K + c) * 2;
+  double a = 0.0, b = 0.0;
+  for (int i = threadIdx.x; i < bpi; i += 256) { a += p[(size_t)i * K * 2]; b += p[(size_t)i * K * 2 + 1]; }
+  a = pp_wave_sum_d(a);
+  b = pp_wave_sum_d(b);
+  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = a; sh[1][threadIdx.x >> 6] = b; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  assoc_vol[(size_t)blockIdx.x * 2] = ((sh[0][0] + sh[0][1]) + sh[0][2]) + sh[0][3];
+  assoc_vol[(size_t)blockIdx.x * 2 + 1] = ((sh[1][0] + sh[1][1]) + sh[1][2]) + sh[1][3];
+}
+
+// sums[0] = sum NC_nc, sums[1] = N K (a count: exact); coef[n][c] = {a, b} = {-2 / V, A / V^2}, 0 for an inactive class
+__global__ __launch_bounds__(256) void nc_final_kernel(const double* __restrict__ assoc_vol, int NK, float* __restrict__ coef,
+                                                       double* __restrict__ sums) {
+  __shared__ double sh[4];
+  double t = 0.0;
+  for (int i = threadIdx.x; i < NK; i += 256) {
+    const double A = assoc_vol[(size_t)i * 2], V = assoc_vol[(size_t)i * 2 + 1];
+    const bool active = V > NC_V_MIN;
+    if (active) t += 1.0 - A / V;
+    coef[(size_t)i * 2] = active ? (float)(-2.0 / V) : 0.f;
+    coef[(size_t)i * 2 + 1] = active ? (float)(A / (V * V)) : 0.f;
+  }
+  t = pp_wave_sum_d(t);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  sums[0] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+  sums[1] = (double)NK;
+}
+
+// u_ic = p_ic (G_ic - <p_i, G_i>), G_ic = m_i (a_nc q_ic + b_nc d_i), over q in place; V pixels per thread (4: 16-byte accesses)
+template <int V>
+__global__ __launch_bounds__(LS_THREADS) void nc_grad_kernel(const float* __restrict__ z, const float* __restrict__ mask,
+                                                             const float* __restrict__ dws, const float* __restrict__ coef, int K, int HW,
+                                                             float* __restrict__ unit) {
+  struct alignas(4 * V) Vec { float f[V]; };
+  const int n = blockIdx.y, i = blockIdx.x * LS_THREADS + threadIdx.x;
+  if (i >= HW / V) return;
+  const Vec* zn = reinterpret_cast<const Vec*>(z + (size_t)n * K * HW) + i;
+  Vec* un = reinterpret_cast<Vec*>(unit + (size_t)n * K * HW) + i;
+  const float* cf = coef + (size_t)n * K * 2;
+  const int ld = HW / V;
+  const Vec dv = reinterpret_cast<const Vec*>(dws + (size_t)n * HW)[i];
+  Vec mv;
+#pragma unroll
+  for (int j = 0; j < V; ++j) mv.f[j] = 1.f;
+  if (mask) mv = reinterpret_cast<const Vec*>(mask + (size_t)n * HW)[i];
+  float mx[V], sum[V], dot[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) { mx[j] = -INFINITY; sum[j] = 0.f; dot[j] = 0.f; }
+  for (int k = 0; k < K; ++k) {
+    const Vec v = zn[(size_t)k * ld];
+#pragma unroll
+    for (int j = 0; j < V; ++j) mx[j] = fmaxf(mx[j], v.f[j]);
+  }
+  for (int k = 0; k < K; ++k) {
+    const Vec v = zn[(size_t)k * ld];
+#pragma unroll
+    for (int j = 0; j < V; ++j) sum[j] += expf(v.f[j] - mx[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < V; ++j) sum[j] = 1.f / sum[j];
+  for (int k = 0; k < K; ++k) {
+    const Vec v = zn[(size_t)k * ld], qv = un[(size_t)k * ld];
+    const float a = cf[2 * k], b = cf[2 * k + 1];
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+      dot[j] = __builtin_fmaf(crf_prob(v.f[j], mx[j], sum[j]), mv.f[j] * __builtin_fmaf(a, qv.f[j], b * dv.f[j]), dot[j]);
+  }
+  for (int k = 0; k < K; ++k) {
+    const Vec v = zn[(size_t)k * ld], qv = un[(size_t)k * ld];
+    const float a = cf[2 * k], b = cf[2 * k + 1];
+    Vec o;
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+      o.f[j] = crf_prob(v.f[j], mx[j], sum[j]) * (mv.f[j] * __builtin_fmaf(a, qv.f[j], b * dv.f[j]) - dot[j]);
+    un[(size_t)k * ld] = o;
+  }
+}
+
+// dlogits += grad_scale * g_up / max(D, 1) * u: 16-byte accesses, D read on the device (behind the cross-rank reduction of sums)
+__global__ __launch_bounds__(LS_THREADS) void nc_bwd_kernel(const float* __restrict__ unit, const double* __restrict__ sums,
+                                                            const float* __restrict__ g_up, float grad_scale, float* __restrict__ dz,
+                                                            long long n, long long n4) {
+  const float f = (float)((double)(*g_up * grad_scale) / fmax(sums[1], 1.0));
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+  for (long long i = t; i < n4; i += step) {
+    const float4 u = reinterpret_cast<const float4*>(unit)[i];
+    float4 g = reinterpret_cast<float4*>(dz)[i];
+    g.x = __builtin_fmaf(f, u.x, g.x); g.y = __builtin_fmaf(f, u.y, g.y); g.z = __builtin_fmaf(f, u.z, g.z); g.w = __builtin_fmaf(f, u.w, g.w);
+    reinterpret_cast<float4*>(dz)[i] = g;
+  }
+  for (long long i = n4 * 4 + t; i < n; i += step) dz[i] = __builtin_fmaf(f, unit[i], dz[i]);
+}
+
+// workspace: [blocks][K][2] double partials | [N][K][2] float (a, b), padded to 16 bytes | [N][H][W] float d
+static inline size_t nc_partial_bytes(int N, int K, int H, int W) { return (size_t)crf_blocks(N, H, W) * K * 2 * sizeof(double); }
+static inline size_t nc_coef_bytes(int N, int K) { return ((size_t)N * K * 2 * sizeof(float) + 15) & ~(size_t)15; }
+
+extern "C" size_t pp_nc_loss_workspace(int N, int K, int H, int W) {
+  if (N < 1 || K < 1 || H < 1 || W < 1) return 0;
+  return nc_partial_bytes(N, K, H, W) + nc_coef_bytes(N, K) + (size_t)N * H * W * sizeof(float);
+}
+
+extern "C" int pp_nc_loss_fwd(const float* logits, const float* image, const float* valid_mask, int N, int K, int C, int H, int W,
+                              int radius, int dilation, float sigma_xy, float sigma_rgb, float* unit_grad, double* assoc_vol,
+                              double* sums, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PP_CHECK_ARG(logits && image && assoc_vol && sums && workspace, "nc_loss_fwd: null pointer");
+  // (N and the rows of tiles are grid.z and grid.y: 65535 each)
+  PP_CHECK_ARG(N >= 1 && N <= 65535 && H >= 1 && H <= 65535 * CRF_TH && W >= 1 && (long long)H * W * K < 0x7fffffffLL,
+               "nc_loss_fwd: N=%d (<= 65535) H=%d (<= %d) W=%d", N, H, 65535 * CRF_TH, W);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && C >= 1 && C <= CRF_MAXC, "nc_loss_fwd: K=%d (1..%d) C=%d (1..%d)", K, PP_MAXK, C, CRF_MAXC);
+  PP_CHECK_ARG(radius >= 1 && radius <= CRF_MAXR && dilation >= 1 && dilation <= CRF_MAXD && radius * dilation <= CRF_MAXHALO,
+               "nc_loss_fwd: radius=%d (1..%d) dilation=%d (1..%d), radius * dilation <= %d", radius, CRF_MAXR, dilation, CRF_MAXD, CRF_MAXHALO);
+  PP_CHECK_ARG(sigma_xy > 0.f && sigma_rgb > 0.f && sigma_xy < INFINITY && sigma_rgb < INFINITY, "nc_loss_fwd: sigma_xy=%g sigma_rgb=%g (> 0)",
+               (double)sigma_xy, (double)sigma_rgb);
+  PP_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "nc_loss_fwd: the workspace must be 16-byte aligned");
+  if (workspace_bytes < pp_nc_loss_workspace(N, K, H, W)) {
+    pp_set_error("nc_loss_fwd: workspace too small (%zu < %zu)", workspace_bytes, pp_nc_loss_workspace(N, K, H, W));
+    return PP_ERR_WORKSPACE;
+  }
+  const int halo = radius * dilation, NC = (C == 1 || C == 3) ? C : CRF_MAXC;
+  // class chunks: as few as the LDS bound allows, of equal width (as pp_crf_loss_fwd)
+  int nchunks = pp_cdiv(K, CRF_KC), KC = pp_cdiv(K, nchunks);
+  while (crf_lds_bytes((KC + NC + 1) | 1, halo) > CRF_LDS_MAX) { ++nchunks; KC = pp_cdiv(K, nchunks); }
+  nchunks = pp_cdiv(K, KC);
+  const size_t lds = crf_lds_bytes((KC + NC + 1) | 1, halo);
+  const double log2e = 1.4426950408889634;
+  const float a_xy = (float)(-log2e / (2.0 * (double)sigma_xy * sigma_xy)), a_rgb = (float)(-log2e / (2.0 * (double)sigma_rgb * sigma_rgb));
+  const dim3 grid(pp_cdiv(W, CRF_TW), pp_cdiv(H, CRF_TH), N);
+  const int bpi = pp_cdiv(W, CRF_TW) * pp_cdiv(H, CRF_TH), HW = H * W;
+  double* partial = (double*)workspace;
+  float* coef = (float*)((char*)workspace + nc_partial_bytes(N, K, H, W));
+  float* dws = (float*)((char*)coef + nc_coef_bytes(N, K));
+  const double P = (double)N * H * W, nb = (2.0 * radius + 1.0) * (2.0 * radius + 1.0) - 1.0;
+  pp_prof_begin(PP_K_LOSS, P * nb * nchunks * (2.0 * KC + 3.0 * C + 4.0), P * (4.0 * K * (unit_grad ? 4 : 1) + 4.0 * C + 4.0), s);
+#define NC_LAUNCH(KC_, CT_)                                                                                                    \
+  do {                                                                                                                           \
+    auto kern = nc_fwd_kernel<KC_, CT_>;                                                                                         \
+    pp_max_lds(reinterpret_cast<const void*>(kern), CRF_LDS_MAX);                                                                \
+    hipLaunchKernelGGL(kern, grid, dim3(CRF_THREADS), lds, s, logits, image, valid_mask, K, C, H, W, radius, dilation, a_xy,     \
+                       a_rgb, nchunks, unit_grad, dws, partial);                                                                \
+  } while (0)
+#define NC_BY_C(KC_) do { if (C == 1) NC_LAUNCH(KC_, 1); else if (C == 3) NC_LAUNCH(KC_, 3); else NC_LAUNCH(KC_, 0); } while (0)
+  switch (KC) {
+    case 1: NC_BY_C(1); break;
+    case 2: NC_BY_C(2); break;
+    case 3: NC_BY_C(3); break;
+    case 4: NC_BY_C(4); break;
+    case 5: NC_BY_C(5); break;
+    case 6: NC_BY_C(6); break;
+    case 7: NC_BY_C(7); break;
+    default: NC_BY_C(8); break;
+  }
+#undef NC_BY_C
+#undef NC_LAUNCH
+  hipLaunchKernelGGL(nc_reduce_kernel, dim3(N * K), dim3(256), 0, s, (const double*)partial, bpi, K, assoc_vol);
+  hipLaunchKernelGGL(nc_final_kernel, dim3(1), dim3(256), 0, s, (const double*)assoc_vol, N * K, coef, sums);
+  if (unit_grad) {
+    const bool v4 = (HW & 3) == 0 && ((((uintptr_t)logits | (uintptr_t)unit_grad | (uintptr_t)valid_mask) & 15) == 0);
+    if (v4)
+      hipLaunchKernelGGL(nc_grad_kernel<4>, dim3(pp_cdiv(HW / 4, LS_THREADS), N), dim3(LS_THREADS), 0, s, logits, valid_mask,
+                         (const float*)dws, (const float*)coef, K, HW, unit_grad);
+    else
+      hipLaunchKernelGGL(nc_grad_kernel<1>, dim3(pp_cdiv(HW, LS_THREADS), N), dim3(LS_THREADS), 0, s, logits, valid_mask,
+                         (const float*)dws, (const float*)coef, K, HW, unit_grad);
+  }
+  pp_prof_end(s);
+  return pp_launch_status("nc_loss_fwd");
+}
+
+extern "C" int pp_nc_loss_bwd(const float* unit_grad, const double* sums, const float* g_up, float grad_scale, float* dlogits,
+                              long long n, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PP_CHECK_ARG(unit_grad && sums && g_up && dlogits && n >= 1, "nc_loss_bwd: bad arguments");
+  const long long n4 = ((((uintptr_t)unit_grad | (uintptr_t)dlogits) & 15) == 0) ? n >> 2 : 0;
+  pp_prof_begin(PP_K_LOSS, 2.0 * (double)n, 12.0 * (double)n, s);
+  hipLaunchKernelGGL(nc_bwd_kernel, dim3(ls_blocks(n4 ? n4 : n, 8192)), dim3(LS_THREADS), 0, s, unit_grad, sums, g_up, grad_scale, dlogits,
+                     n, n4);
+  pp_prof_end(s);
+  return pp_launch_status("nc_loss_bwd");
 }
 
 // ---------------------------------------------------------------- 95 % Hausdorff distance (inference.py:217-237)

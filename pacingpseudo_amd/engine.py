@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from ._lib import PpBnCoefItem, PpLazyIn, PpPackItem, PpWinoPackItem, lib, lib_for, prof_range, stream_ptr
 from .convop import ConvOp, select as conv_select
-from .losses.losses import check_crf_params
+from .losses.losses import check_crf_params, check_nc_params
 
 WINO_ENABLED = os.environ.get('PP_WINO', '1') != '0'      # A/B switch for the Winograd path
 # split-fp16 ("f16x3") direct convolution for the non-Winograd layers with at least this many output channels
@@ -482,18 +482,29 @@ class _Plan:
         # [0:6] segmentation losses (pp_seg_losses_fwd), [6:8] auxiliary partial CE (pp_aux_pce_fwd)
         # With the gated-CRF loss (--do_loss_crf) its two sums sit between them, [6:8] (pp_crf_loss_fwd), and the auxiliary pair at
         # [8:10]: a step without the auxiliary path still reduces one contiguous block.  Its buffers exist in such plans only.
-        self.crf = None
+        # The normalised-cut loss (--do_loss_nc) likewise: its pair (pp_nc_loss_fwd: sum NC, N K) directly behind the CRF pair when that
+        # exists, else at [6:8], and the auxiliary pair behind it; [0:reg_end] is what a step without the auxiliary path reduces.
+        self.crf = self.nc = None
+        self.all_sums = torch.zeros(8 + (2 if eng.crf is not None else 0) + (2 if eng.nc is not None else 0), device=dev, dtype=torch.float64)
+        self.reg_end = 6
         if eng.crf is not None:
             check_crf_params(K=net.num_classes, C=net.input_ch, **eng.crf)
-            self.all_sums = torch.zeros(10, device=dev, dtype=torch.float64)
             nws = lib.pp_crf_loss_workspace(B, H, W)
             self.crf = dict(sums=self.all_sums[6:8], ws=torch.empty(nws, device=dev, dtype=torch.uint8), ws_bytes=nws,
                             unit=torch.empty((B, net.num_classes, H, W), **f32) if trainable else None)
-        else:
-            self.all_sums = torch.zeros(8, device=dev, dtype=torch.float64)
+            self.reg_end = 8
+        if eng.nc is not None:
+            check_nc_params(K=net.num_classes, C=net.input_ch, **eng.nc)
+            nws = lib.pp_nc_loss_workspace(B, net.num_classes, H, W)
+            s0 = self.reg_end
+            # fin: where pp_losses_finalize's ratio slot (sums[2] / sums[3]) finds the pair
+            self.nc = dict(sums=self.all_sums[s0:s0 + 2], fin=self.all_sums[s0 - 2:], ws=torch.empty(nws, device=dev, dtype=torch.uint8),
+                           ws_bytes=nws, assoc_vol=torch.zeros((B, net.num_classes, 2), device=dev, dtype=torch.float64),
+                           unit=torch.empty((B, net.num_classes, H, W), **f32) if trainable else None)
+            self.reg_end = s0 + 2
         self.sums = self.all_sums[:6]
         if self.aux is not None:
-            self.aux['sums'] = self.all_sums[8:10] if self.crf is not None else self.all_sums[6:8]
+            self.aux['sums'] = self.all_sums[self.reg_end:self.reg_end + 2]
         self.target = torch.empty((B, H, W), device=dev, dtype=torch.int64)
 
     def ws_args(self):
@@ -627,6 +638,12 @@ class StepEngine:
             self.crf = check_crf_params(radius=getattr(args, 'crf_radius', 5), dilation=getattr(args, 'crf_dilation', 1),
                                         sigma_xy=getattr(args, 'crf_sigma_xy', 6.0), sigma_rgb=getattr(args, 'crf_sigma_rgb', 0.1),
                                         K=backbone.num_classes)
+        # --do_loss_nc: the normalised cut on the weak logits, handled as the CRF loss is
+        self.nc = None
+        if getattr(args, 'do_loss_nc', False):
+            self.nc = check_nc_params(radius=getattr(args, 'nc_radius', 5), dilation=getattr(args, 'nc_dilation', 1),
+                                      sigma_xy=getattr(args, 'nc_sigma_xy', 6.0), sigma_rgb=getattr(args, 'nc_sigma_rgb', 0.1),
+                                      K=backbone.num_classes)
         self.storage = getattr(args, 'storage', 'fp32') or 'fp32'
         if os.environ.get('PP_ACT_H16', '0') == '1' and self.storage == 'fp32':
             self.storage = 'fp16'
@@ -1376,6 +1393,13 @@ class StepEngine:
                                    B, K, Cin, H, W, c['radius'], c['dilation'], c['sigma_xy'], c['sigma_rgb'],
                                    plan.crf['unit'].data_ptr() if need_grad else None, plan.crf['sums'].data_ptr(),
                                    plan.crf['ws'].data_ptr(), plan.crf['ws_bytes'], st)
+        do_nc_loss = bool(train and plan.nc is not None)
+        if do_nc_loss:
+            c = self.nc
+            plan.K.pp_nc_loss_fwd(logits.data_ptr(), image.data_ptr(), valid_mask.data_ptr() if valid_mask is not None else None,
+                                  B, K, Cin, H, W, c['radius'], c['dilation'], c['sigma_xy'], c['sigma_rgb'],
+                                  plan.nc['unit'].data_ptr() if need_grad else None, plan.nc['assoc_vol'].data_ptr(),
+                                  plan.nc['sums'].data_ptr(), plan.nc['ws'].data_ptr(), plan.nc['ws_bytes'], st)
         if do_aux:
             if side is not None:
                 torch.cuda.current_stream().wait_event(plan.aux_join)
@@ -1384,7 +1408,7 @@ class StepEngine:
             ax, a = self.aux, plan.aux
             drop, feat, wfc, logits_aux = A['drop'], A['feat'], A['wfc'], A['logits_aux']
         if self.comm is not None:
-            self.comm.allreduce_sums(plan.all_sums if do_aux else (plan.all_sums[:8] if do_crf_loss else plan.sums))
+            self.comm.allreduce_sums(plan.all_sums if do_aux else (plan.all_sums[:plan.reg_end] if (do_crf_loss or do_nc_loss) else plan.sums))
         out = {}
         loss_pce = torch.empty((), device=dev, dtype=torch.float32)
         loss_ent = torch.empty((), device=dev, dtype=torch.float32) if do_ent else None
@@ -1403,6 +1427,11 @@ class StepEngine:
             loss_crf = torch.empty((), device=dev, dtype=torch.float32)
             plan.K.pp_losses_finalize(plan.all_sums[4:].data_ptr(), 1 if crf_mask is not None else 0, None, loss_crf.data_ptr(), None, st)
             out['loss_crf'] = loss_crf
+        if do_nc_loss:
+            # sum NC / (N K) over the ranks: the unmasked ratio slot (the count is never 0)
+            loss_nc = torch.empty((), device=dev, dtype=torch.float32)
+            plan.K.pp_losses_finalize(plan.nc['fin'].data_ptr(), 0, None, loss_nc.data_ptr(), None, st)
+            out['loss_nc'] = loss_nc
 
         if do_aux:
             loss_aux = torch.empty((), device=dev, dtype=torch.float32)
@@ -1429,6 +1458,8 @@ class StepEngine:
                              drop=self.last_drop_masks if do_aux else None)
             if do_crf_loss:
                 self.last.update(do_crf=True, crf_mask=crf_mask)
+            if do_nc_loss:
+                self.last.update(do_nc=True)
         return out
 
     def _aux_input(self, plan, aux_group, st) -> View:
@@ -1521,6 +1552,9 @@ class StepEngine:
                 # streaming add of the unit gradient the forward left, behind the kernel that WRITES dlogits[:B]
                 plan.K.pp_crf_loss_bwd(plan.crf['unit'].data_ptr(), plan.crf['sums'].data_ptr(), 1 if S['crf_mask'] is not None else 0,
                                        gp('loss_crf'), plan.loss_scale, plan.dlogits.data_ptr(), B * K * H * W, st)
+            if S.get('do_nc') and gp('loss_nc') is not None:
+                plan.K.pp_nc_loss_bwd(plan.nc['unit'].data_ptr(), plan.nc['sums'].data_ptr(), gp('loss_nc'), plan.loss_scale,
+                                      plan.dlogits.data_ptr(), B * K * H * W, st)
         with prof_range('backward: decoder'):
             g6 = self._unet_backward_decoder(plan, S['bn_training'], grads, st)
         if S['do_aux']:

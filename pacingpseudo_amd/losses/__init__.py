@@ -1,0 +1,1 @@
+from .losses import normalized_cut_loss  # noqa: F401

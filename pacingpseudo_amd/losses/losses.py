@@ -265,6 +265,62 @@ def gated_crf_loss(input, image, valid_mask=None, radius=5, dilation=1, sigma_xy
     return _CrfLoss.apply(z, x, m, prm)
 
 
+def check_nc_params(radius=5, dilation=1, sigma_xy=6.0, sigma_rgb=0.1, K=None, C=None) -> dict:
+    """The accepted ranges of the normalised-cut loss (include/pacingpseudo_hip.h: pp_nc_loss_fwd) -- those of check_crf_params: the
+    two losses walk the same window -- checked before any launch.  Returns the normalised parameters."""
+    try:
+        return check_crf_params(radius, dilation, sigma_xy, sigma_rgb, K=K, C=C)
+    except (ValueError, NotImplementedError) as e:
+        raise type(e)(str(e).replace('gated CRF', 'normalised cut', 1)) from None
+
+
+class _NcLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, image, mask, prm):
+        N, K, H, W = z.shape
+        st = stream_ptr()
+        dev = z.device
+        # [2:4] = sum NC, N K: where pp_losses_finalize's ratio slot reads them (the unmasked form: the count is never 0)
+        sums = torch.zeros(4, device=dev, dtype=torch.float64)
+        assoc_vol = torch.empty((N, K, 2), device=dev, dtype=torch.float64)
+        nws = lib.pp_nc_loss_workspace(N, K, H, W)
+        ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+        unit = torch.empty_like(z) if ctx.needs_input_grad[0] else None
+        lib.pp_nc_loss_fwd(z.data_ptr(), image.data_ptr(), mask.data_ptr() if mask is not None else None, N, K, image.shape[1], H, W,
+                           prm['radius'], prm['dilation'], prm['sigma_xy'], prm['sigma_rgb'],
+                           unit.data_ptr() if unit is not None else None, assoc_vol.data_ptr(), sums[2:].data_ptr(), ws.data_ptr(), nws, st)
+        out = torch.empty((), device=dev, dtype=torch.float32)
+        lib.pp_losses_finalize(sums.data_ptr(), 0, None, out.data_ptr(), None, st)
+        ctx.unit, ctx.sums = unit, sums
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        unit = ctx.unit
+        g = g.to(torch.float32).contiguous()
+        dz = torch.zeros_like(unit)
+        lib.pp_nc_loss_bwd(unit.data_ptr(), ctx.sums[2:].data_ptr(), g.data_ptr(), 1.0, dz.data_ptr(), unit.numel(), stream_ptr())
+        return dz, None, None, None
+
+
+def normalized_cut_loss(input, image, valid_mask=None, radius=5, dilation=1, sigma_xy=6.0, sigma_rgb=0.1):
+    """Normalised cut over the local bilateral window of gated_crf_loss (this implementation's addition; the reference has no such
+    loss): (1/(N K)) sum_n sum_c (1 - A_nc / V_nc) with p = softmax(input), q_ic = sum_j m_j k_ij p_jc, d_i = sum_j m_j k_ij,
+    A_nc = sum_i m_i p_ic q_ic, V_nc = sum_i m_i p_ic d_i; a class with V_nc <= 1e-6 in an image adds 0 and gets no gradient.
+    Differentiable in `input` only."""
+    z, x = _check(input, 'input'), _check(image, 'image')
+    N, K, H, W = z.shape
+    if x.shape[0] != N or tuple(x.shape[2:]) != (H, W):
+        raise ValueError(f'image must be (N,C,H,W) with the N, H, W of input {tuple(z.shape)}, got {tuple(x.shape)}')
+    m = None
+    if valid_mask is not None:
+        m = _check(valid_mask, 'valid_mask')
+        if tuple(m.shape) != (N, 1, H, W):
+            raise ValueError(f'valid_mask must be {(N, 1, H, W)}, got {tuple(m.shape)}')
+    prm = check_nc_params(radius, dilation, sigma_xy, sigma_rgb, K=K, C=x.shape[1])
+    return _NcLoss.apply(z, x, m, prm)
+
+
 class _WeightedSum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weights, *terms):

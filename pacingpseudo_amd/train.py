@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import resume
-from .losses.losses import check_crf_params
+from .losses.losses import check_crf_params, check_nc_params
 from .optim import add_clip_flag, add_ema_flags, log_clip_stats, positive_float, positive_int
 
 parser = argparse.ArgumentParser(description='PacingPseudo training on MI355X (flag surface of the reference driver)')
@@ -156,6 +156,17 @@ parser.add_argument('--crf_radius', type=positive_int, default=5, help='neighbou
 parser.add_argument('--crf_dilation', type=positive_int, default=1, help='spacing d of the neighbourhood offsets in pixels (1 .. 4, r * d <= 16)')
 parser.add_argument('--crf_sigma_xy', type=positive_float, default=6.0, help='width of the position kernel, in offsets')
 parser.add_argument('--crf_sigma_rgb', type=positive_float, default=0.1, help='width of the intensity kernel, in units of the network input')
+# normalised cut on the weak-view prediction over the same local bilateral window (pp_nc_loss_*); the reference has
+# no such loss.  It divides each class's cut by that class's volume, so it lacks the Potts term's shrinking bias; the two may be on together
+parser.add_argument('--do_loss_nc', action='store_true',
+                    help='add the normalised-cut loss: per image and class, 1 - association / volume over a local bilateral window '
+                         '(--nc_radius, --nc_dilation, --nc_sigma_xy, --nc_sigma_rgb)')
+parser.add_argument('--loss_nc_weight', type=float, default=0.1, help='its weight (an untuned first value)')
+parser.add_argument('--ramp_up_loss_nc', action='store_true', help='Gaussian ramp-up of that weight over the epochs (--ramp_up_scale)')
+parser.add_argument('--nc_radius', type=positive_int, default=5, help='neighbourhood radius r: offsets dy, dx in [-r, r] (1 .. 8)')
+parser.add_argument('--nc_dilation', type=positive_int, default=1, help='spacing d of the neighbourhood offsets in pixels (1 .. 4, r * d <= 16)')
+parser.add_argument('--nc_sigma_xy', type=positive_float, default=6.0, help='width of the position kernel, in offsets')
+parser.add_argument('--nc_sigma_rgb', type=positive_float, default=0.1, help='width of the intensity kernel, in units of the network input')
 add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
 add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
@@ -203,6 +214,10 @@ def parse_args(argv=None):
         check_crf_params(args.crf_radius, args.crf_dilation, args.crf_sigma_xy, args.crf_sigma_rgb)
     except (ValueError, NotImplementedError) as e:
         parser.error(f'--crf_radius / --crf_dilation / --crf_sigma_xy / --crf_sigma_rgb: {e}')
+    try:
+        check_nc_params(args.nc_radius, args.nc_dilation, args.nc_sigma_xy, args.nc_sigma_rgb)
+    except (ValueError, NotImplementedError) as e:
+        parser.error(f'--nc_radius / --nc_dilation / --nc_sigma_xy / --nc_sigma_rgb: {e}')
     return args
 
 
@@ -337,6 +352,7 @@ def train_interface(args, resume_state=None):
         # loss meters live on the GPU: [sum pce*n, sum ent*n, sum cr*n, sum aux*n, sum mem, n, iterations]
         acc = torch.zeros(7, device=device, dtype=torch.float64)
         acc_crf = torch.zeros(1, device=device, dtype=torch.float64) if args.do_loss_crf else None      # sum crf*n (--do_loss_crf only)
+        acc_nc = torch.zeros(1, device=device, dtype=torch.float64) if args.do_loss_nc else None        # sum nc*n (--do_loss_nc only)
         n_img = 0
         for idx, batch in enumerate(train_loader):
             if args.max_iters and idx >= args.max_iters:
@@ -355,6 +371,8 @@ def train_interface(args, resume_state=None):
             w_cr = gaussian_ramp_up(t=curr_epoch, base_value=args.loss_cr_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_cr else 1.0
             w_crf = (gaussian_ramp_up(t=curr_epoch, base_value=args.loss_crf_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_crf
                      else args.loss_crf_weight)
+            w_nc = (gaussian_ramp_up(t=curr_epoch, base_value=args.loss_nc_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_nc
+                    else args.loss_nc_weight)
 
             def assemble(out, _epoch=None):
                 # train_chaos.py:273-310: pce + ent * w_ent + cr * w_cr + aux * w_aux + memory * w_mem -- one launch each way
@@ -370,6 +388,8 @@ def train_interface(args, resume_state=None):
                         terms.append(out['loss_memory']); weights.append(args.loss_memory_weight)
                 if args.do_loss_crf:
                     terms.append(out['loss_crf']); weights.append(w_crf)
+                if args.do_loss_nc:
+                    terms.append(out['loss_nc']); weights.append(w_nc)
                 return weighted_loss_sum(terms, weights)
             if args.graph_step and n == args.batch_size:      # (a ragged last batch runs eagerly: another shape, another plan)
                 if graph_step is None:
@@ -394,10 +414,13 @@ def train_interface(args, resume_state=None):
                     acc[4] += net_outputs['loss_memory'].detach() * args.loss_memory_weight
             if args.do_loss_crf:
                 acc_crf[0] += net_outputs['loss_crf'].detach() * (w_crf * n)
+            if args.do_loss_nc:
+                acc_nc[0] += net_outputs['loss_nc'].detach() * (w_nc * n)
             acc[5] += n
             acc[6] += 1
             n_img += n
-        a = (torch.cat([acc, acc_crf]) if args.do_loss_crf else acc).cpu().numpy()      # the one host sync of the epoch
+        extra = [t for t in (acc_crf, acc_nc) if t is not None]                        # [7] crf when on, nc behind it
+        a = (torch.cat([acc] + extra) if extra else acc).cpu().numpy()      # the one host sync of the epoch
         epoch_toc = time.time()
         cnt, its = max(a[5], 1), max(a[6], 1)
         # 16-bit storage: optimizer steps the overflow guard skipped this epoch (a static loss scale that keeps
@@ -421,6 +444,9 @@ def train_interface(args, resume_state=None):
                                              'themselves are not finite')
         if rank == 0:
             crf_col = ", loss_crf: {:.6f}".format(a[7] / cnt) if args.do_loss_crf else ""
+            i_nc = 8 if args.do_loss_crf else 7
+            if args.do_loss_nc:
+                crf_col += ", loss_nc: {:.6f}".format(a[i_nc] / cnt)
             logging.info("epoch: {:03d}, lr: {:.6f}, loss_pce: {:.6f}, loss_ent: {:.6f}, loss_cr: {:.6f}, loss_aux_cls: {:.6f}, "
                          "loss_memory: {:.6f}{}, {:.2f} s/epoch".format(curr_epoch, new_lr, a[0] / cnt, a[1] / cnt, a[2] / cnt,
                                                                        a[3] / cnt, a[4] / its, crf_col, epoch_toc - epoch_tic))
@@ -449,6 +475,8 @@ def train_interface(args, resume_state=None):
             scalars.add('losses/loss_memory', a[4] / its, curr_epoch)
             if args.do_loss_crf:
                 scalars.add('train/loss_crf', a[7] / cnt, curr_epoch)
+            if args.do_loss_nc:
+                scalars.add('train/loss_nc', a[i_nc] / cnt, curr_epoch)
             scalars.add('lr/current_lr', new_lr, curr_epoch)
             scalars.add('losses/loss_pce_val', loss_pce_val, curr_epoch)
             for i, nm in enumerate(names):

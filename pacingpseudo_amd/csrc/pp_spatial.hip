@@ -952,8 +952,8 @@ PP_NS_END
 // neighbours P2..P9 clockwise from north, B = their sum, A = number of 0 -> 1 steps around the ring:
 //   delete in sub-iteration 1 when 2 <= B <= 6, A == 1, P2*P4*P6 == 0 and P4*P6*P8 == 0,
 //   delete in sub-iteration 2 when 2 <= B <= 6, A == 1, P2*P4*P8 == 0 and P2*P6*P8 == 0;   until nothing changes.
-// One block per mask keeps the (zero-bordered) image twice in LDS: masks up to about 280 x 280 (256 x 256 slices fit).
-#define SK_MAXPIX (322 * 322)
+// One block per mask keeps the (zero-bordered) image twice in LDS: (H + 2)(W + 2) <= 81888, squares up to 284 x 284 (256 x 256
+// slices fit); pp_skeletonize checks it.
 __global__ __launch_bounds__(1024) void skeletonize_kernel(unsigned char* __restrict__ masks, int H, int W, int max_sweeps) {
   extern __shared__ unsigned char sk[];             // [2][(H+2)*(W+2)]
   const int Wp = W + 2, Np = (H + 2) * Wp;
@@ -1039,9 +1039,12 @@ __global__ void endpoints_kernel(const unsigned char* __restrict__ img, unsigned
 }
 
 extern "C" int pp_skeletonize(unsigned char* masks, int M, int H, int W, void* stream) {
-  PP_CHECK_ARG(masks && M >= 1 && H >= 1 && W >= 1 && (H + 2) * (W + 2) <= SK_MAXPIX, "skeletonize: bad arguments");
+  // two zero-bordered byte images in dynamic LDS plus the kernel's 4 static bytes (`changed`) against the 160 KB of a workgroup:
+  // (H + 2)(W + 2) <= 81888, so at most 2 * 81888 + 4 = 163780 of 163840 bytes.  The largest square admitted is 284 x 284
+  // (286^2 = 81796); 280 x 280 takes 159052 bytes.  The product is taken in 64 bits: in 32 bits H = W = 65534 wraps round to 0.
+  PP_CHECK_ARG(masks && M >= 1 && H >= 1 && W >= 1 && 2LL * (H + 2LL) * (W + 2LL) <= 160 * 1024 - 64,
+               "skeletonize: bad arguments, or the image does not fit the LDS");
   const int lds = 2 * (H + 2) * (W + 2);
-  PP_CHECK_ARG(lds <= 160 * 1024 - 64, "skeletonize: image does not fit the LDS");
   pp_max_lds(reinterpret_cast<const void*>(skeletonize_kernel), lds);
   hipLaunchKernelGGL(skeletonize_kernel, dim3(M), dim3(1024), lds, (hipStream_t)stream, masks, H, W, H + W);
   return pp_launch_status("skeletonize");
@@ -1049,7 +1052,8 @@ extern "C" int pp_skeletonize(unsigned char* masks, int M, int H, int W, void* s
 
 extern "C" int pp_dilate_antidiagonal(unsigned char* seeds, const unsigned char* masks, int M, int H, int W, int iterations,
                                       void* stream) {
-  PP_CHECK_ARG(seeds && masks && M >= 1 && iterations >= 0 && 2 * (H + 2) * (W + 2) <= 160 * 1024 - 64, "dilate_antidiagonal: bad arguments");
+  PP_CHECK_ARG(seeds && masks && M >= 1 && H >= 1 && W >= 1 && iterations >= 0 && 2LL * (H + 2LL) * (W + 2LL) <= 160 * 1024 - 64,
+               "dilate_antidiagonal: bad arguments");
   const int lds = 2 * (H + 2) * (W + 2);
   pp_max_lds(reinterpret_cast<const void*>(dilate_antidiag_kernel), lds);
   hipLaunchKernelGGL(dilate_antidiag_kernel, dim3(M), dim3(1024), lds, (hipStream_t)stream, seeds, masks, H, W, iterations);

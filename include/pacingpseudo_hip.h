@@ -589,6 +589,28 @@ int pp_nc_loss_fwd(const float* logits, const float* image, const float* valid_m
 int pp_nc_loss_bwd(const float* unit_grad, const double* sums, const float* g_up, float grad_scale, float* dlogits, long long n,
                    void* stream);
 
+/* Mumford-Shah level-set loss with an anisotropic total-variation term on the weak-view logits (this implementation's addition;
+ * DESIGN.md section 7).  With p = softmax(logits) over K, x the image (N,C,H,W), C <= 4, m the valid mask (NULL: 1 everywhere):
+ *   S_nc = sum_{i in n} m_i p_ic,  mu_ncr = sum_{i in n} m_i p_ic x_ir / S_nc if S_nc > 1e-6 (else the class is inactive in that
+ *   image: no level-set term, no level-set gradient),  e_ic = sum_r (x_ir - mu_ncr)^2,
+ *   E = sum_nci m_i p_ic e_ic + tv_weight * sum_nc sum_(i,j) m_i m_j |p_ic - p_jc|   ((i, j): the vertical and horizontal neighbour
+ *   pairs inside the image, each once),  L = E / D,  D = N H W, or max(sum m, 1e-8) with a mask.
+ * pp_ms_loss_fwd writes stats[n][c] = {S, mu_0 .. mu_{C-1}} and sums[0] = E, sums[1] = sum m (mask) or N H W in double, in a fixed
+ * order (no atomics); the loss is sums[0] / sums[1] -- data-parallel callers add `sums` over the ranks first.  With unit_grad
+ * (N,K,H,W) non-NULL the energy pass also leaves u_ic = p_ic (g_ic - <p_i, g_i>) there,
+ *   g_ic = m_i e_ic [active] + tv_weight * sum_{j in 4-neighbours of i inside the image} m_i m_j sign(p_ic - p_jc), sign(0) = 0
+ * (the derivative through mu vanishes: mu is the m p-weighted mean);  pp_ms_loss_bwd then ACCUMULATES
+ *   dlogits[e] += grad_scale * g_up[0] * (1 / D) * unit_grad[e],  e < n = N K H W
+ * reading D from `sums` on the device.  Accepted: 1 <= K <= 32, 1 <= C <= 4, H, W >= 1, tv_weight >= 0 and finite.  The workspace
+ * (pp_ms_loss_workspace bytes, 16-byte aligned) holds the per-block partials of both passes and the fp32 copy of the means.  No
+ * gradient flows to the image or the mask. */
+size_t pp_ms_loss_workspace(int N, int K, int C, int H, int W);
+int pp_ms_loss_fwd(const float* logits, const float* image, const float* valid_mask, int N, int K, int C, int H, int W,
+                   float tv_weight, float* unit_grad, double* stats, double* sums, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int pp_ms_loss_bwd(const float* unit_grad, const double* sums, int has_mask, const float* g_up, float grad_scale, float* dlogits,
+                   long long n, void* stream);
+
 /* Connected components of class maps and the keep-largest-component filter of an evaluation pipeline (this implementation's
  * addition: the reference scores its raw arg-max, inference.py:159-190).  cls: int64 class maps [N][H][W].
  * Two pixels of ONE image are connected when they are neighbours -- the 4-neighbourhood for connectivity 1, the 8-neighbourhood

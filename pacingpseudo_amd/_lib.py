@@ -178,6 +178,9 @@ _PROTOS = {
     'pp_nc_loss_workspace': (sz, [i32, i32, i32, i32]),
     'pp_nc_loss_fwd': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, sz, vp]),
     'pp_nc_loss_bwd': (i32, [vp, vp, vp, f32, vp, i64, vp]),
+    'pp_ms_loss_workspace': (sz, [i32, i32, i32, i32, i32]),
+    'pp_ms_loss_fwd': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, sz, vp]),
+    'pp_ms_loss_bwd': (i32, [vp, vp, i32, vp, f32, vp, i64, vp]),
     'pp_components_workspace': (sz, [i32, i32, i32, i32]),
     'pp_label_components': (i32, [vp, i32, i32, i32, i32, vp, vp, sz, vp]),
     'pp_keep_largest_components': (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),

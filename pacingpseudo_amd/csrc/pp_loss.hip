@@ -1670,6 +1670,279 @@ extern "C" int pp_nc_loss_bwd(const float* unit_grad, const double* sums, const 
   return pp_launch_status("nc_loss_bwd");
 }
 
+// ---------------------------------------------------------------- Mumford-Shah level-set loss on the weak-view logits
+//   S_nc = sum_i m_i p_ic,  mu_ncr = sum_i m_i p_ic x_ir / S_nc if S_nc > 1e-6 (else the class is inactive in that image),
+//   e_ic = sum_r (x_ir - mu_ncr)^2,  E_ls = sum_nci m_i p_ic e_ic [active],  E_tv = sum_nc sum_(i,j) m_i m_j |p_ic - p_jc| over the
+//   vertical and horizontal neighbour pairs inside the image (each once),  L = (E_ls + lambda E_tv) / D,  D = N H W, or
+//   max(sum m, 1e-8) with a mask.  mu is the m p-weighted mean, so the derivative through mu vanishes:
+//   g_ic = m_i e_ic [active] + lambda sum_{j in 4-neighbours} m_i m_j sign(p_ic - p_jc),  dL/dz_ic = (1/D) p_ic (g_ic - <p_i, g_i>).
+// ms_sums_kernel streams logits, image and mask once (V pixels per thread) and leaves one double partial of S and of every X_r per
+// (block, class); blocks never straddle an image.  ms_stats_kernel adds the blocks of one image in a fixed order per (n, c) into
+// stats[n][c] = {S, mu_0 .. mu_{C-1}} (double) and the fp32 copy {active, mu_r} the next pass reads (formed in double, rounded once).
+// ms_energy_kernel owns a 32 x 8 tile: it stages the probabilities of ALL K classes and the mask of tile + a one-pixel halo in LDS,
+// class-major (m = 0 outside the image: such a neighbour adds nothing), every staged pixel through the one expression crf_prob
+// behind crf_softmax_norm -- a pixel's probabilities are the same bits in a tile's interior, in a halo and in the next tile, so
+// sign() and |.| see a difference only where there is one.  Each lane then walks the classes of its pixel twice over LDS with
+// nothing but scalars live (energy and <p, g>; then u = p (g - <p, g>)): no class array in registers at any K.  Per block one double
+// partial of the energy and of sum m; crf_reduce_kernel adds them in a fixed order.  No atomics: the same bits run after run.
+#define MS_S_MIN 1e-6
+#define MS_TW 32
+#define MS_TH 8
+#define MS_THREADS (MS_TW * MS_TH)
+#define MS_LW (MS_TW + 2)
+#define MS_LH (MS_TH + 2)
+#define MS_NSTAT (1 + CRF_MAXC)                       // floats per (n, c) of the fp32 copy: active flag, mu_0 .. mu_3
+
+template <int V>
+__global__ __launch_bounds__(LS_THREADS) void ms_sums_kernel(const float* __restrict__ z, const float* __restrict__ img,
+                                                             const float* __restrict__ mask, int K, int C, int HW,
+                                                             double* __restrict__ partial /*[N][gridDim.x][K][1 + C]*/) {
+  struct alignas(4 * V) Vec { float f[V]; };
+  __shared__ double sh[PP_MAXK * MS_NSTAT][LS_THREADS / 64];
+  const int n = blockIdx.y, ld = HW / V, i0 = blockIdx.x * LS_THREADS + threadIdx.x;
+  const bool on = i0 < ld;
+  const int i = on ? i0 : ld - 1;                    // lanes past the image read its last group and weigh it 0
+  const Vec* zn = reinterpret_cast<const Vec*>(z + (size_t)n * K * HW) + i;
+  const Vec* xn = reinterpret_cast<const Vec*>(img + (size_t)n * C * HW) + i;
+  Vec mv, xv[CRF_MAXC];
+#pragma unroll
+  for (int j = 0; j < V; ++j) mv.f[j] = 1.f;
+  if (mask) mv = reinterpret_cast<const Vec*>(mask + (size_t)n * HW)[i];
+  if (!on) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) mv.f[j] = 0.f;
+  }
+#pragma unroll
+  for (int r = 0; r < CRF_MAXC; ++r) {
+    if (r < C) xv[r] = xn[(size_t)r * ld];
+    else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) xv[r].f[j] = 0.f;
+    }
+  }
+  float mx[V], inv[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) { mx[j] = -INFINITY; inv[j] = 0.f; }
+  for (int k = 0; k < K; ++k) {
+    const Vec v = zn[(size_t)k * ld];
+#pragma unroll
+    for (int j = 0; j < V; ++j) mx[j] = fmaxf(mx[j], v.f[j]);
+  }
+  for (int k = 0; k < K; ++k) {
+    const Vec v = zn[(size_t)k * ld];
+#pragma unroll
+    for (int j = 0; j < V; ++j) inv[j] += expf(v.f[j] - mx[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < V; ++j) inv[j] = 1.f / inv[j];
+  const int wave = threadIdx.x >> 6, nq = 1 + C;
+  for (int k = 0; k < K; ++k) {
+    const Vec v = zn[(size_t)k * ld];
+    double a[MS_NSTAT];
+#pragma unroll
+    for (int r = 0; r < MS_NSTAT; ++r) a[r] = 0.0;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const double w = (double)(mv.f[j] * crf_prob(v.f[j], mx[j], inv[j]));
+      a[0] += w;
+#pragma unroll
+      for (int r = 0; r < CRF_MAXC; ++r) a[1 + r] += w * (double)xv[r].f[j];
+    }
+#pragma unroll
+    for (int r = 0; r < MS_NSTAT; ++r) {
+      if (r < nq) {                                  // (uniform)
+        const double t = pp_wave_sum_d(a[r]);
+        if ((threadIdx.x & 63) == 0) sh[k * nq + r][wave] = t;
+      }
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < K * nq) {
+    const double* w = sh[threadIdx.x];
+    partial[((size_t)n * gridDim.x + blockIdx.x) * K * nq + threadIdx.x] = ((w[0] + w[1]) + w[2]) + w[3];
+  }
+}
+
+// stats[n][c] = {S, mu_0 .. mu_{C-1}} and statf[n][c] = {active, mu_0 .. mu_3}: block (n, c) adds that image's blocks, thread t
+// blocks t, t + 256, ... in order, then the butterfly -- one quantity after the other
+__global__ __launch_bounds__(256) void ms_stats_kernel(const double* __restrict__ partial, int bpi, int K, int C,
+                                                       double* __restrict__ stats, float* __restrict__ statf) {
+  __shared__ double sh[MS_NSTAT][4];
+  const int n = blockIdx.x / K, c = blockIdx.x - n * K, nq = 1 + C;
+  const double* p = partial + ((size_t)n * bpi * K + c) * nq;
+  for (int r = 0; r < nq; ++r) {
+    double a = 0.0;
+    for (int i = threadIdx.x; i < bpi; i += 256) a += p[(size_t)i * K * nq + r];
+    a = pp_wave_sum_d(a);
+    if ((threadIdx.x & 63) == 0) sh[r][threadIdx.x >> 6] = a;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double S = ((sh[0][0] + sh[0][1]) + sh[0][2]) + sh[0][3];
+  const bool active = S > MS_S_MIN;
+  double* o = stats + (size_t)blockIdx.x * nq;
+  float* of = statf + (size_t)blockIdx.x * MS_NSTAT;
+  o[0] = S;
+  of[0] = active ? 1.f : 0.f;
+  for (int r = 0; r < CRF_MAXC; ++r) {
+    double mu = 0.0;
+    if (r < C && active) mu = (((sh[1 + r][0] + sh[1 + r][1]) + sh[1 + r][2]) + sh[1 + r][3]) / S;
+    if (r < C) o[1 + r] = mu;
+    of[1 + r] = (float)mu;
+  }
+}
+
+__device__ __forceinline__ float ms_sign(float a, float b) { return (a > b ? 1.f : 0.f) - (a < b ? 1.f : 0.f); }
+
+__global__ __launch_bounds__(MS_THREADS) void ms_energy_kernel(const float* __restrict__ z, const float* __restrict__ img,
+                                                               const float* __restrict__ mask, const float* __restrict__ statf,
+                                                               int K, int C, int H, int W, float lambda,
+                                                               float* __restrict__ unit /*(N,K,H,W) or null*/,
+                                                               double* __restrict__ partial /*[blocks][2]*/) {
+  extern __shared__ float ms_lds[];                  // [K + 1][MS_LH][MS_LW]: the classes' probabilities, then the mask
+  __shared__ double shd[2][MS_THREADS / 64];
+  constexpr int PL = MS_LH * MS_LW;
+  const int HW = H * W, n = blockIdx.z, x0 = blockIdx.x * MS_TW, y0 = blockIdx.y * MS_TH;
+  const float* zn = z + (size_t)n * K * HW;
+  const float* mn = mask ? mask + (size_t)n * HW : nullptr;
+  for (int s = threadIdx.x; s < PL; s += MS_THREADS) {
+    const int sy = s / MS_LW, sx = s - sy * MS_LW;
+    const int py = y0 - 1 + sy, px = x0 - 1 + sx;
+    if (px >= 0 && px < W && py >= 0 && py < H) {
+      const int sq = py * W + px;
+      float mx, inv;
+      crf_softmax_norm(zn + sq, K, HW, mx, inv);
+      for (int c = 0; c < K; ++c) ms_lds[c * PL + s] = crf_prob(zn[(size_t)c * HW + sq], mx, inv);
+      ms_lds[K * PL + s] = mn ? mn[sq] : 1.f;
+    } else {
+      for (int c = 0; c <= K; ++c) ms_lds[c * PL + s] = 0.f;
+    }
+  }
+  __syncthreads();
+  const int lx = threadIdx.x & (MS_TW - 1), ly = threadIdx.x / MS_TW;
+  const int gx = x0 + lx, gy = y0 + ly;
+  const bool inside = gx < W && gy < H;
+  const int q = inside ? gy * W + gx : 0;
+  const int ls = (ly + 1) * MS_LW + lx + 1;
+  const float* ml = ms_lds + K * PL;
+  // (0 outside the image, so a lane outside the image adds nothing and a neighbour outside it neither)
+  const float mi = ml[ls];
+  const float wl = mi * ml[ls - 1], wr = mi * ml[ls + 1], wu = mi * ml[ls - MS_LW], wd = mi * ml[ls + MS_LW];
+  float xi[CRF_MAXC];
+#pragma unroll
+  for (int r = 0; r < CRF_MAXC; ++r) xi[r] = (r < C && inside) ? img[((size_t)n * C + r) * HW + q] : 0.f;
+  const float* sf = statf + (size_t)n * K * MS_NSTAT;
+  float en = 0.f, dot = 0.f;
+  for (int c = 0; c < K; ++c) {
+    const float* pl = ms_lds + c * PL + ls;
+    const float p = pl[0], pL = pl[-1], pR = pl[1], pU = pl[-MS_LW], pD = pl[MS_LW];
+    float e = 0.f;
+#pragma unroll
+    for (int r = 0; r < CRF_MAXC; ++r) { const float t = xi[r] - sf[c * MS_NSTAT + 1 + r]; e = __builtin_fmaf(t, t, e); }
+    e *= mi * sf[c * MS_NSTAT];
+    const float t = (wl * ms_sign(p, pL) + wr * ms_sign(p, pR)) + (wu * ms_sign(p, pU) + wd * ms_sign(p, pD));
+    const float g = __builtin_fmaf(lambda, t, e);
+    dot = __builtin_fmaf(p, g, dot);
+    en += p * e + lambda * (wr * fabsf(p - pR) + wd * fabsf(p - pD));
+  }
+  if (unit && inside) {
+    float* un = unit + (size_t)n * K * HW + q;
+    for (int c = 0; c < K; ++c) {
+      const float* pl = ms_lds + c * PL + ls;
+      const float p = pl[0], pL = pl[-1], pR = pl[1], pU = pl[-MS_LW], pD = pl[MS_LW];
+      float e = 0.f;
+#pragma unroll
+      for (int r = 0; r < CRF_MAXC; ++r) { const float t = xi[r] - sf[c * MS_NSTAT + 1 + r]; e = __builtin_fmaf(t, t, e); }
+      e *= mi * sf[c * MS_NSTAT];
+      const float t = (wl * ms_sign(p, pL) + wr * ms_sign(p, pR)) + (wu * ms_sign(p, pU) + wd * ms_sign(p, pD));
+      un[(size_t)c * HW] = p * (__builtin_fmaf(lambda, t, e) - dot);
+    }
+  }
+  double a = pp_wave_sum_d((double)en), b = pp_wave_sum_d((double)mi);
+  if ((threadIdx.x & 63) == 0) { shd[0][threadIdx.x >> 6] = a; shd[1][threadIdx.x >> 6] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* o = partial + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2;
+    o[0] = ((shd[0][0] + shd[0][1]) + shd[0][2]) + shd[0][3];
+    o[1] = ((shd[1][0] + shd[1][1]) + shd[1][2]) + shd[1][3];
+  }
+}
+
+// dlogits += grad_scale * g_up / D * u: 16-byte accesses, D read on the device (behind the cross-rank reduction of sums)
+__global__ __launch_bounds__(LS_THREADS) void ms_bwd_kernel(const float* __restrict__ unit, const double* __restrict__ sums,
+                                                            int has_mask, const float* __restrict__ g_up, float grad_scale,
+                                                            float* __restrict__ dz, long long n, long long n4) {
+  const double D = has_mask ? fmax(sums[1], 1e-8) : sums[1];
+  const float f = (float)((double)(*g_up * grad_scale) / D);
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+  for (long long i = t; i < n4; i += step) {
+    const float4 u = reinterpret_cast<const float4*>(unit)[i];
+    float4 g = reinterpret_cast<float4*>(dz)[i];
+    g.x = __builtin_fmaf(f, u.x, g.x); g.y = __builtin_fmaf(f, u.y, g.y); g.z = __builtin_fmaf(f, u.z, g.z); g.w = __builtin_fmaf(f, u.w, g.w);
+    reinterpret_cast<float4*>(dz)[i] = g;
+  }
+  for (long long i = n4 * 4 + t; i < n; i += step) dz[i] = __builtin_fmaf(f, unit[i], dz[i]);
+}
+
+// workspace: [N][bpi][K][1 + C] double partials of the sums pass | [tiles][2] double partials of the energy pass |
+// [N][K][MS_NSTAT] float {active, mu}; bpi: blocks per image of the sums pass at ONE pixel per thread (the four-pixel form needs fewer)
+static inline int ms_bpi(int H, int W) { return pp_cdiv((long long)H * W, LS_THREADS); }
+static inline int ms_tiles(int N, int H, int W) { return N * pp_cdiv(H, MS_TH) * pp_cdiv(W, MS_TW); }
+static inline size_t ms_sums_bytes(int N, int K, int C, int H, int W) { return (size_t)N * ms_bpi(H, W) * K * (1 + C) * sizeof(double); }
+
+extern "C" size_t pp_ms_loss_workspace(int N, int K, int C, int H, int W) {
+  if (N < 1 || K < 1 || C < 1 || H < 1 || W < 1) return 0;
+  return ms_sums_bytes(N, K, C, H, W) + (size_t)ms_tiles(N, H, W) * 2 * sizeof(double) + (size_t)N * K * MS_NSTAT * sizeof(float);
+}
+
+extern "C" int pp_ms_loss_fwd(const float* logits, const float* image, const float* valid_mask, int N, int K, int C, int H, int W,
+                              float tv_weight, float* unit_grad, double* stats, double* sums, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PP_CHECK_ARG(logits && image && stats && sums && workspace, "ms_loss_fwd: null pointer");
+  // (N is grid.y of the sums pass and grid.z of the energy pass, the rows of tiles are its grid.y: 65535 each)
+  PP_CHECK_ARG(N >= 1 && N <= 65535 && H >= 1 && H <= 65535 * MS_TH && W >= 1 && (long long)H * W * K < 0x7fffffffLL,
+               "ms_loss_fwd: N=%d (<= 65535) H=%d (<= %d) W=%d", N, H, 65535 * MS_TH, W);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && C >= 1 && C <= CRF_MAXC, "ms_loss_fwd: K=%d (1..%d) C=%d (1..%d)", K, PP_MAXK, C, CRF_MAXC);
+  PP_CHECK_ARG(tv_weight >= 0.f && tv_weight < INFINITY, "ms_loss_fwd: tv_weight=%g (>= 0, finite)", (double)tv_weight);
+  PP_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "ms_loss_fwd: the workspace must be 16-byte aligned");
+  if (workspace_bytes < pp_ms_loss_workspace(N, K, C, H, W)) {
+    pp_set_error("ms_loss_fwd: workspace too small (%zu < %zu)", workspace_bytes, pp_ms_loss_workspace(N, K, C, H, W));
+    return PP_ERR_WORKSPACE;
+  }
+  const int HW = H * W, tiles = ms_tiles(N, H, W);
+  double* part_s = (double*)workspace;
+  double* part_e = (double*)((char*)workspace + ms_sums_bytes(N, K, C, H, W));
+  float* statf = (float*)(part_e + (size_t)tiles * 2);
+  const double P = (double)N * HW;
+  pp_prof_begin(PP_K_LOSS, P * K * (60.0 + 4.0 * C), P * (4.0 * K * (unit_grad ? 3 : 2) + 8.0 * C + 8.0), s);
+  const bool v4 = (HW & 3) == 0 && ((((uintptr_t)logits | (uintptr_t)image | (uintptr_t)valid_mask) & 15) == 0);
+  const int bpi = v4 ? pp_cdiv(HW / 4, LS_THREADS) : ms_bpi(H, W);
+  if (v4)
+    hipLaunchKernelGGL(ms_sums_kernel<4>, dim3(bpi, N), dim3(LS_THREADS), 0, s, logits, image, valid_mask, K, C, HW, part_s);
+  else
+    hipLaunchKernelGGL(ms_sums_kernel<1>, dim3(bpi, N), dim3(LS_THREADS), 0, s, logits, image, valid_mask, K, C, HW, part_s);
+  hipLaunchKernelGGL(ms_stats_kernel, dim3(N * K), dim3(256), 0, s, (const double*)part_s, bpi, K, C, stats, statf);
+  hipLaunchKernelGGL(ms_energy_kernel, dim3(pp_cdiv(W, MS_TW), pp_cdiv(H, MS_TH), N), dim3(MS_THREADS),
+                     (size_t)(K + 1) * MS_LH * MS_LW * sizeof(float), s, logits, image, valid_mask, (const float*)statf, K, C, H, W,
+                     tv_weight, unit_grad, part_e);
+  hipLaunchKernelGGL(crf_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)part_e, tiles, valid_mask ? 1 : 0, P, sums);
+  pp_prof_end(s);
+  return pp_launch_status("ms_loss_fwd");
+}
+
+extern "C" int pp_ms_loss_bwd(const float* unit_grad, const double* sums, int has_mask, const float* g_up, float grad_scale,
+                              float* dlogits, long long n, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PP_CHECK_ARG(unit_grad && sums && g_up && dlogits && n >= 1, "ms_loss_bwd: bad arguments");
+  const long long n4 = ((((uintptr_t)unit_grad | (uintptr_t)dlogits) & 15) == 0) ? n >> 2 : 0;
+  pp_prof_begin(PP_K_LOSS, 2.0 * (double)n, 12.0 * (double)n, s);
+  hipLaunchKernelGGL(ms_bwd_kernel, dim3(ls_blocks(n4 ? n4 : n, 8192)), dim3(LS_THREADS), 0, s, unit_grad, sums, has_mask, g_up, grad_scale,
+                     dlogits, n, n4);
+  pp_prof_end(s);
+  return pp_launch_status("ms_loss_bwd");
+}
+
 // ---------------------------------------------------------------- 95 % Hausdorff distance (inference.py:217-237)
 // The reference calls medpy.metric.binary.hd95(pred == k, label == k, spacing, connectivity 1): the surface of a mask is
 // mask XOR erode(mask, 4-neighbourhood cross, outside = background); each directed set is the Euclidean distance (in

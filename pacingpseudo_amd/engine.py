@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from ._lib import PpBnCoefItem, PpLazyIn, PpPackItem, PpWinoPackItem, lib, lib_for, prof_range, stream_ptr
 from .convop import ConvOp, select as conv_select
-from .losses.losses import check_crf_params, check_nc_params
+from .losses.losses import check_crf_params, check_ms_params, check_nc_params
 
 WINO_ENABLED = os.environ.get('PP_WINO', '1') != '0'      # A/B switch for the Winograd path
 # split-fp16 ("f16x3") direct convolution for the non-Winograd layers with at least this many output channels
@@ -484,8 +484,10 @@ class _Plan:
         # [8:10]: a step without the auxiliary path still reduces one contiguous block.  Its buffers exist in such plans only.
         # The normalised-cut loss (--do_loss_nc) likewise: its pair (pp_nc_loss_fwd: sum NC, N K) directly behind the CRF pair when that
         # exists, else at [6:8], and the auxiliary pair behind it; [0:reg_end] is what a step without the auxiliary path reduces.
-        self.crf = self.nc = None
-        self.all_sums = torch.zeros(8 + (2 if eng.crf is not None else 0) + (2 if eng.nc is not None else 0), device=dev, dtype=torch.float64)
+        # The Mumford-Shah loss (--do_loss_ms) likewise: its pair (pp_ms_loss_fwd: energy, denominator) directly behind the NC pair when
+        # that exists, else behind the CRF pair, else at [6:8]; the auxiliary pair follows last.
+        self.crf = self.nc = self.ms = None
+        self.all_sums = torch.zeros(8 + 2 * sum(x is not None for x in (eng.crf, eng.nc, eng.ms)), device=dev, dtype=torch.float64)
         self.reg_end = 6
         if eng.crf is not None:
             check_crf_params(K=net.num_classes, C=net.input_ch, **eng.crf)
@@ -500,6 +502,14 @@ class _Plan:
             # fin: where pp_losses_finalize's ratio slot (sums[2] / sums[3]) finds the pair
             self.nc = dict(sums=self.all_sums[s0:s0 + 2], fin=self.all_sums[s0 - 2:], ws=torch.empty(nws, device=dev, dtype=torch.uint8),
                            ws_bytes=nws, assoc_vol=torch.zeros((B, net.num_classes, 2), device=dev, dtype=torch.float64),
+                           unit=torch.empty((B, net.num_classes, H, W), **f32) if trainable else None)
+            self.reg_end = s0 + 2
+        if eng.ms is not None:
+            check_ms_params(K=net.num_classes, C=net.input_ch, **eng.ms)
+            nws = lib.pp_ms_loss_workspace(B, net.num_classes, net.input_ch, H, W)
+            s0 = self.reg_end
+            self.ms = dict(sums=self.all_sums[s0:s0 + 2], fin=self.all_sums[s0 - 2:], ws=torch.empty(nws, device=dev, dtype=torch.uint8),
+                           ws_bytes=nws, stats=torch.zeros((B, net.num_classes, 1 + net.input_ch), device=dev, dtype=torch.float64),
                            unit=torch.empty((B, net.num_classes, H, W), **f32) if trainable else None)
             self.reg_end = s0 + 2
         self.sums = self.all_sums[:6]
@@ -644,6 +654,10 @@ class StepEngine:
             self.nc = check_nc_params(radius=getattr(args, 'nc_radius', 5), dilation=getattr(args, 'nc_dilation', 1),
                                       sigma_xy=getattr(args, 'nc_sigma_xy', 6.0), sigma_rgb=getattr(args, 'nc_sigma_rgb', 0.1),
                                       K=backbone.num_classes)
+        # --do_loss_ms: the Mumford-Shah level-set loss on the weak logits, handled as the CRF loss is
+        self.ms = None
+        if getattr(args, 'do_loss_ms', False):
+            self.ms = check_ms_params(tv_weight=getattr(args, 'ms_tv_weight', 1.0), K=backbone.num_classes)
         self.storage = getattr(args, 'storage', 'fp32') or 'fp32'
         if os.environ.get('PP_ACT_H16', '0') == '1' and self.storage == 'fp32':
             self.storage = 'fp16'
@@ -1400,6 +1414,11 @@ class StepEngine:
                                   B, K, Cin, H, W, c['radius'], c['dilation'], c['sigma_xy'], c['sigma_rgb'],
                                   plan.nc['unit'].data_ptr() if need_grad else None, plan.nc['assoc_vol'].data_ptr(),
                                   plan.nc['sums'].data_ptr(), plan.nc['ws'].data_ptr(), plan.nc['ws_bytes'], st)
+        do_ms_loss = bool(train and plan.ms is not None)
+        if do_ms_loss:                                      # (the mask as for the CRF loss: whenever the batch has one)
+            plan.K.pp_ms_loss_fwd(logits.data_ptr(), image.data_ptr(), valid_mask.data_ptr() if valid_mask is not None else None,
+                                  B, K, Cin, H, W, self.ms['tv_weight'], plan.ms['unit'].data_ptr() if need_grad else None,
+                                  plan.ms['stats'].data_ptr(), plan.ms['sums'].data_ptr(), plan.ms['ws'].data_ptr(), plan.ms['ws_bytes'], st)
         if do_aux:
             if side is not None:
                 torch.cuda.current_stream().wait_event(plan.aux_join)
@@ -1408,7 +1427,7 @@ class StepEngine:
             ax, a = self.aux, plan.aux
             drop, feat, wfc, logits_aux = A['drop'], A['feat'], A['wfc'], A['logits_aux']
         if self.comm is not None:
-            self.comm.allreduce_sums(plan.all_sums if do_aux else (plan.all_sums[:plan.reg_end] if (do_crf_loss or do_nc_loss) else plan.sums))
+            self.comm.allreduce_sums(plan.all_sums if do_aux else (plan.all_sums[:plan.reg_end] if (do_crf_loss or do_nc_loss or do_ms_loss) else plan.sums))
         out = {}
         loss_pce = torch.empty((), device=dev, dtype=torch.float32)
         loss_ent = torch.empty((), device=dev, dtype=torch.float32) if do_ent else None
@@ -1432,6 +1451,11 @@ class StepEngine:
             loss_nc = torch.empty((), device=dev, dtype=torch.float32)
             plan.K.pp_losses_finalize(plan.nc['fin'].data_ptr(), 0, None, loss_nc.data_ptr(), None, st)
             out['loss_nc'] = loss_nc
+        if do_ms_loss:
+            # energy / D over the ranks: the masked-ratio slot, D = max(sum m, 1e-8) with a mask
+            loss_ms = torch.empty((), device=dev, dtype=torch.float32)
+            plan.K.pp_losses_finalize(plan.ms['fin'].data_ptr(), 1 if valid_mask is not None else 0, None, loss_ms.data_ptr(), None, st)
+            out['loss_ms'] = loss_ms
 
         if do_aux:
             loss_aux = torch.empty((), device=dev, dtype=torch.float32)
@@ -1460,6 +1484,8 @@ class StepEngine:
                 self.last.update(do_crf=True, crf_mask=crf_mask)
             if do_nc_loss:
                 self.last.update(do_nc=True)
+            if do_ms_loss:
+                self.last.update(do_ms=True, ms_mask=valid_mask is not None)
         return out
 
     def _aux_input(self, plan, aux_group, st) -> View:
@@ -1555,6 +1581,9 @@ class StepEngine:
             if S.get('do_nc') and gp('loss_nc') is not None:
                 plan.K.pp_nc_loss_bwd(plan.nc['unit'].data_ptr(), plan.nc['sums'].data_ptr(), gp('loss_nc'), plan.loss_scale,
                                       plan.dlogits.data_ptr(), B * K * H * W, st)
+            if S.get('do_ms') and gp('loss_ms') is not None:
+                plan.K.pp_ms_loss_bwd(plan.ms['unit'].data_ptr(), plan.ms['sums'].data_ptr(), 1 if S['ms_mask'] else 0, gp('loss_ms'),
+                                      plan.loss_scale, plan.dlogits.data_ptr(), B * K * H * W, st)
         with prof_range('backward: decoder'):
             g6 = self._unet_backward_decoder(plan, S['bn_training'], grads, st)
         if S['do_aux']:

@@ -1,1 +1,1 @@
-from .losses import normalized_cut_loss  # noqa: F401
+from .losses import mumford_shah_loss, normalized_cut_loss  # noqa: F401

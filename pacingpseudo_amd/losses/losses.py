@@ -321,6 +321,77 @@ def normalized_cut_loss(input, image, valid_mask=None, radius=5, dilation=1, sig
     return _NcLoss.apply(z, x, m, prm)
 
 
+MS_MAX_CHANNELS, MS_MAX_CLASSES = 4, 32
+
+
+def check_ms_params(tv_weight=1.0, K=None, C=None) -> dict:
+    """The accepted ranges of the Mumford-Shah level-set loss (include/pacingpseudo_hip.h: pp_ms_loss_fwd), checked before any
+    launch: ValueError for a total-variation weight that is negative or not finite, NotImplementedError for more classes or image
+    channels than the kernels take.  Returns the normalised parameters."""
+    import math
+    try:
+        tv_weight = float(tv_weight)
+    except (TypeError, ValueError):
+        raise ValueError(f'Mumford-Shah: tv_weight must be a number (got {tv_weight!r})') from None
+    if not (tv_weight >= 0.0 and math.isfinite(tv_weight)):
+        raise ValueError(f'Mumford-Shah: tv_weight must be >= 0 and finite (got {tv_weight!r})')
+    if K is not None and not 1 <= K <= MS_MAX_CLASSES:
+        raise NotImplementedError(f'Mumford-Shah: 1 .. {MS_MAX_CLASSES} classes (got {K})')
+    if C is not None and not 1 <= C <= MS_MAX_CHANNELS:
+        raise NotImplementedError(f'Mumford-Shah: 1 .. {MS_MAX_CHANNELS} image channels (got {C})')
+    return dict(tv_weight=tv_weight)
+
+
+class _MsLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, image, mask, prm):
+        N, K, H, W = z.shape
+        C = image.shape[1]
+        st = stream_ptr()
+        dev = z.device
+        # [2:4] = energy, denominator: where pp_losses_finalize's masked-ratio slot reads them
+        sums = torch.zeros(4, device=dev, dtype=torch.float64)
+        stats = torch.empty((N, K, 1 + C), device=dev, dtype=torch.float64)
+        nws = lib.pp_ms_loss_workspace(N, K, C, H, W)
+        ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+        unit = torch.empty_like(z) if ctx.needs_input_grad[0] else None
+        lib.pp_ms_loss_fwd(z.data_ptr(), image.data_ptr(), mask.data_ptr() if mask is not None else None, N, K, C, H, W,
+                           prm['tv_weight'], unit.data_ptr() if unit is not None else None, stats.data_ptr(), sums[2:].data_ptr(),
+                           ws.data_ptr(), nws, st)
+        out = torch.empty((), device=dev, dtype=torch.float32)
+        lib.pp_losses_finalize(sums.data_ptr(), 1 if mask is not None else 0, None, out.data_ptr(), None, st)
+        ctx.unit, ctx.sums, ctx.has_mask = unit, sums, mask is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        unit = ctx.unit
+        g = g.to(torch.float32).contiguous()
+        dz = torch.zeros_like(unit)
+        lib.pp_ms_loss_bwd(unit.data_ptr(), ctx.sums[2:].data_ptr(), 1 if ctx.has_mask else 0, g.data_ptr(), 1.0, dz.data_ptr(),
+                           unit.numel(), stream_ptr())
+        return dz, None, None, None
+
+
+def mumford_shah_loss(input, image, valid_mask=None, tv_weight=1.0):
+    """Mumford-Shah level-set loss with an anisotropic total-variation term (this implementation's addition; the reference has no
+    such loss): (1/D) (sum_nci m_i p_ic |x_i - mu_nc|^2 + tv_weight sum_nc sum_(i,j) m_i m_j |p_ic - p_jc|) with p = softmax(input),
+    mu_nc the m p-weighted mean of the `image` channels over image n (a class with sum_i m_i p_ic <= 1e-6 in an image adds no
+    level-set term), (i, j) the vertical and horizontal neighbour pairs, D = N H W or max(sum(valid_mask), 1e-8).  Differentiable
+    in `input` only."""
+    z, x = _check(input, 'input'), _check(image, 'image')
+    N, K, H, W = z.shape
+    if x.shape[0] != N or tuple(x.shape[2:]) != (H, W):
+        raise ValueError(f'image must be (N,C,H,W) with the N, H, W of input {tuple(z.shape)}, got {tuple(x.shape)}')
+    m = None
+    if valid_mask is not None:
+        m = _check(valid_mask, 'valid_mask')
+        if tuple(m.shape) != (N, 1, H, W):
+            raise ValueError(f'valid_mask must be {(N, 1, H, W)}, got {tuple(m.shape)}')
+    prm = check_ms_params(tv_weight, K=K, C=x.shape[1])
+    return _MsLoss.apply(z, x, m, prm)
+
+
 class _WeightedSum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weights, *terms):

@@ -26,7 +26,7 @@ from .aux_path_memory import AuxPath
 from ..engine import StepEngine
 from ..flat import FlatSlab
 
-_LOSS_KEYS = ('loss_pce', 'loss_ent', 'loss_cr', 'loss_crf', 'loss_nc', 'loss_aux_cls', 'loss_memory')
+_LOSS_KEYS = ('loss_pce', 'loss_ent', 'loss_cr', 'loss_crf', 'loss_nc', 'loss_ms', 'loss_aux_cls', 'loss_memory')
 
 
 class _StepFunction(torch.autograd.Function):
@@ -115,6 +115,8 @@ class ConsistencyRegulr(nn.Module):
                 keys.append('loss_crf')
             if getattr(a, 'do_loss_nc', False):
                 keys.append('loss_nc')
+            if getattr(a, 'do_loss_ms', False):
+                keys.append('loss_ms')
             if a.do_aux_path:
                 keys += ['logits_aux_cls', 'loss_aux_cls']
                 if a.do_memory:

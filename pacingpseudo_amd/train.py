@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import resume
-from .losses.losses import check_crf_params, check_nc_params
+from .losses.losses import check_crf_params, check_ms_params, check_nc_params
 from .optim import add_clip_flag, add_ema_flags, log_clip_stats, positive_float, positive_int
 
 parser = argparse.ArgumentParser(description='PacingPseudo training on MI355X (flag surface of the reference driver)')
@@ -167,6 +167,16 @@ parser.add_argument('--nc_radius', type=positive_int, default=5, help='neighbour
 parser.add_argument('--nc_dilation', type=positive_int, default=1, help='spacing d of the neighbourhood offsets in pixels (1 .. 4, r * d <= 16)')
 parser.add_argument('--nc_sigma_xy', type=positive_float, default=6.0, help='width of the position kernel, in offsets')
 parser.add_argument('--nc_sigma_rgb', type=positive_float, default=0.1, help='width of the intensity kernel, in units of the network input')
+# Mumford-Shah level-set loss with a total-variation term on the weak-view prediction (pp_ms_loss_*); the reference
+# has no such loss.  It asks that each class region be piecewise constant in the image (a per-image region statistic) and that the class
+# maps have short boundaries; it may be on together with the CRF and the normalised-cut losses
+parser.add_argument('--do_loss_ms', action='store_true',
+                    help='add the Mumford-Shah level-set loss: per image and class the soft-region variance of the image intensities, '
+                         'plus --ms_tv_weight times the anisotropic total variation of the class maps')
+parser.add_argument('--loss_ms_weight', type=float, default=0.1, help='its weight (an untuned first value)')
+parser.add_argument('--ramp_up_loss_ms', action='store_true', help='Gaussian ramp-up of that weight over the epochs (--ramp_up_scale)')
+parser.add_argument('--ms_tv_weight', type=float, default=1.0,
+                    help='weight of the total-variation term inside that loss, >= 0 (an untuned first value)')
 add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
 add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
@@ -218,6 +228,10 @@ def parse_args(argv=None):
         check_nc_params(args.nc_radius, args.nc_dilation, args.nc_sigma_xy, args.nc_sigma_rgb)
     except (ValueError, NotImplementedError) as e:
         parser.error(f'--nc_radius / --nc_dilation / --nc_sigma_xy / --nc_sigma_rgb: {e}')
+    try:
+        check_ms_params(args.ms_tv_weight)
+    except (ValueError, NotImplementedError) as e:
+        parser.error(f'--ms_tv_weight: {e}')
     return args
 
 
@@ -353,6 +367,7 @@ def train_interface(args, resume_state=None):
         acc = torch.zeros(7, device=device, dtype=torch.float64)
         acc_crf = torch.zeros(1, device=device, dtype=torch.float64) if args.do_loss_crf else None      # sum crf*n (--do_loss_crf only)
         acc_nc = torch.zeros(1, device=device, dtype=torch.float64) if args.do_loss_nc else None        # sum nc*n (--do_loss_nc only)
+        acc_ms = torch.zeros(1, device=device, dtype=torch.float64) if args.do_loss_ms else None        # sum ms*n (--do_loss_ms only)
         n_img = 0
         for idx, batch in enumerate(train_loader):
             if args.max_iters and idx >= args.max_iters:
@@ -373,6 +388,8 @@ def train_interface(args, resume_state=None):
                      else args.loss_crf_weight)
             w_nc = (gaussian_ramp_up(t=curr_epoch, base_value=args.loss_nc_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_nc
                     else args.loss_nc_weight)
+            w_ms = (gaussian_ramp_up(t=curr_epoch, base_value=args.loss_ms_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_ms
+                    else args.loss_ms_weight)
 
             def assemble(out, _epoch=None):
                 # train_chaos.py:273-310: pce + ent * w_ent + cr * w_cr + aux * w_aux + memory * w_mem -- one launch each way
@@ -390,6 +407,8 @@ def train_interface(args, resume_state=None):
                     terms.append(out['loss_crf']); weights.append(w_crf)
                 if args.do_loss_nc:
                     terms.append(out['loss_nc']); weights.append(w_nc)
+                if args.do_loss_ms:
+                    terms.append(out['loss_ms']); weights.append(w_ms)
                 return weighted_loss_sum(terms, weights)
             if args.graph_step and n == args.batch_size:      # (a ragged last batch runs eagerly: another shape, another plan)
                 if graph_step is None:
@@ -416,10 +435,12 @@ def train_interface(args, resume_state=None):
                 acc_crf[0] += net_outputs['loss_crf'].detach() * (w_crf * n)
             if args.do_loss_nc:
                 acc_nc[0] += net_outputs['loss_nc'].detach() * (w_nc * n)
+            if args.do_loss_ms:
+                acc_ms[0] += net_outputs['loss_ms'].detach() * (w_ms * n)
             acc[5] += n
             acc[6] += 1
             n_img += n
-        extra = [t for t in (acc_crf, acc_nc) if t is not None]                        # [7] crf when on, nc behind it
+        extra = [t for t in (acc_crf, acc_nc, acc_ms) if t is not None]                # [7] crf when on, nc behind it, ms last
         a = (torch.cat([acc] + extra) if extra else acc).cpu().numpy()      # the one host sync of the epoch
         epoch_toc = time.time()
         cnt, its = max(a[5], 1), max(a[6], 1)
@@ -447,6 +468,9 @@ def train_interface(args, resume_state=None):
             i_nc = 8 if args.do_loss_crf else 7
             if args.do_loss_nc:
                 crf_col += ", loss_nc: {:.6f}".format(a[i_nc] / cnt)
+            i_ms = i_nc + (1 if args.do_loss_nc else 0)
+            if args.do_loss_ms:
+                crf_col += ", loss_ms: {:.6f}".format(a[i_ms] / cnt)
             logging.info("epoch: {:03d}, lr: {:.6f}, loss_pce: {:.6f}, loss_ent: {:.6f}, loss_cr: {:.6f}, loss_aux_cls: {:.6f}, "
                          "loss_memory: {:.6f}{}, {:.2f} s/epoch".format(curr_epoch, new_lr, a[0] / cnt, a[1] / cnt, a[2] / cnt,
                                                                        a[3] / cnt, a[4] / its, crf_col, epoch_toc - epoch_tic))
@@ -477,6 +501,8 @@ def train_interface(args, resume_state=None):
                 scalars.add('train/loss_crf', a[7] / cnt, curr_epoch)
             if args.do_loss_nc:
                 scalars.add('train/loss_nc', a[i_nc] / cnt, curr_epoch)
+            if args.do_loss_ms:
+                scalars.add('train/loss_ms', a[i_ms] / cnt, curr_epoch)
             scalars.add('lr/current_lr', new_lr, curr_epoch)
             scalars.add('losses/loss_pce_val', loss_pce_val, curr_epoch)
             for i, nm in enumerate(names):

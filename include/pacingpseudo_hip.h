@@ -502,7 +502,8 @@ int pp_seg_losses_bwd(const float* logits_w, const float* logits_s, const int64_
                       const double* sums, const float* g_pce, const float* g_ent, const float* g_cr,
                       float grad_scale, float* dlogits_w, float* dlogits_s, void* stream);
 /* auxiliary head: F.interpolate(logits (N,K,h,w) -> (H,W), bilinear, align_corners) fused with partial CE.
- * sums[2] = pCE sum, #labelled. */
+ * sums[2] = pCE sum, #labelled.  workspace >= 16 bytes (two doubles) per block of its grid of min(1024, ceil(N * H * W / 256))
+ * blocks; pp_seg_losses_workspace(N, H * W), 40 bytes per block of the same grid, covers it (how the engine sizes it). */
 int pp_aux_pce_fwd(const float* lo, int N, int K, int h, int w, int H, int W, const int64_t* target,
                    int ignore_index, float* logits_up, double* sums, void* workspace, size_t workspace_bytes,
                    void* stream);

@@ -1948,8 +1948,8 @@ extern "C" int pp_ms_loss_bwd(const float* unit_grad, const double* sums, int ha
 // mask XOR erode(mask, 4-neighbourhood cross, outside = background); each directed set is the Euclidean distance (in
 // units of the pixel spacing) from every surface pixel of one mask to the nearest surface pixel of the other, and the
 // metric is the 95th percentile of both sets together.  Per (image, class): one block compacts the two surfaces into
-// coordinate lists (order irrelevant: only minima and a percentile are taken), then every surface pixel scans the
-// other list staged through LDS.  dist: [N][K][2][cap] floats, counts: [N][K][4] = {surface a, surface b, |a|, |b|}.
+// coordinate lists (row-major order: the distance sets come out in the same order in every run), then every surface pixel scans
+// the other list staged through LDS.  dist: [N][K][2][cap] floats, counts: [N][K][4] = {surface a, surface b, |a|, |b|}.
 #define HD_THREADS 256
 __global__ __launch_bounds__(HD_THREADS) void hd_surface_kernel(const long long* __restrict__ pred, const long long* __restrict__ label,
                                                                 int K, int H, int W, int cap, int* __restrict__ coords,
@@ -1960,24 +1960,41 @@ __global__ __launch_bounds__(HD_THREADS) void hd_surface_kernel(const long long*
   int* ca = coords + ((size_t)blockIdx.x * 2 + 0) * cap;
   int* cb = coords + ((size_t)blockIdx.x * 2 + 1) * cap;
   int* cnt = counts + (size_t)blockIdx.x * 4;
-  __shared__ int na, nb, ta, tb;
-  if (threadIdx.x == 0) { na = 0; nb = 0; ta = 0; tb = 0; }
-  __syncthreads();
+  // Ordered compaction: the lists hold the surface pixels in row-major order whatever the waves' schedule (ballot + population
+  // count inside a wave, the waves' totals through LDS).  An append through an LDS counter gave the same SET in an order that
+  // changed from run to run; pp_surface_reduce adds the distances in storage order, so its sums inherit the order.
+  __shared__ int wa[HD_THREADS / 64], wb[HD_THREADS / 64];
+  __shared__ int ta, tb;
+  if (threadIdx.x == 0) { ta = 0; tb = 0; }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long lt_mask = (1ull << lane) - 1ull;
+  int na = 0, nb = 0;                                           // list lengths so far: the same in every thread
   int my_ta = 0, my_tb = 0;
-  for (int p = threadIdx.x; p < H * W; p += HD_THREADS) {
-    const int y = p / W, x = p % W;
-    const bool a = A[p] == k, b = B[p] == k;
-    my_ta += a; my_tb += b;
-    if (a) {
-      const bool inner = y > 0 && y < H - 1 && x > 0 && x < W - 1 && A[p - W] == k && A[p + W] == k && A[p - 1] == k && A[p + 1] == k;
-      if (!inner) { const int i = atomicAdd(&na, 1); if (i < cap) ca[i] = p; }
+  for (int p0 = 0; p0 < H * W; p0 += HD_THREADS) {              // uniform trip count: the barriers below are reached by all
+    const int p = p0 + threadIdx.x;
+    bool sa = false, sb = false;
+    if (p < H * W) {
+      const int y = p / W, x = p % W;
+      const bool a = A[p] == k, b = B[p] == k;
+      const bool border = !(y > 0 && y < H - 1 && x > 0 && x < W - 1);
+      my_ta += a; my_tb += b;
+      sa = a && (border || !(A[p - W] == k && A[p + W] == k && A[p - 1] == k && A[p + 1] == k));
+      sb = b && (border || !(B[p - W] == k && B[p + W] == k && B[p - 1] == k && B[p + 1] == k));
     }
-    if (b) {
-      const bool inner = y > 0 && y < H - 1 && x > 0 && x < W - 1 && B[p - W] == k && B[p + W] == k && B[p - 1] == k && B[p + 1] == k;
-      if (!inner) { const int i = atomicAdd(&nb, 1); if (i < cap) cb[i] = p; }
+    const unsigned long long ma = __ballot(sa), mb = __ballot(sb);
+    if (lane == 0) { wa[wave] = __popcll(ma); wb[wave] = __popcll(mb); }
+    __syncthreads();
+    int oa = na, ob = nb;
+#pragma unroll
+    for (int q = 0; q < HD_THREADS / 64; ++q) {
+      if (q < wave) { oa += wa[q]; ob += wb[q]; }
+      na += wa[q]; nb += wb[q];
     }
+    if (sa) { const int i = oa + __popcll(ma & lt_mask); if (i < cap) ca[i] = p; }
+    if (sb) { const int i = ob + __popcll(mb & lt_mask); if (i < cap) cb[i] = p; }
+    __syncthreads();                                            // wa / wb are rewritten by the next trip
   }
-  atomicAdd(&ta, my_ta);
+  atomicAdd(&ta, my_ta);                                        // integer: order independent
   atomicAdd(&tb, my_tb);
   __syncthreads();
   if (threadIdx.x == 0) { cnt[0] = na; cnt[1] = nb; cnt[2] = ta; cnt[3] = tb; }

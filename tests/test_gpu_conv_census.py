@@ -17,6 +17,13 @@ A second recording (tests/_launch_census.py::record_batches) runs batch 3 and 12
 128-pixel images, one test case per configuration; an edge table feeds hand-made launches to the same adapters at the states of
 the launch plans (asserted through the library's plan queries), and a planted-mistake test shows the gate fails when an entry
 point is called wrongly.
+Every operand of a replay -- inputs, outputs, kept transforms, statistics rows, workspaces -- lies between sentinel bands of 0xFF
+bytes (tests/_guard.py; _Run.d / _Run.out / _ws / _full / _empty / _zeros / _b): a read outside an input's extent that reaches a
+result turns it into NaN and fails the float64 comparison, a write outside an output or a workspace adds a failing result line
+'<buffer> band'.  A workspace is EXACTLY as large as the query include/pacingpseudo_hip.h names for that launch returns (what the
+engine allocates for it) and starts as 0xFF, so a query that is too small, a kernel that writes a few bytes past it and a kernel
+that relies on what an earlier layer left in the workspace all show.  The run's entry-point table (_Checked) holds every device
+pointer of a launch to this: one that points into no banded buffer of the run is a failing result line.
 A recorded launch without a replay adapter fails the census by name.  Outside the census: the stand-alone AuxPath.forward (it calls
 the library directly, not through a plan) and --precision fp16 (fp16-grade by design, tested on its own).
 """
@@ -28,6 +35,8 @@ from collections import defaultdict
 import pytest
 import torch
 import torch.nn.functional as F
+
+from tests._guard import BandSet
 
 pytestmark = pytest.mark.gpu
 
@@ -112,17 +121,48 @@ def _nhwc(t):
     return t.permute(0, 2, 3, 1)
 
 
+class _Checked:
+    """The entry-point table of a run: before a launch goes out, every device pointer it is handed (a void* argument; the
+    stream, null pointers, host item tables and the pointers inside a lazy-input struct are not looked at) must point into the
+    payload of a banded buffer of this run.  One that does not adds a failing result line naming the argument, so an operand that
+    slipped past the bands cannot go unnoticed.  Adapters reach the library through run.K (the entry under test) or _L() (helper
+    launches: packs, statistics, loss finalisation); both are wrapped."""
+
+    def __init__(self, inner, run):
+        self._inner, self._run = inner, run
+
+    def __getattr__(self, name):
+        fn = getattr(self._inner, name)
+        from tests._launch_census import is_launch
+        if not is_launch(name):
+            return fn
+
+        def call(*a):
+            from pacingpseudo_amd._lib import _PROTOS
+            spans = [(b.data_ptr(), b.data_ptr() + b.nbytes) for _, b in self._run.bands.items]
+            for i, (t, v) in enumerate(zip(_PROTOS[name][1][:-1], a)):
+                if t is ctypes.c_void_p and isinstance(v, int) and v and not any(lo <= v < hi or v == lo == hi for lo, hi in spans):
+                    self._run.res.append((f'{name} argument {i} points into no banded buffer', None, False, None, False))
+            return fn(*a)
+        return call
+
+
 class _Run:
     """One execution of a launch: K = entry-point table, dt = activation dtype; collects (label, device result, fp64 reference,
     tolerance, is-activation) and canary verdicts."""
 
     def __init__(self, K, dt, want_ref):
         from pacingpseudo_amd._lib import stream_ptr
-        self.K, self.dt, self.want_ref, self.st = K, dt, want_ref, stream_ptr()
+        self.K, self.dt, self.want_ref, self.st = _Checked(K, self), dt, want_ref, stream_ptr()
         self.res, self.keep = [], []
+        from pacingpseudo_amd._lib import lib
+        self.L = _Checked(lib, self)          # the fp32 table for helper launches beside the one under test: checked alike
+        self.bands = BandSet(0xFF, _dev())        # every operand of the launch made through d / out / _ws / _full / _empty / _zeros / _b
 
     def d(self, t, act=True):
-        x = t.to(_dev()).to(self.dt if act else torch.float32).contiguous()
+        """t on the device in the run's activation type (act) or fp32, between sentinel bands -- inputs too: a read outside an
+        input's extent that reaches a result makes it NaN."""
+        x = self.bands.tensor(t, self.dt if act else torch.float32)
         self.keep.append(x)
         return x
 
@@ -143,12 +183,51 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+_CUR = [None]       # the _Run whose adapter is executing (replay sets it): where the helpers below register their buffers
+
+
+def _L():
+    """The library for an adapter's helper launches and size queries: inside a replay the run's checked fp32 table."""
+    from pacingpseudo_amd._lib import lib
+    return _CUR[0].L if _CUR[0] is not None else lib
+
+
+def _bands():
+    if _CUR[0] is None:
+        raise RuntimeError('an operand helper of the census was called outside a replay: its bands would never be read')
+    return _CUR[0].bands
+
+
+def _shape(shape):
+    return tuple(shape[0]) if len(shape) == 1 and isinstance(shape[0], (tuple, list, torch.Size)) else tuple(shape)
+
+
 def _ws(n):
-    return torch.empty(max(int(n), 1) + 64, dtype=torch.uint8, device=_dev())
+    """A workspace of EXACTLY n bytes (the size the header's query returns for the launch, which is what the engine allocates
+    for it), stale (0xFF) and with a sentinel band behind it (tests/_guard.py)."""
+    return _bands().ws(int(n))
+
+
+def _full(shape, value, dtype=torch.float32):
+    return _bands().tensor(_shape((shape,)), dtype, fill=value)
+
+
+def _zeros(*shape, dtype=torch.float32):
+    return _bands().tensor(_shape(shape), dtype, fill=0)
+
+
+def _empty(*shape, dtype=torch.float32):
+    """an uninitialised buffer between bands: the payload starts as 0xFF (NaN / -1), so reading an element nobody wrote shows."""
+    return _bands().tensor(_shape(shape), dtype)
+
+
+def _b(t):
+    """t (any device) as a banded device tensor of the same type"""
+    return _bands().tensor(t)
 
 
 def _amax(t):
-    return t.float().abs().max().reshape(1).contiguous()
+    return _b(t.float().abs().max().reshape(1))
 
 
 def _cudnn_off():
@@ -157,8 +236,9 @@ def _cudnn_off():
 
 # ---------------------------------------------------------------------------------------------------------------- adapters
 def _pack_direct(w, O_, I, f16):
-    from pacingpseudo_amd._lib import lib, stream_ptr
-    wf, wb = torch.zeros(O_, 9, I, device=_dev()), torch.zeros(I, 9, O_, device=_dev())
+    from pacingpseudo_amd._lib import stream_ptr
+    lib = _L()
+    wf, wb = _zeros(O_, 9, I), _zeros(I, 9, O_)
     (lib.pp_pack_conv3x3_weights_f16x3 if f16 else lib.pp_pack_conv3x3_weights)(w.data_ptr(), O_, I, I, wf.data_ptr(), wb.data_ptr(),
                                                                                   stream_ptr())
     return wf, wb
@@ -166,10 +246,11 @@ def _pack_direct(w, O_, I, f16):
 
 def _pack_wino(w, O_, I, tile, f16, K=None):
     """U of the geometry's tile, packed through the entry-point table K of the run (a stand-in table can pack wrongly)."""
-    from pacingpseudo_amd._lib import lib, stream_ptr
+    from pacingpseudo_amd._lib import stream_ptr
+    lib = _L()
     K = lib if K is None else K
     n = (tile + 2) ** 2
-    uf, ub = torch.zeros(n, O_, I, device=_dev()), torch.zeros(n, I, O_, device=_dev())
+    uf, ub = _zeros(n, O_, I), _zeros(n, I, O_)
     (K.pp_wino_pack_weights_f16x3 if f16 else K.pp_wino_pack_weights)(w.data_ptr(), O_, I, tile, uf.data_ptr(), ub.data_ptr(),
                                                                       stream_ptr())
     return uf, ub
@@ -187,7 +268,7 @@ def _conv_in(ops, lz, run, ld, C, B, H, W, scale=1.0):
     st = PpLazyIn(cd.data_ptr(), lz[1], lz[2])
     run.keep.append(st)
     xd = run.d(x)
-    y = torch.empty_like(xd)
+    y = _empty(xd.shape, dtype=xd.dtype)
     y.copy_(xd)
     run.K.pp_lazy_materialize(xd.data_ptr(), ld, ctypes.byref(st), y.data_ptr(), ld, C, B, H * W, run.st)
     run.keep.append(y)
@@ -202,8 +283,8 @@ def _direct_fwd(key, run):
     _, ld_in, C, _, bias, _, ld_out, N, B, H, W, dil, acc = a[:13]
     ops = _Ops(key)
     x, _, x64, _ = _conv_in(ops, None, run, ld_in, C, B, H, W)
-    w = ops.randn(N, C, 3, 3, scale=1 / math.sqrt(9 * C)).to(_dev())
-    b = ops.randn(N).to(_dev())
+    w = _b(ops.randn(N, C, 3, 3, scale=1 / math.sqrt(9 * C)))
+    b = _b(ops.randn(N))
     prior = ops.r(ops.randn(B, H, W, N)) if acc else None
     wf, _ = _pack_direct(w, N, C, f16)
     out = run.out(B, H, W, ld_out, N, prior)
@@ -228,16 +309,16 @@ def _wino_fwd(key, run):
     _, name, a = key
     f16 = name.endswith('_f16x3')
     _, ld_in, C, _, bias, _, ld_out, N, B, H, W, dil, acc, vkeep = a[:14]
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     ops = _Ops(key)
     x, _, x64, _ = _conv_in(ops, None, run, ld_in, C, B, H, W)
-    w = ops.randn(N, C, 3, 3, scale=1 / math.sqrt(9 * C)).to(_dev())
-    b = ops.randn(N).to(_dev())
+    w = _b(ops.randn(N, C, 3, 3, scale=1 / math.sqrt(9 * C)))
+    b = _b(ops.randn(N))
     prior = ops.r(ops.randn(B, H, W, N)) if acc else None
     U, _ = _pack_wino(w, N, C, lib.pp_conv3x3_wino_tile(H, W, dil), f16, run.K)
     nws = lib.pp_conv3x3_wino_workspace(C, N, B, H, W, dil)
     ws = _ws(nws)
-    vk = torch.empty(lib.pp_conv3x3_wino_vkeep_elems(C, B, H, W, dil), device=_dev()) if vkeep else None
+    vk = _empty(lib.pp_conv3x3_wino_vkeep_elems(C, B, H, W, dil)) if vkeep else None
     out = run.out(B, H, W, ld_out, N, prior)
     (run.K.pp_conv3x3_wino_fwd_f16x3 if f16 else run.K.pp_conv3x3_wino_fwd)(
         x.data_ptr(), ld_in, C, U.data_ptr(), _p(b) if bias else None, out.data_ptr(), ld_out, N, B, H, W, dil, acc, _p(vk),
@@ -262,17 +343,17 @@ def _bn_fwd(key, run):
     ops = _Ops(key)
     x, lz, x64, ymat = _conv_in(ops, a[-2] if name.endswith('_lazy') else None, run, ld_in, C, B, H, W)
     stats_ptr = a[21] if wino else a[19]
-    w = ops.randn(N, C, 3, 3, scale=1 / math.sqrt(9 * C)).to(_dev())
-    b = ops.randn(N).to(_dev())
-    sc = (torch.rand(N, generator=ops.g) + 0.5).to(_dev())
-    sh = ops.randn(N).to(_dev())
-    from pacingpseudo_amd._lib import lib
+    w = _b(ops.randn(N, C, 3, 3, scale=1 / math.sqrt(9 * C)))
+    b = _b(ops.randn(N))
+    sc = _b((torch.rand(N, generator=ops.g) + 0.5))
+    sh = _b(ops.randn(N))
+    lib = _L()
     if wino:
         tile = lib.pp_conv3x3_wino_tile(H, W, dil)
         U, _ = _pack_wino(w, N, C, tile, f16, run.K)
         nws = lib.pp_conv3x3_wino_workspace(C, N, B, H, W, dil)
         ws = _ws(nws)
-        vk = torch.empty(lib.pp_conv3x3_wino_vkeep_elems(C, B, H, W, dil), device=_dev()) if vkeep else None
+        vk = _empty(lib.pp_conv3x3_wino_vkeep_elems(C, B, H, W, dil)) if vkeep else None
     else:
         U, _ = _pack_direct(w, N, C, f16)
         am = _amax(x[..., :C]) if in_amax else None
@@ -281,7 +362,7 @@ def _bn_fwd(key, run):
     results = []
     for src, lzs in ((x, lz),) + (((ymat, None),) if lz is not None else ()):
         out = run.out(B, H, W, ld_out, N)
-        stats = torch.full((nst // 8 + 2,), float('nan'), dtype=torch.float64, device=_dev())
+        stats = _full((nst // 8,), float('nan'), dtype=torch.float64)
         sp = stats.data_ptr() if stats_ptr else None
         if wino:
             run.K.pp_conv3x3_wino_fwd_bn(src.data_ptr(), ld_in, C, U.data_ptr(), _p(b) if bias else None, out.data_ptr(), ld_out, N,
@@ -327,11 +408,11 @@ def _bwd_data(key, run):
     _, ld_dz, O_, _, _, ld_dx, I, B, H, W, dil, acc = a[:12]
     ops = _Ops(key)
     dz = run.d(ops.act(B, H, W, ld_dz, O_, ops.gs))
-    w = ops.randn(O_, I, 3, 3, scale=1 / math.sqrt(9 * I)).to(_dev())
+    w = _b(ops.randn(O_, I, 3, 3, scale=1 / math.sqrt(9 * I)))
     prior = ops.r(ops.randn(B, H, W, I, scale=ops.gs)) if acc else None
     dx = run.out(B, H, W, ld_dx, I, prior)
     am = _amax(dz[..., :O_]) if (f16 and a[-2]) else None
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     if wino:
         _, Ub = _pack_wino(w, O_, I, lib.pp_conv3x3_wino_tile(H, W, dil), f16, run.K)
         nws = lib.pp_conv3x3_wino_workspace(O_, I, B, H, W, dil)
@@ -363,7 +444,7 @@ def _bwd_weight(key, run):
     """pp_conv3x3_bwd_weight[_f16x3[_lazy]] / pp_conv3x3_wino_bwd_weight[_f16x3] (kept V: made by the matching forward first)"""
     _, name, a = key
     wino, f16 = 'wino' in name, '_f16x3' in name
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     if wino:
         _, ld_dz, O_, _, ld_x, C, B, H, W, dil, _, acc, vcached = a[:13]
         Cpad, I = C, C
@@ -381,19 +462,20 @@ def _bwd_weight(key, run):
     am = _amax(dz[..., :O_]) if (f16 and a[-3 if name.endswith('_lazy') else -2]) else None
     outs = []
     for src, lzs in ((x, lz),) + (((ymat, None),) if lz is not None else ()):
-        dw = (prior.clone() if acc else torch.full((O_, I, 3, 3), 5.0)).to(_dev())
+        dw = _b(prior.clone() if acc else torch.full((O_, I, 3, 3), 5.0))
         if wino:
-            nws = max(lib.pp_conv3x3_wino_bwd_weight_workspace(O_, C, B, H, W, dil), lib.pp_conv3x3_wino_workspace(C, O_, B, H, W, dil))
+            nws = lib.pp_conv3x3_wino_bwd_weight_workspace(O_, C, B, H, W, dil)
             ws = _ws(nws)
             vk = None
             if vcached:
                 tile = lib.pp_conv3x3_wino_tile(H, W, dil)
-                vk = torch.empty(lib.pp_conv3x3_wino_vkeep_elems(C, B, H, W, dil), device=_dev())
-                uf, _ = _pack_wino(ops.randn(O_, C, 3, 3).to(_dev()), O_, C, tile, f16, run.K)
+                vk = _empty(lib.pp_conv3x3_wino_vkeep_elems(C, B, H, W, dil))
+                uf, _ = _pack_wino(_b(ops.randn(O_, C, 3, 3)), O_, C, tile, f16, run.K)
                 tmp = run.out(B, H, W, O_, O_)
                 fwd = run.K.pp_conv3x3_wino_fwd_f16x3 if f16 else run.K.pp_conv3x3_wino_fwd
-                fwd(src.data_ptr(), ld_x, C, uf.data_ptr(), None, tmp.data_ptr(), O_, O_, B, H, W, dil, 0, vk.data_ptr(), ws.data_ptr(),
-                    nws, run.st)
+                nwf = lib.pp_conv3x3_wino_workspace(C, O_, B, H, W, dil)             # the forward that keeps V: its own workspace
+                fwd(src.data_ptr(), ld_x, C, uf.data_ptr(), None, tmp.data_ptr(), O_, O_, B, H, W, dil, 0, vk.data_ptr(),
+                    _ws(nwf).data_ptr(), nwf, run.st)
             args = (dz.data_ptr(), ld_dz, O_, src.data_ptr(), ld_x, C, B, H, W, dil, dw.data_ptr(), acc, _p(vk), ws.data_ptr(), nws)
             if f16:
                 run.K.pp_conv3x3_wino_bwd_weight_f16x3(*args, _p(am), run.st)
@@ -428,19 +510,19 @@ def _conv1x1(key, run):
     there the lazy form is held to the fp32 twin's float64 reference instead of to the entry fed the stored y."""
     _, name, a = key
     ops = _Ops(key)
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     if 'fwd' in name:
         _, ld_x, C, _, bias, _, K_, N, HW = a[:9]
     else:
         _, _, ld_x, C, _, dxp, ld_dx, _, dbp, K_, N, HW, acc_dx, acc_p = a[:14]
     x, lz, x64, ymat = _conv_in(ops, a[-2] if name.endswith('_lazy') else None, run, ld_x, C, N, HW, 1)
-    w = ops.randn(K_, C, scale=1 / math.sqrt(C)).to(_dev())
+    w = _b(ops.randn(K_, C, scale=1 / math.sqrt(C)))
     y64 = x64.reshape(N, C, HW) if x64 is not None else None
     if 'fwd' in name:
-        b = ops.randn(K_).to(_dev())
+        b = _b(ops.randn(K_))
         outs = []
         for src, lzs in ((x, lz),) + (((ymat, None),) if lz is not None else ()):
-            lo = torch.full((N, K_, HW), 7.0, device=_dev())
+            lo = _full((N, K_, HW), 7.0)
             args = (src.data_ptr(), ld_x, C, w.data_ptr(), _p(b) if bias else None, lo.data_ptr(), K_, N, HW)
             if lzs is not None:
                 run.K.pp_conv1x1_nhwc_to_nchw_fwd_lazy(*args, ctypes.byref(lzs), run.st)
@@ -455,7 +537,7 @@ def _conv1x1(key, run):
             ref = torch.einsum('kc,ncp->nkp', w.double(), y64) + (b.double().view(1, -1, 1) if bias else 0)
         run.check('logits', outs[0], ref, act=False)
         return
-    dl = (ops.randn(N, K_, HW) * ops.gs).to(_dev())
+    dl = _b((ops.randn(N, K_, HW) * ops.gs))
     pdx = ops.r(ops.randn(N, 1, HW, C, scale=ops.gs)) if acc_dx else None
     pdw, pdb = ops.randn(K_, C) * ops.gs, ops.randn(K_) * ops.gs
     nws = lib.pp_conv1x1_bwd_workspace(K_, C, N, HW)
@@ -463,8 +545,8 @@ def _conv1x1(key, run):
     outs = []
     for src, lzs in ((x, lz),) + (((ymat, None),) if lz is not None else ()):
         dx = run.out(N, 1, HW, ld_dx, C, pdx) if dxp else None
-        dw = (pdw if acc_p else torch.full((K_, C), 5.0)).to(_dev())
-        db = (pdb if acc_p else torch.full((K_,), 5.0)).to(_dev())
+        dw = _b(pdw if acc_p else torch.full((K_, C), 5.0))
+        db = _b(pdb if acc_p else torch.full((K_,), 5.0))
         args = (dl.data_ptr(), src.data_ptr(), ld_x, C, w.data_ptr(), _p(dx), ld_dx, dw.data_ptr(), _p(db) if dbp else None, K_, N,
                 HW, acc_dx, acc_p, ws.data_ptr(), nws)
         if lzs is not None:
@@ -495,14 +577,14 @@ def _convtranspose(key, run):
     """pp_convtranspose_fwd / _bwd_data / _bwd_weight (--is_trans_conv, fp32 storage only)"""
     _, name, a = key
     ops = _Ops(key)
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     if name == 'pp_convtranspose_fwd':
         _, ld_x, Cin, _, _, ld_out, Cout, k, N, H, W = a[:11]
     elif name == 'pp_convtranspose_bwd_data':
         _, ld_out, Cout, _, _, ld_x, Cin, k, N, H, W, acc = a[:12]
     else:
         _, ld_out, Cout, _, ld_x, Cin, k, N, H, W, _, acc = a[:12]
-    w = ops.randn(Cin, Cout, k, k, scale=1 / math.sqrt(Cin)).to(_dev())
+    w = _b(ops.randn(Cin, Cout, k, k, scale=1 / math.sqrt(Cin)))
     if name == 'pp_convtranspose_fwd':
         x = run.d(ops.act(N, H, W, ld_x, Cin))
         out = run.out(N, k * H, k * W, ld_out, Cout)
@@ -529,7 +611,7 @@ def _convtranspose(key, run):
         return
     x = run.d(ops.act(N, H, W, ld_x, Cin))
     prior = ops.randn(Cin, Cout, k, k, scale=ops.gs) if acc else None
-    dw = (prior.clone() if acc else torch.full((Cin, Cout, k, k), 5.0)).to(_dev())
+    dw = _b(prior.clone() if acc else torch.full((Cin, Cout, k, k), 5.0))
     nws = lib.pp_convtranspose_bwd_weight_workspace(Cin, Cout, k, N, H, W)
     ws = _ws(nws)
     run.K.pp_convtranspose_bwd_weight(dout.data_ptr(), ld_out, Cout, x.data_ptr(), ld_x, Cin, k, N, H, W, dw.data_ptr(), acc,
@@ -564,7 +646,7 @@ def _wgrad_c1(key, run):
         _, ld_dy, _, ld_z, _, _, _, _, _, training, _, ld_x, H, W, _, acc_dw, _, _, _, acc_p, C, ppg, groups = a[:23]
         P = ppg * groups
     B = P // (groups * H * W)
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     ops = _Ops(key)
     N = B * groups
     x = ops.act(N, H, W, ld_x, 1)
@@ -575,24 +657,27 @@ def _wgrad_c1(key, run):
     gamma, beta = torch.rand(C, generator=ops.g) + 0.5, ops.randn(C)
     gamma[0] = -0.7
     rm, rv = ops.randn(C) * 0.1, torch.rand(C, generator=ops.g) + 0.5
-    coef = torch.empty(4, groups, C, device=_dev())
+    coef = _empty(4, groups, C)
     mean, invstd, scale, shift = (coef[i].data_ptr() for i in range(4))
-    gd, bd = (t.to(_dev()) for t in (gamma, beta))
-    nbt = torch.zeros((), dtype=torch.int64, device=_dev())
-    nws = max(lib.pp_bn_lrelu_bwd_wgrad_c1_workspace(C, P // groups, groups), lib.pp_bn_lrelu_bwd_wgrad_c1_workspace(C, P, 1),
-              lib.pp_bn_workspace(C, P // groups, groups))
+    gd, bd = (_b(t) for t in (gamma, beta))
+    nbt = _zeros((), dtype=torch.int64)
+    # the launch under test: exactly what its own query returns (the eval form: all pixels as one group); the statistics call
+    # that only prepares the coefficient rows has a workspace of its own
+    nws = lib.pp_bn_lrelu_bwd_wgrad_c1_workspace(C, P, 1) if ev else lib.pp_bn_lrelu_bwd_wgrad_c1_workspace(C, P // groups, groups)
     ws = _ws(nws)
+    nws_stats = lib.pp_bn_workspace(C, P // groups, groups)
+    ws_stats = _ws(nws_stats)
 
     def rows(zt):           # the coefficient rows the kernels are handed, from the library itself
-        rmd, rvd = rm.to(_dev()), rv.to(_dev())
+        rmd, rvd = _b(rm), _b(rv)
         if training:
             lib.pp_bn_train_stats(zt.data_ptr(), ld_z, C, P // groups, groups, 1e-5, 0.1, gd.data_ptr(), bd.data_ptr(), rmd.data_ptr(),
-                                  rvd.data_ptr(), nbt.data_ptr(), mean, invstd, scale, shift, ws.data_ptr(), nws, run.st)
+                                  rvd.data_ptr(), nbt.data_ptr(), mean, invstd, scale, shift, ws_stats.data_ptr(), nws_stats, run.st)
         else:
             lib.pp_bn_eval_coeffs(C, groups, 1e-5, gd.data_ptr(), bd.data_ptr(), rmd.data_ptr(), rvd.data_ptr(), mean, invstd, scale,
                                   shift, run.st)
         torch.cuda.synchronize()
-    z32 = z.to(_dev())
+    z32 = _b(z)
     rows(z32)
     v = z32[..., :C].double().reshape(groups, -1, C)
     near = ((v * coef[2].double()[:, None] + coef[3].double()[:, None]).abs() < 1e-4).reshape(N, H, W, C)
@@ -607,9 +692,9 @@ def _wgrad_c1(key, run):
     res = []
     pdw, pp = ops.randn(C, 1, 3, 3) * ops.gs, ops.randn(3, C) * ops.gs
     for K, dt in ((run.K, run.dt),) if run.dt == torch.float32 else ((lib, torch.float32), (run.K, run.dt)):
-        xd, zd, dyd = (t.to(_dev()).to(dt).contiguous() for t in (x, zsrc, dy))
-        dw = (pdw if acc_dw else torch.full((C, 1, 3, 3), 5.0)).to(_dev())
-        dg, db, dbc = ((pp[i] if acc_p else torch.full((C,), 9.0)).to(_dev()) for i in range(3))
+        xd, zd, dyd = (_b(t.to(_dev()).to(dt)) for t in (x, zsrc, dy))
+        dw = _b(pdw if acc_dw else torch.full((C, 1, 3, 3), 5.0))
+        dg, db, dbc = (_b(pp[i] if acc_p else torch.full((C,), 9.0)) for i in range(3))
         if ev:
             K.pp_bn_lrelu_bwd_eval_wgrad_c1(dyd.data_ptr(), ld_dy, zd.data_ptr(), ld_z, scale, gd.data_ptr(), bd.data_ptr(), xd.data_ptr(),
                                             ld_x, H, W, dw.data_ptr(), acc_dw, dg.data_ptr(), db.data_ptr(), dbc.data_ptr(), acc_p, C,
@@ -685,6 +770,19 @@ def _act_ratio(h, f, storage):
     return float(((h64 - f64).abs() / bound).max())
 
 
+def _execute(adapter, key, run):
+    """Run one adapter with `run` as the home of its buffers, then add one result line per buffer, '<label> band': intact or not
+    (all bands of the launch compared on the device, one read)."""
+    _CUR[0] = run
+    try:
+        adapter(key, run)
+    finally:
+        _CUR[0] = None
+    torch.cuda.synchronize()
+    for label, ok in run.bands.verdicts():
+        run.res.append((label + ' band', None, ok, None, False))
+
+
 def replay(key, adapters=None, table=None):
     """[(label, error / tolerance)] of one recorded launch; raises KeyError naming an entry without an adapter.  adapters: another
     family's table of adapters (tests/test_gpu_stream_census.py); table: a stand-in for the fp32 entry-point table."""
@@ -697,8 +795,7 @@ def replay(key, adapters=None, table=None):
         lib = table
     out = []
     r32 = _Run(lib, torch.float32, True)
-    adapters[name]((storage, name, a), r32)
-    torch.cuda.synchronize()
+    _execute(adapters[name], (storage, name, a), r32)
     for label, got, ref, tol, _ in r32.res:
         tag = 'fp32 twin ' if storage != 'fp32' else ''
         if got is None:
@@ -707,8 +804,7 @@ def replay(key, adapters=None, table=None):
             out.append((tag + label, _rel(got, ref) / tol))
     if storage != 'fp32':
         r16 = _Run(lib_for(storage), MANT[storage][2], False)
-        adapters[name]((storage, name, a), r16)
-        torch.cuda.synchronize()
+        _execute(adapters[name], (storage, name, a), r16)
         twin = {lab: got for lab, got, _, _, _ in r32.res}
         twin_ref = {lab: ref for lab, _, ref, _, _ in r32.res if ref is not None}
         for label, got, ref, tol, act in r16.res:
@@ -1154,9 +1250,9 @@ def _set(i, value):
 def _i_true_is_cpad(fn, a):
     """pp_conv3x3_bwd_weight with I_true = Cpad: the gradient in the (O, Cpad, 3, 3) layout.  It goes to a buffer of that size;
     the caller's (O, I, 3, 3) buffer receives what it would have held (the leading O * I * 9 floats): nothing is written outside."""
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     O_, Cpad, I = a[2], a[5], a[6]
-    big = torch.zeros(O_ * Cpad * 9, device=_dev())
+    big = _zeros(O_ * Cpad * 9)
     dw, a[6], a[11] = a[11], Cpad, big.data_ptr()
     rc = fn(*a)
     n = O_ * I * 9
@@ -1168,7 +1264,7 @@ def _i_true_is_cpad(fn, a):
 def _other_x(fn, a):
     """the Winograd forward that fills the kept V, run on another tensor of the same extent"""
     B, H, W = a[8], a[9], a[10]
-    other = torch.randn(B * H * W * a[1], generator=torch.Generator().manual_seed(5)).to(_dev())
+    other = _b(torch.randn(B * H * W * a[1], generator=torch.Generator().manual_seed(5)))
     a[0] = other.data_ptr()
     rc = fn(*a)
     torch.cuda.synchronize()
@@ -1177,7 +1273,7 @@ def _other_x(fn, a):
 
 def _stale_amax(fn, a):
     """max |dz| of an earlier, 2^8 times smaller dz: the split-fp16 operands leave the fp16 range"""
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     lib.pp_scale(a[-2], 1, 2.0 ** -8, a[-1])
     rc = fn(*a)
     lib.pp_scale(a[-2], 1, 2.0 ** 8, a[-1])
@@ -1205,6 +1301,7 @@ def test_planted_mistake_fails_the_replay(plant):
     key = ('fp32',) + _EDGE_OF[tag]
     honest = dict(replay(key))
     assert all(r <= 1.0 for r in honest.values()), honest
+    assert sum(label.endswith(' band') for label in honest) >= 2, 'no sentinel-band verdicts in the replay (an input and an output at least)'
     planted = dict(replay(key, table=_Planted(lib, entry, wrong)))
     for label in must_fail:
         assert not planted[label] <= 1.0, (plant, label, planted)

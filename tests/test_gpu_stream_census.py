@@ -26,6 +26,8 @@ The recording also wraps engine.py's module-level entry-point table, so the laun
 pp_bn_eval_coeffs_batch (every row against float64 and bit for bit against pp_bn_eval_coeffs), the batched split-fp16 weight packs
 (bit for bit against the per-layer packs the convolution census feeds its kernels with), pp_scale_guard.  Their item tables are host
 arrays the launch shape cannot show, so the adapters build tables of the recorded length over layers of several widths.
+Operands, outputs and workspaces lie between the sentinel bands of the convolution census (tests/_guard.py, 0xFF); _bn_ws gives
+every BatchNorm launch exactly the bytes include/pacingpseudo_hip.h asks for that entry point.
 Together the two censuses own every recorded launch: a name without an adapter in either fails by name; nothing is excluded.
 What the operands give up: backward operands are moved off the LeakyReLU kink (|z * scale + shift| >= 1e-4) and the operands of the
 pooled forms lie on a 2^-10 grid, because there fp32 and float64 legitimately choose differently; the replay therefore cannot see
@@ -49,8 +51,8 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle import pacing_oracle as O  # noqa: E402
-from tests.test_gpu_conv_census import (MANT, TOL, TOL_SUMS, _dev, _is_conv_launch, _lazy64, _Ops, _p, _Run, _ws,  # noqa: E402
-                                        replay as _replay)
+from tests.test_gpu_conv_census import (MANT, TOL, TOL_SUMS, _b, _dev, _empty, _full, _is_conv_launch, _L, _lazy64, _Ops, _p,  # noqa: E402
+                                        _Run, _ws, _zeros, replay as _replay)
 
 TOL_BIL = 1e-5        # test_bilinear
 TOL_LOSS = 1e-5       # loss values, bank rows, up-sampled logits (tests/test_gpu_ops.py)
@@ -124,9 +126,23 @@ def _f32(run, t):
     return run.d(t, act=False)
 
 
-def _bn_ws(C, ppg, groups):
-    from pacingpseudo_amd._lib import lib
-    n = max(lib.pp_bn_workspace(C, ppg, groups), lib.pp_bn_workspace(C, ppg * groups, 1)) + 64 * groups * C + 4096
+def _bn_ws(name, C, ppg, groups):
+    """(workspace, bytes) of one BatchNorm launch: EXACTLY what include/pacingpseudo_hip.h asks for that entry point, from the
+    query the engine sizes its workspace with -- the statistics and sums passes pp_bn_workspace(C, P_per_group, groups); the
+    backward forms with batch statistics 3 * groups * C floats (the k rows of the apply pass) on top; the one-pass eval forms
+    pp_bn_workspace(C, P_total, 1); pp_bn_lrelu_bwd_apply 6 * groups * C floats + 16."""
+    lib = _L()
+    short = name[len('pp_bn_lrelu_bwd'):] if name.startswith('pp_bn_lrelu_bwd') else None
+    if short in ('', '_amax', '_pool'):
+        n = lib.pp_bn_workspace(C, ppg, groups) + 3 * groups * C * 4
+    elif short in ('_eval', '_eval_pool'):
+        n = lib.pp_bn_workspace(C, ppg * groups, 1)
+    elif short == '_apply':
+        n = 6 * groups * C * 4 + 16
+    elif short == '_sums' or name in ('pp_bn_train_stats', 'pp_bn_stats_sums'):
+        n = lib.pp_bn_workspace(C, ppg, groups)
+    else:
+        raise KeyError(name)
     return _ws(n), n
 
 
@@ -175,17 +191,17 @@ def _bn_stats(key, run):
     z = ops.norm_z(groups, ppg, 1, C)
     zd = run.d(ops.pad(z, ld))
     z64 = z.double().reshape(groups, ppg, C)
-    ws, nws = _bn_ws(C, ppg, groups)
+    ws, nws = _bn_ws(name, C, ppg, groups)
     if name == 'pp_bn_stats_sums':
-        sums = torch.full((groups, 2, C), 7.0, dtype=torch.float64, device=_dev())
+        sums = _full((groups, 2, C), 7.0, dtype=torch.float64)
         run.K.pp_bn_stats_sums(zd.data_ptr(), ld, C, ppg, groups, sums.data_ptr(), ws.data_ptr(), nws, run.st)
         run.check('sum', sums[:, 0], z64.sum(1), TOL_SUMS, act=False)
         run.check('sum of squares', sums[:, 1], z64.pow(2).sum(1), TOL_SUMS, act=False)
         return
     gamma, beta, rm, rv = ops.affine(C)
     gd, bd, rmd, rvd = (_f32(run, t.clone()) for t in (gamma, beta, rm, rv))
-    nbt = torch.full((), 3, dtype=torch.int64, device=_dev())
-    coef = torch.full((4, groups, C), 7.0, device=_dev())
+    nbt = _full((), 3, dtype=torch.int64)
+    coef = _full((4, groups, C), 7.0)
     run.K.pp_bn_train_stats(zd.data_ptr(), ld, C, ppg, groups, eps, mom, gd.data_ptr(), bd.data_ptr(), rmd.data_ptr(), rvd.data_ptr(),
                             nbt.data_ptr(), *(coef[i].data_ptr() for i in range(4)), ws.data_ptr(), nws, run.st)
     _check_stats(run, z64, gamma, beta, rm, rv, eps, mom, coef, rmd, rvd, nbt)
@@ -216,18 +232,18 @@ def _bn_finalize(key, run):
     lazy = name.endswith('_lazy')
     ops = _DOps(key)
     z64 = ops.norm_z(groups, n, 1, C).double().reshape(groups, n, C)
-    part = torch.zeros(groups, rows, 2, C, dtype=torch.float64, device=_dev())
+    part = _zeros(groups, rows, 2, C, dtype=torch.float64)
     for r, chunk in enumerate(torch.tensor_split(z64, rows, dim=1)):
         part[:, r, 0], part[:, r, 1] = chunk.sum(1), chunk.pow(2).sum(1)
     gamma, beta, rm, rv = ops.affine(C)
     gd, bd, rmd, rvd = (_f32(run, t.clone()) for t in (gamma, beta, rm, rv))
-    nbt = torch.full((), 3, dtype=torch.int64, device=_dev())
-    coef = torch.full((4, groups, C), 7.0, device=_dev())
+    nbt = _full((), 3, dtype=torch.int64)
+    coef = _full((4, groups, C), 7.0)
     args = (part.data_ptr(), rows, C, n, groups, eps, mom, gd.data_ptr(), bd.data_ptr(), rmd.data_ptr(), rvd.data_ptr(),
             nbt.data_ptr(), *(coef[i].data_ptr() for i in range(4)))
     if lazy:
         lld, slope = a[17], a[18]
-        lz = torch.full((groups, 3, lld), 7.0, device=_dev())
+        lz = _full((groups, 3, lld), 7.0)
         run.K.pp_bn_train_finalize_lazy(*args, lz.data_ptr(), lld, slope, run.st)
     else:
         run.K.pp_bn_train_finalize(*args, run.st)
@@ -246,7 +262,7 @@ def _bn_eval_coeffs(key, run):
     ops = _DOps(key)
     gamma, beta, rm, rv = ops.affine(C)
     gd, bd, rmd, rvd = (_f32(run, t) for t in (gamma, beta, rm, rv))
-    coef = torch.full((4, groups, C), 7.0, device=_dev())
+    coef = _full((4, groups, C), 7.0)
     run.K.pp_bn_eval_coeffs(C, groups, eps, gd.data_ptr(), bd.data_ptr(), rmd.data_ptr(), rvd.data_ptr(),
                             *(coef[i].data_ptr() for i in range(4)), run.st)
     ref = _coef64(torch.zeros(groups, 1, C, dtype=torch.float64, device=_dev()), gamma, beta, rm, rv, False, eps)
@@ -260,7 +276,8 @@ def _bn_eval_coeffs_batch(key, run):
     bit for bit against pp_bn_eval_coeffs of that layer."""
     _, _, a = key
     _, n, eps = a[:3]
-    from pacingpseudo_amd._lib import PpBnCoefItem, lib
+    from pacingpseudo_amd._lib import PpBnCoefItem
+    lib = _L()
     ops = _DOps(key)
     widths = (32, 64, 128, 256, 512, 1024, 12, 516)
     items, layers = [], []
@@ -279,7 +296,7 @@ def _bn_eval_coeffs_batch(key, run):
         ref = _coef64(torch.zeros(groups, 1, C, dtype=torch.float64, device=_dev()), *par, False, eps)
         for j, lab in enumerate(('save_mean', 'save_invstd', 'scale', 'shift')):
             run.check(f'layer {i} (C={C}, groups={groups}) {lab}', coef[j], ref[j], TOL_SUMS, act=False)
-        one = torch.full((4, groups, C), 7.0, device=_dev())
+        one = _full((4, groups, C), 7.0)
         lib.pp_bn_eval_coeffs(C, groups, eps, *(t.data_ptr() for t in dev), *(one[j].data_ptr() for j in range(4)), run.st)
         same = same and torch.equal(one, coef)
     _flag(run, 'rows bit-identical to pp_bn_eval_coeffs', same)
@@ -409,8 +426,8 @@ def _bn_bwd(key, run):
     gd, bd = _f32(run, gamma), _f32(run, beta)
     bufs, prior = _param_grads(run, ops, C, acc, (dgp, dbp, dcp))
     dz = _out(run, (N, H, W), ld_dz, C)
-    am = torch.full((1,), 1e30, device=_dev()) if amp else None
-    ws, nws = _bn_ws(C, ppg, groups)
+    am = _full((1,), 1e30) if amp else None
+    ws, nws = _bn_ws(name, C, ppg, groups)
     K, st = run.K, run.st
     tail = (dz.data_ptr(), ld_dz, _p(bufs[0]), _p(bufs[1]), _p(bufs[2]), acc, C)
     if short == '':
@@ -421,8 +438,7 @@ def _bn_bwd(key, run):
                                groups, slope, ws.data_ptr(), nws, _p(am), st)
     elif short == '_apply':
         # local = global sums (one rank), given in float64: (sum g, sum g * xhat) per group and channel
-        s64 = _bwd_sums64(z64.reshape(groups, ppg, C), dy.double().reshape(groups, ppg, C), coef.double(), slope)
-        run.keep.append(s64)
+        s64 = _b(_bwd_sums64(z64.reshape(groups, ppg, C), dy.double().reshape(groups, ppg, C), coef.double(), slope))
         K.pp_bn_lrelu_bwd_apply(dyd.data_ptr(), ld_dy, src.data_ptr(), ld_z, scale, shift, mean, invstd, gd.data_ptr(), training,
                                 s64.data_ptr(), s64.data_ptr(), n_glob, *tail, ppg, groups, slope, ws.data_ptr(), nws, _p(am), st)
     elif short == '_pool':
@@ -446,7 +462,7 @@ def _bwd_sums64(z64, dy64, coef64, slope):
 
 def _bn_bwd_sums(key, run):
     """pp_bn_lrelu_bwd_sums (the local half of the synchronised backward)"""
-    _, _, a = key
+    _, name, a = key
     _, ld_dy, _, ld_z, _, _, _, _, C, ppg, groups, slope = a[:12]
     ops = _DOps(key)
     z = ops.norm_z(groups, ppg, 1, C)
@@ -454,8 +470,8 @@ def _bn_bwd_sums(key, run):
     z, coef = _off_kink(ops, z, groups, lambda t: _coef64(t.double().reshape(groups, ppg, C), gamma, beta, rm, rv, True, EPS).float(), 2, 3)
     dy = ops.r(ops.randn(groups, ppg, 1, C, scale=ops.gs))
     zd, dyd, cd = run.d(ops.pad(z, ld_z)), run.d(ops.pad(dy, ld_dy)), _f32(run, coef)
-    sums = torch.full((groups, 2, C), 7.0, dtype=torch.float64, device=_dev())
-    ws, nws = _bn_ws(C, ppg, groups)
+    sums = _full((groups, 2, C), 7.0, dtype=torch.float64)
+    ws, nws = _bn_ws(name, C, ppg, groups)
     run.K.pp_bn_lrelu_bwd_sums(dyd.data_ptr(), ld_dy, zd.data_ptr(), ld_z, cd[2].data_ptr(), cd[3].data_ptr(), cd[0].data_ptr(),
                                cd[1].data_ptr(), C, ppg, groups, slope, sums.data_ptr(), ws.data_ptr(), nws, run.st)
     ref = _bwd_sums64(z.double().reshape(groups, ppg, C), dy.double().reshape(groups, ppg, C), coef.double(), slope)
@@ -481,12 +497,12 @@ def _gn_stats(key, run):
     """pp_gn_stats"""
     _, _, a = key
     _, ld, C, HW, N, G, eps = a[:7]
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     ops = _DOps(key)
     z = ops.norm_z(N, HW, 1, C)
     gamma, beta, _, _ = ops.affine(C)
     zd, gd, bd = run.d(ops.pad(z, ld)), _f32(run, gamma), _f32(run, beta)
-    rows = torch.full((5, N, C), 7.0, device=_dev())
+    rows = _full((5, N, C), 7.0)
     nws = lib.pp_gn_workspace(C, HW, N)
     ws = _ws(nws)
     run.K.pp_gn_stats(zd.data_ptr(), ld, C, HW, N, G, eps, gd.data_ptr(), bd.data_ptr(), *(rows[i].data_ptr() for i in range(5)),
@@ -506,7 +522,7 @@ def _gn_bwd(key, run):
     else:
         (_, ld_dy, _, ld_z, _, _, _, _, _, _, _, ld_dz, dgp, dbp, dcp, acc, C, HW, N, G, slope) = a[:21]
         H, W, amp = HW, 1, a[23]
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     ops = _DOps(key)
     z = ops.norm_z(N, H, W, C, grid=2.0 ** -10 if pool else None)
     gamma, beta, _, _ = ops.affine(C)
@@ -527,7 +543,7 @@ def _gn_bwd(key, run):
     refs = (gr.grad, br.grad, zr.grad.sum((0, 2, 3)))
     bufs, prior = _param_grads(run, ops, C, acc, (dgp, dbp, dcp))
     dz = _out(run, (N, H, W), ld_dz, C)
-    am = torch.full((1,), 1e30, device=_dev()) if amp else None
+    am = _full((1,), 1e30) if amp else None
     nws = lib.pp_gn_workspace(C, H * W, N)
     ws = _ws(nws)
     mean, invstd, xbar, scale, shift = (rd[i].data_ptr() for i in range(5))
@@ -694,7 +710,7 @@ def _pack_weights(key, run):
     layouts, so they are checked by what they are for -- the forward and the data-gradient kernels fed with them, on a small
     image of the geometry that selects the recorded Winograd tile."""
     _, name, a = key
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     ops = _DOps(key)
     _, O_, I = a[:3]
     wb_given = a[5] is not None
@@ -704,26 +720,26 @@ def _pack_weights(key, run):
         geo = next(g for g in ((1, 16, 16, 1), (1, 6, 10, 1), (1, 28, 28, 2)) if lib.pp_conv3x3_wino_tile(*g[1:]) == tile)
         B, H, W, dil = geo
         n = (tile + 2) ** 2
-        wf, wb = torch.zeros(n, O_, I, device=_dev()), (torch.zeros(n, I, O_, device=_dev()) if wb_given else None)
+        wf, wb = _zeros(n, O_, I), (_zeros(n, I, O_) if wb_given else None)
         run.K.pp_wino_pack_weights(w.data_ptr(), O_, I, tile, wf.data_ptr(), _p(wb), run.st)
         Ipad = I
     else:
         Ipad = a[3]
         B, H, W, dil = 1, 8, 8, 1
-        wf, wb = torch.zeros(O_, 9, Ipad, device=_dev()), (torch.zeros(Ipad, 9, O_, device=_dev()) if wb_given else None)
+        wf, wb = _zeros(O_, 9, Ipad), (_zeros(Ipad, 9, O_) if wb_given else None)
         run.K.pp_pack_conv3x3_weights(w.data_ptr(), O_, I, Ipad, wf.data_ptr(), _p(wb), run.st)
     x = ops.randn(B, H, W, Ipad)
     x[..., I:] = 0
-    dz = ops.randn(B, H, W, O_)
-    y, dx = torch.empty(B, H, W, O_, device=_dev()), torch.empty(B, H, W, Ipad, device=_dev())
+    x, dz = _b(x), _b(ops.randn(B, H, W, O_))
+    y, dx = _empty(B, H, W, O_), _empty(B, H, W, Ipad)
     if name == 'pp_wino_pack_weights':
-        nws = max(lib.pp_conv3x3_wino_workspace(I, O_, B, H, W, dil), lib.pp_conv3x3_wino_workspace(O_, I, B, H, W, dil))
-        ws = _ws(nws)
-        lib.pp_conv3x3_wino_fwd(x.data_ptr(), Ipad, I, wf.data_ptr(), None, y.data_ptr(), O_, O_, B, H, W, dil, 0, None, ws.data_ptr(), nws,
-                                run.st)
+        nws = lib.pp_conv3x3_wino_workspace(I, O_, B, H, W, dil)                 # each launch its own, exact workspace
+        lib.pp_conv3x3_wino_fwd(x.data_ptr(), Ipad, I, wf.data_ptr(), None, y.data_ptr(), O_, O_, B, H, W, dil, 0, None,
+                                _ws(nws).data_ptr(), nws, run.st)
         if wb_given:
-            lib.pp_conv3x3_wino_bwd_data(dz.data_ptr(), O_, O_, wb.data_ptr(), dx.data_ptr(), Ipad, I, B, H, W, dil, 0, ws.data_ptr(), nws,
-                                         run.st)
+            nws = lib.pp_conv3x3_wino_workspace(O_, I, B, H, W, dil)
+            lib.pp_conv3x3_wino_bwd_data(dz.data_ptr(), O_, O_, wb.data_ptr(), dx.data_ptr(), Ipad, I, B, H, W, dil, 0,
+                                         _ws(nws).data_ptr(), nws, run.st)
     else:
         lib.pp_conv3x3_fwd(x.data_ptr(), Ipad, Ipad, wf.data_ptr(), None, y.data_ptr(), O_, O_, B, H, W, dil, 0, run.st)
         if wb_given:
@@ -741,7 +757,8 @@ def _pack_batch(key, run):
     held to them bit for bit, layer by layer, over layer shapes of several sizes."""
     _, name, a = key
     n = a[1]
-    from pacingpseudo_amd._lib import PpPackItem, PpWinoPackItem, lib
+    from pacingpseudo_amd._lib import PpPackItem, PpWinoPackItem
+    lib = _L()
     ops = _DOps(key)
     wino = name.startswith('pp_wino')
     shapes = ((32, 32), (64, 32), (16, 64), (128, 16), (16, 128), (256, 64), (48, 80), (512, 256))
@@ -750,7 +767,7 @@ def _pack_batch(key, run):
         O_, I = shapes[i % len(shapes)]
         w = _f32(run, ops.randn(O_, I, 3, 3, scale=1 / math.sqrt(9 * I)))
         planes = 36 if wino else 9
-        bufs = [torch.zeros(d, device=_dev()) for d in (((planes, O_, I), (planes, I, O_)) if wino else ((O_, planes, I), (I, planes, O_)))
+        bufs = [_zeros(d) for d in (((planes, O_, I), (planes, I, O_)) if wino else ((O_, planes, I), (I, planes, O_)))
                 for _ in range(2)]                      # wf, wf', wb, wb'
         items.append(PpWinoPackItem(w.data_ptr(), O_, I, bufs[0].data_ptr(), bufs[2].data_ptr()) if wino else
                      PpPackItem(w.data_ptr(), O_, I, I, bufs[0].data_ptr(), bufs[2].data_ptr()))
@@ -775,15 +792,15 @@ def _scale(key, run):
     _, n, value = a[:3]
     ops = _DOps(key)
     x = ops.randn(n)
-    p = x.clone()
+    p = _b(x)
     if name == 'pp_scale':
         run.K.pp_scale(p.data_ptr(), n, value, run.st)
     else:
-        bad = torch.zeros(2, dtype=torch.int32, device=_dev())
+        bad = _zeros(2, dtype=torch.int32)
         run.K.pp_scale_guard(p.data_ptr(), n, value, bad.data_ptr(), run.st)
-        q = x.clone()
+        q = _b(x)
         q[n // 2] = float('inf')
-        bad2 = torch.zeros(2, dtype=torch.int32, device=_dev())
+        bad2 = _zeros(2, dtype=torch.int32)
         run.K.pp_scale_guard(q.data_ptr(), n, value, bad2.data_ptr(), run.st)
         _flag(run, 'guard word: 0 for finite values, 1 for an infinite one', bad.tolist() == [0, 0] and bad2.tolist() == [1, 0])
     _exact(run, 'p', p, x.double() * torch.tensor(value).float().double())
@@ -794,7 +811,7 @@ def _loss_operands(ops, N, K, HW):
     zw, zs = ops.randn(N, K, HW, 1, scale=2.0), ops.randn(N, K, HW, 1, scale=2.0)
     t = torch.randint(0, K + 1, (N, HW, 1), generator=ops.g, device=_dev())
     mask = (ops.rand(N, 1, HW, 1) > 0.3).float()
-    return zw, zs, t, mask
+    return _b(zw), _b(zs), _b(t), _b(mask)
 
 
 def _argmax(key, run):
@@ -806,7 +823,8 @@ def _argmax(key, run):
     x[0, 0, 0] = x[0, C - 1, 0] = 9.0
     t = torch.randint(0, C, (N, HW), generator=ops.g, device=_dev())
     x[1 % N, :, 1:] = F.one_hot(t[1 % N, 1:], C).t().float()              # a one-hot plane, as the scribbles are
-    out = torch.full((N, HW), -1, dtype=torch.int64, device=_dev())
+    x = _b(x)
+    out = _full((N, HW), -1, dtype=torch.int64)
     run.K.pp_argmax_channels(x.data_ptr(), N, C, HW, out.data_ptr(), run.st)
     _flag(run, 'argmax bit-identical', torch.equal(out, x.argmax(1)))
 
@@ -839,14 +857,14 @@ def _scalar(run, label, got, ref, tol=TOL_LOSS, floor=1.0):
 def _seg_losses(key, run):
     """pp_seg_losses_fwd (+ pp_losses_finalize for the values) / pp_seg_losses_bwd"""
     _, name, a = key
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     bwd = name.endswith('_bwd')
     _, lsp, _, mp, N, K, HW, ignore, do_ent, variant = a[:10]
     ops = _DOps(key)
     zw, zs, t, mask = _loss_operands(ops, N, K, HW)
     variant_ref = variant if lsp else 0
     mask = mask if mp else None
-    sums = torch.zeros(6, dtype=torch.float64, device=_dev())
+    sums = _zeros(6, dtype=torch.float64)
     nws = lib.pp_seg_losses_workspace(N, HW)
     ws = _ws(nws)
     fwd_table = lib if bwd else run.K
@@ -855,7 +873,7 @@ def _seg_losses(key, run):
     detach = a[10] if bwd else 0
     zwr, zsr, pce, ent, cr = _seg64(zw, zs, t, mask, K, ignore, do_ent, variant_ref, detach)
     if not bwd:
-        lp, le, lc = (torch.zeros((), device=_dev()) for _ in range(3))
+        lp, le, lc = (_zeros(()) for _ in range(3))
         lib.pp_losses_finalize(sums.data_ptr(), 1 if mp else 0, lp.data_ptr(), le.data_ptr() if do_ent else None,
                                lc.data_ptr() if variant_ref else None, run.st)
         _scalar(run, 'loss_pce', lp, pce)
@@ -866,9 +884,9 @@ def _seg_losses(key, run):
         return
     _, gpp, gep, gcp, gscale, _, dsp = a[11:18]
     gw = dict(pce=0.7, ent=0.3, cr=1.9)
-    gs = {k: torch.tensor(v, device=_dev()) for k, v in gw.items()}
-    dzw = torch.full_like(zw, 7.0)
-    dzs = torch.full_like(zs, 7.0) if dsp else None
+    gs = {k: _b(torch.tensor(v)) for k, v in gw.items()}
+    dzw = _full(zw.shape, 7.0)
+    dzs = _full(zs.shape, 7.0) if dsp else None
     run.K.pp_seg_losses_bwd(zw.data_ptr(), zs.data_ptr() if lsp else None, t.data_ptr(), _p(mask), N, K, HW, ignore, do_ent, variant, detach,
                             sums.data_ptr(), gs['pce'].data_ptr() if gpp else None, gs['ent'].data_ptr() if gep else None,
                             gs['cr'].data_ptr() if gcp else None, gscale, dzw.data_ptr(), _p(dzs), run.st)
@@ -894,8 +912,8 @@ def _losses_finalize(key, run):
     _, _, a = key
     _, has_mask, lpp, lep, lcp = a[:5]
     ops = _DOps(key)
-    sums = (ops.rand(6).double() * 100 + 1).contiguous()
-    outs = [torch.full((), 7.0, device=_dev()) if p else None for p in (lpp, lep, lcp)]
+    sums = _b(ops.rand(6).double() * 100 + 1)
+    outs = [_full((), 7.0) if p else None for p in (lpp, lep, lcp)]
     run.K.pp_losses_finalize(sums.data_ptr(), has_mask, *(_p(o) for o in outs), run.st)
     for i, (lab, o) in enumerate(zip(('loss_pce', 'loss_ent', 'loss_cr'), outs)):
         if o is not None:
@@ -905,7 +923,7 @@ def _losses_finalize(key, run):
 def _aux_pce(key, run):
     """pp_aux_pce_fwd / pp_aux_pce_bwd (tests/test_gpu_ops.py::test_aux_pce)"""
     _, name, a = key
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     bwd = name.endswith('_bwd')
     if bwd:
         _, _, ignore, _, gscale, _, _, N, K, h, w, H, W = a[:13]
@@ -916,23 +934,24 @@ def _aux_pce(key, run):
     lo = ops.randn(N, K, h, w)
     t = torch.randint(0, K, (N, H, W), generator=ops.g, device=_dev())
     t[ops.rand(N, H, W) > 0.1] = ignore
+    lo, t = _b(lo), _b(t)
     lor = lo.double().requires_grad_(True)
     up = F.interpolate(lor, size=(H, W), mode='bilinear', align_corners=True)
     loss = O.partial_cross_entropy_loss(up, t, ignore)
-    upd = torch.full((N, K, H, W), 7.0, device=_dev())
-    sums = torch.zeros(2, dtype=torch.float64, device=_dev())
-    nws = 1 << 20
+    upd = _full((N, K, H, W), 7.0)
+    sums = _zeros(2, dtype=torch.float64)
+    nws = 16 * min(1024, -(-N * H * W // 256))          # the header: two doubles per block of the grid, nothing more
     ws = _ws(nws)
     (lib if bwd else run.K).pp_aux_pce_fwd(lo.data_ptr(), N, K, h, w, H, W, t.data_ptr(), ignore, upd.data_ptr(), sums.data_ptr(),
                                            ws.data_ptr(), nws, run.st)
     if not bwd:
-        lv = torch.zeros((), device=_dev())
+        lv = _zeros(())
         lib.pp_losses_finalize(sums.data_ptr(), 0, lv.data_ptr(), None, None, run.st)
         run.check('logits_up', upd, up.detach(), TOL_LOSS, act=False)
         _scalar(run, 'loss_aux', lv, loss, floor=0.0)
         return
-    g = torch.tensor(0.01, device=_dev())
-    dlo = torch.full((N, K, h, w), 7.0, device=_dev())
+    g = _b(torch.tensor(0.01))
+    dlo = _full((N, K, h, w), 7.0)
     run.K.pp_aux_pce_bwd(upd.data_ptr(), t.data_ptr(), ignore, g.data_ptr(), gscale, sums.data_ptr(), dlo.data_ptr(), N, K, h, w, H, W,
                          run.st)
     (0.01 * gscale * loss).backward()
@@ -943,13 +962,13 @@ def _memory_update(key, run):
     """pp_memory_update (tests/test_gpu_ops.py::test_memory_update_and_ce; oracle/pacing_oracle.py::memory_update in float64)"""
     _, _, a = key
     _, ld, hid, h, w, _, K, H, W, _, mom, cosine = a[:12]
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     ops = _DOps(key)
     feat = ops.r(ops.randn(1, h, w, hid))
     t = torch.randint(0, K, (1, H, W), generator=ops.g, device=_dev())
     t[ops.rand(1, H, W) > 0.05] = K
     t[t == K - 1] = K                                       # the last class is absent from sample 0
-    scb = F.one_hot(t, K + 1).permute(0, 3, 1, 2).float().contiguous()
+    scb = _b(F.one_hot(t, K + 1).permute(0, 3, 1, 2).float())
     bank = torch.zeros(K, hid, 1, 1, device=_dev())
     bank[1 % K, :, 0, 0] = ops.randn(hid)                   # visited before; the others are first visits
     bank[K - 1, :, 0, 0] = ops.randn(hid)
@@ -971,18 +990,18 @@ def _memory_ce(key, run):
     _, name, a = key
     _, _, K, hid = a[:4]
     ops = _DOps(key)
-    bank, wfc = ops.randn(K, hid), ops.randn(K, hid)
+    bank, wfc = _b(ops.randn(K, hid)), _b(ops.randn(K, hid))
     wr = wfc.double().requires_grad_(True)
     loss = O.cross_entropy_loss(bank.double() @ wr.t(), torch.arange(K, device=_dev()))
     if name.endswith('_fwd'):
-        lv = torch.full((), 7.0, device=_dev())
+        lv = _full((), 7.0)
         run.K.pp_memory_ce_fwd(bank.data_ptr(), wfc.data_ptr(), K, hid, lv.data_ptr(), run.st)
         _scalar(run, 'loss_memory', lv, loss, floor=0.0)
         return
     _, gscale, _, acc = a[4:8]
-    g = torch.tensor(1.5, device=_dev())
+    g = _b(torch.tensor(1.5))
     prior = ops.randn(K, hid)
-    dw = prior.clone() if acc else torch.full((K, hid), 7.0, device=_dev())
+    dw = _b(prior) if acc else _full((K, hid), 7.0)
     run.K.pp_memory_ce_bwd(bank.data_ptr(), wfc.data_ptr(), K, hid, g.data_ptr(), gscale, dw.data_ptr(), acc, run.st)
     (1.5 * gscale * loss).backward()
     run.check('dwfc', dw, wr.grad + (prior.double() if acc else 0), act=False)
@@ -991,25 +1010,25 @@ def _memory_ce(key, run):
 def _crf(key, run):
     """pp_crf_loss_fwd / pp_crf_loss_bwd against tests/_crf_reference.py (tolerances of tests/test_gpu_crf.py)"""
     _, name, a = key
-    from pacingpseudo_amd._lib import lib
+    lib = _L()
     from tests._crf_reference import crf_loss_and_grad, smooth_image
     ops = _DOps(key)
     if name.endswith('_bwd'):
         _, _, has_mask, _, gscale, _, n = a[:7]
-        unit, prior = ops.randn(n), ops.randn(n)
-        sums = torch.tensor([3.0, 1000.0 if has_mask else float(n)], dtype=torch.float64, device=_dev())
-        g = torch.tensor(0.3, device=_dev())
-        dl = prior.clone()
+        unit, prior = _b(ops.randn(n)), ops.randn(n)
+        sums = _b(torch.tensor([3.0, 1000.0 if has_mask else float(n)], dtype=torch.float64))
+        g = _b(torch.tensor(0.3))
+        dl = _b(prior)
         run.K.pp_crf_loss_bwd(unit.data_ptr(), sums.data_ptr(), has_mask, g.data_ptr(), gscale, dl.data_ptr(), n, run.st)
         run.check('dlogits', dl, prior.double() + gscale * 0.3 * (-2.0 / float(sums[1])) * unit.double(), act=False)
         return
     _, _, mp, N, K, C, H, W, radius, dilation, sxy, srgb, up = a[:13]
-    z, mask = ops.randn(N, K, H, W, scale=2.0), ((ops.rand(N, 1, H, W) > 0.3).float() if mp else None)
-    img = smooth_image(N, C, H, W, 5).to(_dev())
+    z, mask = _b(ops.randn(N, K, H, W, scale=2.0)), (_b((ops.rand(N, 1, H, W) > 0.3).float()) if mp else None)
+    img = _b(smooth_image(N, C, H, W, 5))
     ref_loss, ref_grad = crf_loss_and_grad(z.cpu(), img.cpu(), mask.cpu() if mp else None, radius=radius, dilation=dilation,
                                            sigma_xy=sxy, sigma_rgb=srgb)
-    unit = torch.full((N, K, H, W), 7.0, device=_dev()) if up else None
-    sums = torch.zeros(2, dtype=torch.float64, device=_dev())
+    unit = _full((N, K, H, W), 7.0) if up else None
+    sums = _zeros(2, dtype=torch.float64)
     nws = lib.pp_crf_loss_workspace(N, H, W)
     ws = _ws(nws)
     run.K.pp_crf_loss_fwd(z.data_ptr(), img.data_ptr(), _p(mask), N, K, C, H, W, radius, dilation, sxy, srgb, _p(unit), sums.data_ptr(),
@@ -1216,7 +1235,7 @@ def _edge_cases():
 EDGES = _edge_cases()
 
 
-@pytest.mark.parametrize('storage', ['fp32', 'fp16'])
+@pytest.mark.parametrize('storage', ['fp32', 'fp16', 'bf16'])
 @pytest.mark.parametrize('tag,launch', EDGES, ids=[t for t, _ in EDGES])
 def test_edge_launch_matches_float64(tag, launch, storage):
     """Hand-made launch shapes at the sizes where the kernels change path, through the adapters of the census."""
@@ -1224,6 +1243,30 @@ def test_edge_launch_matches_float64(tag, launch, storage):
     bad = [(lab, r) for lab, r in res if not r <= 1.0]
     print(f'{tag} [{storage}]: worst error / tolerance {max(r for _, r in res):.3g}')
     assert not bad, f'{tag} [{storage}] args={launch[1]}: ' + ', '.join(f'{lab} {r:.3g} x tol' for lab, r in bad)
+
+
+def replayed_entry_points():
+    """Every entry point, suffix included, that the recordings and the two edge tables replay in its own storage type."""
+    from tests._launch_census import record, record_batches
+    from tests.test_gpu_conv_census import EDGE_PARAMS
+    suffix = {'fp32': '', 'fp16': '_h16', 'bf16': '_bf16'}
+    seen = {n + suffix[s] for rec in (record(), record_batches()) for (s, n, _) in rec}
+    seen |= {launch[0] + suffix[s] for _, launch, s in EDGE_PARAMS}
+    seen |= {launch[0] + suffix[s] for _, launch in EDGES for s in ('fp32', 'fp16', 'bf16')}
+    return seen
+
+
+def test_twins_the_ownership_gate_counts_are_replayed():
+    """tests/test_bounds_ownership.py counts a census adapter as the owner of its entry point's _h16 / _bf16 twins.  Here that is
+    measured: every such twin is replayed in its storage type by a recording or an edge row, or -- the forms no 16-bit plan
+    takes -- called under its own name by a case of the bounds table (tests/test_gpu_bounds.py)."""
+    from pacingpseudo_amd._lib import _PROTOS
+    from tests.test_gpu_bounds import owned_by_family
+    from tests.test_gpu_conv_census import ADAPTERS as CONV
+    seen = replayed_entry_points() | {e for entries in owned_by_family().values() for e in entries}
+    twins = {b + x for b in set(CONV) | set(ADAPTERS) for x in ('_h16', '_bf16') if b + x in _PROTOS}
+    assert not sorted(twins - seen), sorted(twins - seen)
+    assert not [b for b in set(CONV) | set(ADAPTERS) if b not in seen]
 
 
 # ------------------------------------------------------------------------------------------------------ the gate bites
@@ -1270,6 +1313,7 @@ def test_planted_mistake_fails_the_replay(plant):
     key = ('fp32',) + launch
     honest = dict(replay(key))
     assert all(r <= 1.0 for r in honest.values()), honest
+    assert sum(label.endswith(' band') for label in honest) >= 2, 'no sentinel-band verdicts in the replay (an input and an output at least)'
     planted = dict(replay(key, table=_Planted(lib, launch[0], mutate)))
     for label in must_fail:
         assert planted[label] > 1.0, (plant, label, planted)

@@ -174,6 +174,38 @@ def test_large_noise_pair_and_determinism():
         assert np.array_equal(outs[0][i, [0, 3, 4, 5, 6, 7]], want_row[[0, 3, 4, 5, 6, 7]]), i
 
 
+def test_distance_sets_come_in_row_major_order():
+    """pp_hd95_surface_distances lists each surface in row-major pixel order (an ordered compaction, no append through a counter):
+    dist[item][d][:counts] equals, ELEMENT BY ELEMENT, the reference's sets, which scipy's boolean indexing yields in row-major
+    order.  pp_surface_reduce adds the distances in storage order; its promise of the same bits in every run rests on this.
+    37 x 53 = 1961 pixels: eight trips of the 256-thread block, every wave contributes."""
+    from pacingpseudo_amd._lib import lib, stream_ptr
+    N, K, H, W, spacing = 4, 3, 37, 53, (1.5, 0.75)
+    pred, label = R.seeded_maps((H, W), K)
+    p, t = _gpu(pred), _gpu(label)
+    dist = torch.zeros((N * K, 2, H * W), device='cuda', dtype=torch.float32)
+    counts = torch.empty((N * K, 4), device='cuda', dtype=torch.int32)
+    nws = lib.pp_hd95_workspace(N, K, H, W)
+    ws = torch.empty(nws, device='cuda', dtype=torch.uint8)
+    lib.pp_hd95_surface_distances(p.data_ptr(), t.data_ptr(), N, K, H, W, *spacing, dist.data_ptr(), counts.data_ptr(), ws.data_ptr(), nws,
+                                  stream_ptr())
+    d, c = dist.cpu().numpy(), counts.cpu().numpy()
+    compared = telling = 0
+    for n in range(N):
+        for k in range(K):
+            a, b = np.asarray(pred[n]) == k, np.asarray(label[n]) == k
+            if not (a.any() and b.any()):
+                continue
+            d1, d2 = R.directed_sets(a, b, spacing)
+            i = n * K + k
+            assert c[i, 0] == len(d1) and c[i, 1] == len(d2), (n, k)
+            np.testing.assert_allclose(d[i, 0, :len(d1)], d1, rtol=1e-6, atol=0, err_msg=f'image {n} class {k}: pred -> label')
+            np.testing.assert_allclose(d[i, 1, :len(d2)], d2, rtol=1e-6, atol=0, err_msg=f'image {n} class {k}: label -> pred')
+            compared += len(d1) + len(d2)
+            telling += len(np.unique(d1)) > 3 and len(np.unique(d2)) > 3          # (a set of equal distances does not tell the order)
+    assert compared > 500 and telling >= 4
+
+
 def test_compute_hd_equals_the_oracle():
     from pacingpseudo_amd.utils import compute_hd
     pred, label = R.seeded_maps((37, 53))

@@ -639,6 +639,7 @@ class StepEngine:
         self._wg_stream = None           # second HIP stream of the weight gradients (created on first use)
         self._coefs_ready = frozenset()  # layers whose eval-mode coefficient rows the running forward has written in one batch
         self._bwd_plan = None            # plan of the backward pass in flight
+        self._frozen = 0                 # frozen encoder stages of the forward in flight (backbone.frozen_stages, checked per forward)
         # 16-bit storage of activations / activation gradients for TRAINING plans (`--storage fp16`, BASELINE config 5; PP_ACT_H16=1
         # forces it for A/B runs).  Forward-only plans (validation, inference at native slice sizes) stay fp32.
         # --do_loss_crf: the gated-CRF regulariser on the weak logits; its parameters are constants of the run (checked here, before
@@ -766,9 +767,26 @@ class StepEngine:
             plan.conv[L.name].pack(st)
         plan.packed_key = key
 
-    def _convbn_fwd(self, plan, L: _Layer, x: View, y: View, groups, training, st, pool_out: Optional[View] = None):
+    def _frozen_stages(self) -> int:
+        """N of ``freeze_encoder(N)``: encoder stages 1 .. N run eval-mode BatchNorm in every forward and have no backward.  The
+        only supported set of non-trainable backbone parameters is exactly that prefix; anything else is refused here, before
+        any launch, with the name of the first parameter that is on the wrong side."""
+        n = int(getattr(self.backbone, 'frozen_stages', 0) or 0)
+        prefixes = tuple(f'enc_block{k}.' for k in range(1, n + 1))
+        for name, p in self.backbone.named_parameters():
+            want = not name.startswith(prefixes) if prefixes else True
+            if p.requires_grad != want:
+                raise NotImplementedError(
+                    f'backbone.{name}: requires_grad={p.requires_grad} with frozen_stages={n}; the engine trains everything or '
+                    'everything but an encoder prefix -- use freeze_encoder(n) (--freeze_encoder N), which freezes '
+                    'enc_block1 .. enc_block<n> as a whole')
+        return n
+
+    def _convbn_fwd(self, plan, L: _Layer, x: View, y: View, groups, training, st, pool_out: Optional[View] = None,
+                    record: bool = True):
         """conv3x3 + BatchNorm + LeakyReLU of one layer.  pool_out: where the 2x2 max-pooled copy of the output goes when the
-        caller wants it from the same pass; returns True when it was written (train-mode apply pass), else the caller pools."""
+        caller wants it from the same pass; returns True when it was written (train-mode apply pass), else the caller pools.
+        record=False: a layer of a frozen stage -- nothing is kept for a backward pass."""
         coef = plan.coef[L.name]
         op = plan.conv[L.name]
         C = L.cout
@@ -783,7 +801,7 @@ class StepEngine:
         lazy = bool(training and plan.lazy_out[L.name])
         zptr, zld = (y.ptr, y.ld) if lazy else ((plan.zbuf[L.name].data_ptr(), C) if L.name in plan.zbuf else (None, C))
         L.x, L.y, L.groups = x, y, groups
-        if self._rec is not None:
+        if self._rec is not None and record:
             # what this step's backward reads (kept with the step, not the layer): input view (+ whether it was lazy),
             # output view, groups, whether the output is lazy (then the output buffer holds z)
             self._rec[L.name] = (x, y, groups, lazy, x.lazy)
@@ -1023,16 +1041,22 @@ class StepEngine:
         G = plan.G
         encs = net.enc_blocks()
         pooled_done = False
+        frozen = self._frozen
         for k, e in enumerate(encs, start=1):
             if e.pooling is not None and not pooled_done:
                 src = plan.enc_out[k - 1]
                 assert not src.lazy
                 plan.K.pp_maxpool2_fwd(src.ptr, src.ld, plan.pooled[k].ptr, plan.pooled[k].ld, src.C, src.N, src.H, src.W, st)
             L1, L2 = self.enc_layers[k]
-            self._convbn_fwd(plan, L1, plan.enc_in[k], plan.mid[L1.name], G, training, st)
+            # a frozen stage (freeze_encoder): eval-mode BatchNorm from the running statistics whatever the backbone's mode -- no
+            # statistics update, no SyncBN all-reduce, no lazy output, no backward record (in a train-mode forward its coefficient
+            # rows come from the per-layer pp_bn_eval_coeffs: _eval_coeffs_batch has not run)
+            live = k > frozen
+            tr = training and live
+            self._convbn_fwd(plan, L1, plan.enc_in[k], plan.mid[L1.name], G, tr, st, record=live)
             # the next stage's max-pooling from the same pass that normalises this stage's output (train mode)
             nxt = plan.pooled.get(k + 1) if (k < 6 and encs[k].pooling is not None) else None
-            pooled_done = bool(self._convbn_fwd(plan, L2, plan.mid[L1.name], plan.enc_out[k], G, training, st, pool_out=nxt))
+            pooled_done = bool(self._convbn_fwd(plan, L2, plan.mid[L1.name], plan.enc_out[k], G, tr, st, pool_out=nxt, record=live))
         if after_encoder is not None:
             after_encoder()
         for k in (5, 4, 3, 2, 1):
@@ -1060,7 +1084,9 @@ class StepEngine:
             plan.K.pp_conv1x1_nhwc_to_nchw_fwd(d1.ptr, d1.ld, d1.C, fc.weight.data_ptr(), fc.bias.data_ptr(),
                                             logits.data_ptr(), net.num_classes, d1.N, d1.H * d1.W, st)
 
-    def _unet_backward_decoder(self, plan: _Plan, training, grads, st):
+    def _unet_backward_decoder(self, plan: _Plan, training, grads, st, need_g6: bool = True):
+        """need_g6=False (the whole encoder is frozen): the up-sampling backward of decoder stage 5, whose only product is the
+        gradient wrt encoder stage 6, does not run (a ConvTranspose2d's own weight gradient still does)."""
         net = self.backbone
         decs = net.dec_blocks()
         d1 = plan.dec_out[1]
@@ -1091,9 +1117,10 @@ class StepEngine:
                     src = plan.low_src[k]
                     plan.K.pp_convtranspose_bwd_weight(glow.ptr, glow.ld, d.up_ch, src.ptr, src.ld, src.C, d.scale, src.N, src.H, src.W,
                                                     grads[d.up_samp.weight].data_ptr(), 0, plan.ws.data_ptr(), plan.ws_bytes, st)
-                    plan.K.pp_convtranspose_bwd_data(glow.ptr, glow.ld, d.up_ch, d.up_samp.weight.data_ptr(), dst.ptr, dst.ld, dst.C,
-                                                  d.scale, dst.N, dst.H, dst.W, 0, st)
-                else:
+                    if k < 5 or need_g6:
+                        plan.K.pp_convtranspose_bwd_data(glow.ptr, glow.ld, d.up_ch, d.up_samp.weight.data_ptr(), dst.ptr, dst.ld, dst.C,
+                                                      d.scale, dst.N, dst.H, dst.W, 0, st)
+                elif k < 5 or need_g6:
                     plan.K.pp_bilinear_bwd(glow.ptr, glow.ld, dst.ptr, dst.ld, dst.C, dst.N, dst.H, dst.W, glow.H, glow.W, 0, st)
                 glow = dst
             g_out = glow          # for k == 5 this is the gradient wrt encoder stage 6
@@ -1109,13 +1136,15 @@ class StepEngine:
         d = self.backbone.dec_blocks()[k]
         return _sub(plan.dcat[k], d.up_ch, d.skip_ch)
 
-    def _unet_backward_encoder(self, plan: _Plan, training, grads, g6: View, st):
+    def _unet_backward_encoder(self, plan: _Plan, training, grads, g6: View, st, frozen: int = 0):
+        """frozen = N (freeze_encoder): the walk 6 -> 1 stops behind stage N + 1, whose first layer gets no data gradient; for the
+        stages k <= N nothing is launched -- no norm backward, no weight or data gradient, no pooling gradient into them."""
         encs = self.backbone.enc_blocks()
         # the pooled-tensor gradient of stage k + 1, when it is folded into this stage's BatchNorm backward instead of being
         # added to the skip-gradient buffer by pp_maxpool2_bwd (not under synchronised BatchNorm: its split calls have no such form)
         fuse_pool = FUSE_POOL_BWD and not (training and self.comm is not None and self.sync_bn)
         pool_grad = None
-        for k in (6, 5, 4, 3, 2, 1):
+        for k in range(6, frozen, -1):
             e = encs[k - 1]
             L1, L2 = self.enc_layers[k]
             g_out = self._enc_grad_view(plan, k, g6)
@@ -1123,9 +1152,9 @@ class StepEngine:
             dmid = View(plan.s2.data_ptr(), m.C, m.C, m.N, m.H, m.W, plan.s2[:m.N * m.H * m.W * m.C].view(m.N, m.H, m.W, m.C), es=plan.es)
             self._convbn_bwd(plan, L2, g_out, dmid, False, training, grads, st, pool=pool_grad)
             pool_grad = None
-            if k == 1:
+            if k == frozen + 1:              # (k == 1 without frozen stages: the first layer of the network)
                 self._convbn_bwd(plan, L1, dmid, None, False, training, grads, st)
-                self._bucket('enc_rest')
+                self._bucket('enc_rest' if k <= 4 else f'enc{k}')
                 break
             gprev = self._enc_grad_view(plan, k - 1, g6)
             if e.pooling is not None:
@@ -1169,9 +1198,10 @@ class StepEngine:
     def infer_end_points(self, x: torch.Tensor, training: bool):
         x = self._check_input(x, 'x')
         B, Cin, H, W = x.shape
+        self._frozen = self._frozen_stages()
         plan = self.plan_for(B, H, W, 1, trainable=False)
         self.last_plan = plan
-        plan.begin_forward((bool(training), False))
+        plan.begin_forward((bool(training), False, self._frozen))
         self._rec = None
         st = stream_ptr()
         self._pack_weights(plan, st, need_grad=False)
@@ -1191,10 +1221,11 @@ class StepEngine:
         unet_backward."""
         x = self._check_input(x, 'x')
         B, Cin, H, W = x.shape
+        self._frozen = self._frozen_stages()
         plan = self.plan_for(B, H, W, 1)
         self.last_plan = plan
         training = self.backbone.training
-        plan.begin_forward((bool(training), False))
+        plan.begin_forward((bool(training), False, self._frozen))
         self._rec = {}
         st = stream_ptr()
         self._pack_weights(plan, st)
@@ -1207,7 +1238,7 @@ class StepEngine:
                 ep[f'encoder/stage{k}'] = self._as_nchw(plan.enc_out[k])
             for k in (5, 4, 3, 2, 1):
                 ep[f'decoder/stage{k}'] = self._as_nchw(plan.dec_out[k])
-        self.last = dict(unet=True, rec=self._rec, gen=plan.generation, plan=plan, bn_training=training)
+        self.last = dict(unet=True, rec=self._rec, gen=plan.generation, plan=plan, bn_training=training, frozen=self._frozen)
         return ep
 
     def unet_backward(self, dlogits: torch.Tensor, grads: Dict[torch.nn.Parameter, torch.Tensor],
@@ -1235,8 +1266,8 @@ class StepEngine:
         else:
             plan.dlogits.copy_(dlogits.to(torch.float32))
         with self._wgrad_budget(plan):
-            g6 = self._unet_backward_decoder(plan, S['bn_training'], grads, st)
-            self._unet_backward_encoder(plan, S['bn_training'], grads, g6, st)
+            g6 = self._unet_backward_decoder(plan, S['bn_training'], grads, st, need_g6=S['frozen'] < 6)
+            self._unet_backward_encoder(plan, S['bn_training'], grads, g6, st, S['frozen'])
         self._join_side_stream(plan)
 
     def _wgrad_budget(self, plan):
@@ -1301,6 +1332,7 @@ class StepEngine:
                 raise ValueError('The loss is not implemented.')
             variant = CR_VARIANTS[args.loss_cr_variants]
         G = 2 if do_cr else 1
+        self._frozen = self._frozen_stages()
         plan = self.plan_for(B, H, W, G, trainable=need_grad)
         self.last_plan = plan
         if do_aux and plan.aux is None:
@@ -1309,7 +1341,7 @@ class StepEngine:
         bn_training = self.backbone.training
         dev = image.device
 
-        plan.begin_forward((bool(bn_training), bool(self.aux.training) if self.aux is not None else False))
+        plan.begin_forward((bool(bn_training), bool(self.aux.training) if self.aux is not None else False, self._frozen))
         self._rec = {} if need_grad else None
         with prof_range('pack weights + images'):
             self._pack_weights(plan, st, need_grad=need_grad)
@@ -1478,7 +1510,7 @@ class StepEngine:
             self.last = dict(rec=self._rec, gen=plan.generation, plan=plan, B=B, H=H, W=W, K=K, logits=logits, mask=valid_mask if mask_ptr else None,
                              do_ent=do_ent, do_cr=do_cr, do_aux=do_aux, do_mem=do_mem, variant=variant,
                              bn_training=bn_training, aux_training=self.aux.training if self.aux is not None else False,
-                             aux_group=aux_group, logits_aux=out.get('logits_aux_cls'),
+                             aux_group=aux_group, logits_aux=out.get('logits_aux_cls'), frozen=self._frozen,
                              drop=self.last_drop_masks if do_aux else None)
             if do_crf_loss:
                 self.last.update(do_crf=True, crf_mask=crf_mask)
@@ -1585,7 +1617,7 @@ class StepEngine:
                 plan.K.pp_ms_loss_bwd(plan.ms['unit'].data_ptr(), plan.ms['sums'].data_ptr(), 1 if S['ms_mask'] else 0, gp('loss_ms'),
                                       plan.loss_scale, plan.dlogits.data_ptr(), B * K * H * W, st)
         with prof_range('backward: decoder'):
-            g6 = self._unet_backward_decoder(plan, S['bn_training'], grads, st)
+            g6 = self._unet_backward_decoder(plan, S['bn_training'], grads, st, need_g6=S['frozen'] < 6)
         if S['do_aux']:
             with prof_range('backward: aux path'):
                 if aux_side is not None:
@@ -1595,7 +1627,7 @@ class StepEngine:
                 self._aux_backward_conv(plan, S, grads, st)
                 self._bucket('aux')
         with prof_range('backward: encoder'):
-            self._unet_backward_encoder(plan, S['bn_training'], grads, g6, st)
+            self._unet_backward_encoder(plan, S['bn_training'], grads, g6, st, S['frozen'])
 
     def _aux_backward_head(self, plan, S, gp, grads, st):
         """The part of the auxiliary backward that depends on the loss gradients only: partial CE -> classifier (its weight
@@ -1628,15 +1660,23 @@ class StepEngine:
         drop = S['drop']
         grp = S['aux_group']
 
+        # freeze_encoder: the data gradient into a frozen stage's feature has no reader.  With every gathered stage frozen the
+        # bottleneck convolution gets no data gradient at all (its own parameters still train); else the launch writes all of its
+        # input channels and only the live stages' slices are added to their gradients
+        live = [s > S['frozen'] for s in a['stages']]
+
         def scatter(din: View):
             """din (B,h,w,Cin) += into the gradient slices of the stages the auxiliary input was gathered from."""
             c0 = 0
-            for s in a['stages']:
+            for s, on in zip(a['stages'], live):
                 dst = _batch(self._enc_grad_view(plan, s, None) if s != 6 else self._stage6_grad(plan), grp * B, B)
                 src = _sub(din, c0, dst.C)
-                plan.K.pp_copy_slab(src.ptr, src.ld, dst.ptr, dst.ld, dst.C, B * dst.H * dst.W, 1, st)
+                if on:
+                    plan.K.pp_copy_slab(src.ptr, src.ld, dst.ptr, dst.ld, dst.C, B * dst.H * dst.W, 1, st)
                 c0 += dst.C
-        if drop is not None:
+        if not any(live):
+            self._convbn_bwd(plan, LA, dfeat, None, False, S['aux_training'], grads, st)
+        elif drop is not None:
             ddin = a['drop_din']
             self._convbn_bwd(plan, LA, dfeat, ddin, False, S['aux_training'], grads, st)
             if a['alias_cat5']:

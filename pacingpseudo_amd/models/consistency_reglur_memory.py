@@ -21,7 +21,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .unet import UNet
+from .unet import UNet, release_from_slab
 from .aux_path_memory import AuxPath
 from ..engine import StepEngine
 from ..flat import FlatSlab
@@ -76,6 +76,18 @@ class ConsistencyRegulr(nn.Module):
         if self.backbone.final_conv.weight.is_cuda:
             self._flatten()
         return out
+
+    def freeze_encoder(self, n: int):
+        """``UNet.freeze_encoder`` for the composite model: the backbone is re-partitioned, the slab rebuilt without the
+        frozen parameters (the auxiliary path stays trainable) and packed weights are forgotten."""
+        self.backbone.freeze_encoder(n)
+        for p in self.aux_path.parameters():
+            release_from_slab(p)
+        self.flat = None
+        if self.backbone.final_conv.weight.is_cuda:
+            self._flatten()
+        self.engine.invalidate_packed()
+        return self
 
     def _flatten(self):
         segs = [('backbone', [p for p in self.backbone.parameters() if p.requires_grad]),

@@ -48,6 +48,15 @@ def check_checkpoint_norm(model, state_dict) -> None:
                          f'built with --norm_op {want}: pass --norm_op {have} (and the --norm_groups it was trained with)')
 
 
+def release_from_slab(p) -> None:
+    """Give a parameter its own storage again (a copy of its value) and forget its gradient view: the FlatSlab it lived in no
+    longer owns it, so the model that holds it flattens anew before its next step."""
+    if getattr(p, '_pp_flat', None) is not None:
+        p.data = p.data.clone()
+        del p._pp_flat
+    p.grad = None
+
+
 class ConvLayer(nn.Module):
     """conv3x3 -> BatchNorm2d (or GroupNorm) -> LeakyReLU(0.01) parameter holder (reference: models/unet.py:178-193).
     `norm_op` is called with the channel count, as in the reference: nn.BatchNorm2d, or a callable that builds an affine
@@ -189,6 +198,7 @@ class UNet(nn.Module):
         self.dec_block1 = DecBlock(ch[1], ch[0], ch[0], is_trans_conv=is_trans_conv, norm_op=norm)
         self.final_conv = nn.Conv2d(ch[0], num_classes, 1, 1)
         self._engine = None               # stand-alone (inference) engine, created lazily
+        self.frozen_stages = 0            # freeze_encoder(n): enc_block1 .. enc_block<n> hold constant weights and eval-mode norms
         # a loaded checkpoint (inference.py:138-146 through load_backbone) changes every weight: the stand-alone engine's
         # forward-only plans must re-pack their kernel-side layouts
         self.register_load_state_dict_post_hook(
@@ -200,6 +210,40 @@ class UNet(nn.Module):
 
     def dec_blocks(self):
         return {k: getattr(self, f'dec_block{k}') for k in (5, 4, 3, 2, 1)}
+
+    # ---- fine-tuning with a frozen encoder prefix ------------------------------------------------------------
+    def freeze_encoder(self, n: int):
+        """Hold ``enc_block1 .. enc_block<n>`` fixed (n = 0 .. 6; 0 = train everything): their parameters get
+        ``requires_grad=False`` and every other backbone parameter ``True`` (a second call re-partitions), their norm modules
+        stay in eval mode whatever ``train()`` says, and the engine neither updates their BatchNorm buffers nor launches any
+        of their backward kernels (engine.py: the backward walk stops in front of stage n).  The flat slab is dropped -- the
+        model flattens again without the frozen parameters, so weight decay, moments, the clipping norm and the EMA never see
+        them -- and packed weights are forgotten as after ``load_state_dict``.  Call it before the optimizer is built: an
+        optimizer that already holds slab state answers the next step with its "model was re-flattened" error."""
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= 6:
+            raise ValueError(f'freeze_encoder: n must be an integer in 0 .. 6 (got {n!r})')
+        frozen = {id(p) for k in range(1, n + 1) for p in getattr(self, f'enc_block{k}').parameters()}
+        for p in self.parameters():
+            release_from_slab(p)
+            p.requires_grad_(id(p) not in frozen)
+        self.frozen_stages = n
+        self._flat = None
+        self._apply_frozen_norm_mode()
+        if self._engine is not None:
+            self._engine.invalidate_packed()
+        return self
+
+    def _apply_frozen_norm_mode(self):
+        for k, e in enumerate(self.enc_blocks(), start=1):
+            for m in e.modules():
+                if isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
+                    m.training = bool(self.training and k > self.frozen_stages)
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        if self.frozen_stages:
+            self._apply_frozen_norm_mode()
+        return self
 
     # ---- flat parameter / gradient slabs of the stand-alone (fully-supervised) backbone ------------------------
     def _ensure_flat(self):

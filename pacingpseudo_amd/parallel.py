@@ -24,7 +24,7 @@ same statistics from epoch 1 on and rank 0's checkpoint reflects all shards.
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -59,7 +59,8 @@ def all_reduce_sum(t: torch.Tensor) -> None:
 
 
 def backbone_buckets(model) -> List[Tuple[str, List[torch.nn.Parameter]]]:
-    """Gradient buckets in the order the backward plan completes them (engine.backward_step)."""
+    """Gradient buckets in the order the backward plan completes them (engine.backward_step).  After ``freeze_encoder(n)`` the
+    frozen stages' parameters are in no bucket: `enc_rest` is empty from n = 4 on, then `enc5`, then `enc6`."""
     bb = model.backbone
 
     def ps(*mods):
@@ -81,12 +82,18 @@ class GradReducer:
         self.comm = comm
         self.model = model
         self.pending = []
-        self.ranges: Dict[str, Tuple[int, int]] = {}
+        self.ranges: Dict[str, Optional[Tuple[int, int]]] = {}
 
-    def _range(self, flat, tag) -> Tuple[int, int]:
-        r = self.ranges.get((id(flat), tag))
-        if r is None:
+    def _range(self, flat, tag) -> Optional[Tuple[int, int]]:
+        """Slab range of bucket `tag`; None for a bucket that freezing left without parameters (the same on every rank: the
+        frozen prefix is a flag of the run, so no rank enters a collective the others skip)."""
+        key = (id(flat), tag)
+        r = self.ranges.get(key)
+        if r is None and key not in self.ranges:
             params = dict(backbone_buckets(self.model))[tag]
+            if not params:
+                self.ranges[key] = None
+                return None
             offs = sorted((flat.offsets[p], p.numel()) for p in params)
             lo, hi = offs[0][0], offs[-1][0] + offs[-1][1]
             if sum(n for _, n in offs) != hi - lo:
@@ -97,7 +104,10 @@ class GradReducer:
 
     def bucket_ready(self, flat, tag: str) -> None:
         """Called by the engine right after the launches that complete bucket `tag` were enqueued."""
-        lo, hi = self._range(flat, tag)
+        r = self._range(flat, tag)
+        if r is None:
+            return
+        lo, hi = r
         if dist.get_backend(self.comm.group) == 'nccl':
             # RCCL: enqueued on its own stream behind the launches above, overlapped with the rest of the backward pass
             self.pending.append(dist.all_reduce(flat.grads[lo:hi], op=dist.ReduceOp.SUM, group=self.comm.group,
@@ -124,7 +134,12 @@ def sync_bn_buffers(model, group=None) -> None:
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
         return
     world = dist.get_world_size(group)
-    floats = [b for n, b in model.named_buffers() if n.endswith('running_mean') or n.endswith('running_var')]
+    # (the norm modules of a frozen encoder prefix stay in eval mode inside a training model: their statistics were never
+    # updated, are equal on all ranks already, and must stay bit for bit what the checkpoint held)
+    fixed = {id(b) for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and not m.training
+             and model.training for b in m.buffers(recurse=False)}
+    floats = [b for n, b in model.named_buffers()
+              if (n.endswith('running_mean') or n.endswith('running_var')) and id(b) not in fixed]
     if floats:
         flat = torch.cat([b.reshape(-1) for b in floats])
         dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
@@ -134,7 +149,7 @@ def sync_bn_buffers(model, group=None) -> None:
             b.copy_(flat[o:o + b.numel()].view_as(b))
             o += b.numel()
     for n, b in model.named_buffers():
-        if n.endswith('num_batches_tracked'):
+        if n.endswith('num_batches_tracked') and id(b) not in fixed:
             dist.broadcast(b, src=0, group=group)
 
 

@@ -28,8 +28,10 @@ VERSION = 1
 # (--graph_step replays the eager step bit for bit; --root / --tag only name the run directory, and a resumed run continues in
 # the directory its state file belongs to; --gpu_augment is an accepted no-op; --ema_val_interval only says how often the
 # averaged weights are looked at.)
+# (--init_from / --init_reset_head only say where a FRESH run takes its first weights from; a resumed run takes them from the
+# state file.  --freeze_encoder changes what is trained and is compared.)
 MAY_DIFFER = frozenset({'gpu', 'num_workers', 'graph_step', 'resume', 'state_interval', 'root', 'tag', 'gpu_augment',
-                        'ema_val_interval'})
+                        'ema_val_interval', 'init_from', 'init_reset_head'})
 # flags that are younger than the state-file format, with their parser defaults: a state file written before the flag existed
 # lacks the key, and the run it describes computed what the default computes
 ABSENT_DEFAULTS = {'clip_grad_norm': 0.0, 'ema_decay': 0.0, 'ema_val_interval': 1,
@@ -37,7 +39,8 @@ ABSENT_DEFAULTS = {'clip_grad_norm': 0.0, 'ema_decay': 0.0, 'ema_val_interval': 
                    'crf_sigma_xy': 6.0, 'crf_sigma_rgb': 0.1,
                    'do_loss_nc': False, 'loss_nc_weight': 0.1, 'ramp_up_loss_nc': False, 'nc_radius': 5, 'nc_dilation': 1,
                    'nc_sigma_xy': 6.0, 'nc_sigma_rgb': 0.1,
-                   'do_loss_ms': False, 'loss_ms_weight': 0.1, 'ramp_up_loss_ms': False, 'ms_tv_weight': 1.0}
+                   'do_loss_ms': False, 'loss_ms_weight': 0.1, 'ramp_up_loss_ms': False, 'ms_tv_weight': 1.0,
+                   'freeze_encoder': 0, 'init_from': None, 'init_reset_head': False}
 # attributes the drivers add to the namespace after parsing (not flags)
 _DERIVED = frozenset({'child', 'train_ls', 'val_ls'})
 

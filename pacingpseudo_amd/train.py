@@ -28,7 +28,7 @@ import time
 import numpy as np
 import torch
 
-from . import resume
+from . import finetune, resume
 from .losses.losses import check_crf_params, check_ms_params, check_nc_params
 from .optim import add_clip_flag, add_ema_flags, log_clip_stats, positive_float, positive_int
 
@@ -180,6 +180,7 @@ parser.add_argument('--ms_tv_weight', type=float, default=1.0,
 add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
 add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
+finetune.add_flags(parser)                    # --freeze_encoder N / --init_from PATH / --init_reset_head (pacingpseudo_amd/finetune.py)
 
 
 # The reference ships ONE driver (train_chaos.py) and three dataset packages that differ only in class tables and
@@ -263,6 +264,8 @@ def train_interface(args, resume_state=None):
                              max_step=args.epoch, update_momentum=args.update_momentum,
                              ensemble_mode=args.ensemble_mode),
         args_parser=args).cuda()
+    # --init_from / --freeze_encoder: before the optimizer, the EMA slab and the data-parallel broadcast see the parameters
+    finetune.init_model(args, model, parser, logging.info if rank == 0 else None)
     if world > 1:
         parallel.attach(model, sync_bn=args.sync_bn)
     if rank == 0:

@@ -24,7 +24,7 @@ import time
 import numpy as np
 import torch
 
-from . import resume
+from . import finetune, resume
 from .optim import add_clip_flag, add_ema_flags, log_clip_stats
 
 parser = argparse.ArgumentParser()
@@ -72,6 +72,7 @@ parser.add_argument('--gpu_augment', action='store_true', help='accepted for com
 add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
 add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
+finetune.add_flags(parser)                    # --freeze_encoder N / --init_from PATH / --init_reset_head (pacingpseudo_amd/finetune.py)
 
 
 def train_interface(args, resume_state=None):
@@ -92,6 +93,7 @@ def train_interface(args, resume_state=None):
     model = UNet(input_ch=args.input_ch, init_ch=args.init_ch, max_ch=args.max_ch, num_classes=args.num_classes,
                  output_stride=args.output_stride, is_stride_conv=args.is_stride_conv, is_trans_conv=args.is_trans_conv,
                  elab_end_points=args.elab_end_points, **norm_kwargs(args)).cuda()
+    finetune.init_model(args, model, parser, logging.info)      # --init_from / --freeze_encoder: before the optimizer exists
     logging.info(model)
     optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd, max_grad_norm=args.clip_grad_norm or None,
                           ema_decay=args.ema_decay or None)

@@ -488,7 +488,11 @@ int pp_conv1x1_nchw_to_nhwc_bwd_lazy(const float* dlogits, const float* x, int l
 /* torch.argmax(x, dim=1) on (N,C,HW) fp32 -> int64, first maximum wins (bit-exact pseudo-label masks) */
 int pp_argmax_channels(const float* x, int N, int C, int HW, int64_t* out, void* stream);
 /* sums[6] (double): pCE sum, #labelled, entropy sum, entropy denominator, consistency sum, consistency denominator.
- * cr_variant: 0 none, 1 ce_loss, 2 l1_loss, 3 l2_loss, 4 kl_loss (train_chaos.py:138).  In data-parallel runs the
+ * cr_variant: 0 none, 1 ce_loss, 2 l1_loss, 3 l2_loss, 4 kl_loss (train_chaos.py:138), 5 bikl_loss (half of KL(q||s) + KL(s||q)),
+ * 6 js_loss (Jensen-Shannon), 7 hard_ce_loss (cross entropy of the strong view against the first arg-max of the weak logits).
+ * Unmasked consistency denominator: N*HW*K for 1, 4, 5 (mean over N,K,H,W), N*HW for 2, 3, 6, 7 (channels reduced first); masked:
+ * max(sum(valid_mask), 1e-8) for all.  detach_weak drops the weak-logit gradient of 1, 2, 3, 5, 6; 4 ignores it, 7 has none.
+ * In data-parallel runs the
  * caller all-reduces `sums` before pp_losses_finalize / pp_seg_losses_bwd so losses and gradients are global. */
 size_t pp_seg_losses_workspace(int N, int HW);
 int pp_seg_losses_fwd(const float* logits_w, const float* logits_s, const int64_t* target, const float* valid_mask,

@@ -88,9 +88,160 @@ __device__ __forceinline__ float cr_value(const SM<MK>& w, const SM<MK>& s, int 
   return L;
 }
 
+// ... 5 bikl_loss, 6 js_loss, 7 hard_ce_loss (this implementation's additions to the CLI; bidirectional_kl_loss is
+// losses/losses.py:118-145).  They read the weak / strong log-probability gap t_k = lq_k - ls_k, and where the two views nearly
+// agree (late training) every term is a difference of nearly equal numbers: the rounding of lq_k and ls_k (~1e-7 each) would be
+// 1e-4 of a gap of 1e-3.  Where every logit difference d_k = zw_k - zs_k of the pixel is at most 1/2, cr_gaps therefore takes
+// t_k = d_k - C: d_k is exact to 3e-8 there, and the shift C = log-partition difference is read off the weak arg-max channel c*,
+// where the log-probabilities are smallest.  An error of C is the same for every k and cancels to first order in the terms below
+// (all but one: cr_gaps_recentre).  Elsewhere t_k = lq_k - ls_k as it stands: a d_k of two logits of magnitude 200 (spread 60) is
+// rounded at 1e-5, a log-probability of a class that matters is not.  The two forms approximate the same number; which one a
+// pixel takes changes nothing beyond rounding.
+// c* = first maximum of the weak logits (the tie rule of argmax_channels_kernel); all t_k are finite for finite logits.
+template <int MK>
+__device__ __forceinline__ int cr_gaps(const float (&vw)[MK], const float (&vs)[MK], const SM<MK>& w, const SM<MK>& s, int K,
+                                       float (&t)[MK]) {
+  float mx = vw[0], dmax = 0.f;
+  int cs = 0;
+#pragma unroll
+  for (int k = 1; k < MK; ++k)
+    if (k < K && vw[k] > mx) { mx = vw[k]; cs = k; }
+  float C = 0.f;
+#pragma unroll
+  for (int k = 0; k < MK; ++k) {
+    if (k == cs) C = (vw[k] - vs[k]) - (w.l[k] - s.l[k]);
+    if (k < K) dmax = fmaxf(dmax, fabsf(vw[k] - vs[k]));
+  }
+  const bool close = dmax <= 0.5f;
+#pragma unroll
+  for (int k = 0; k < MK; ++k) t[k] = k < K ? (close ? (vw[k] - vs[k]) - C : w.l[k] - s.l[k]) : 0.f;
+  return cs;
+}
+// q_k - s_k from the gap: s expm1(t) for t <= 0, -q expm1(-t) for t > 0.  expm1 of a non-positive number lies in (-1, 0], so
+// a probability that underflowed to 0 gives 0 * finite = 0.
+__device__ __forceinline__ float cr_pdiff(float q, float s, float t) {
+  const float e = expm1f(-fabsf(t));
+  return t <= 0.f ? s * e : -q * e;
+}
+// bikl_loss: (q_k - s_k) itself is first order in an error of C -- the one term here that is -- and sum_k (q_k - s_k) = 0 measures that
+// error: with every t_k off by e the sum comes out as e (times sum_k min(q_k, s_k)-like weights, 1 where the views agree), so it is
+// subtracted once.  Where the views disagree the sum is rounding noise of ~1e-7 against gaps of order 1.
+template <int MK>
+__device__ __forceinline__ void cr_gaps_recentre(const SM<MK>& w, const SM<MK>& s, int K, float (&t)[MK]) {
+  float e = 0.f;
+#pragma unroll
+  for (int k = 0; k < MK; ++k)
+    if (k < K) e += cr_pdiff(w.p[k], s.p[k], t[k]);
+#pragma unroll
+  for (int k = 0; k < MK; ++k)
+    if (k < K) t[k] -= e;
+}
+// js_loss: lq - lm and ls - lm with lm = log((q + s) / 2) = max(lq, ls) + log((1 + exp(-|t|)) / 2), a log-add-exp of the two
+// log-probabilities: h = log1p(expm1(-|t|) / 2) lies in [-ln 2, 0]; the larger of the two is -h, the smaller -|t| - h.
+__device__ __forceinline__ void cr_js_gaps(float t, float& qm, float& sm) {
+  const float at = fabsf(t), h = log1pf(0.5f * expm1f(-at));
+  qm = t <= 0.f ? -at - h : -h;
+  sm = t <= 0.f ? -h : -at - h;
+}
+template <int MK>
+__device__ __forceinline__ float cr_value_gap(const float (&vw)[MK], const float (&vs)[MK], const SM<MK>& w, const SM<MK>& s,
+                                              int K, int variant) {
+  float t[MK];
+  const int cs = cr_gaps(vw, vs, w, s, K, t);
+  float L = 0.f;
+  if (variant == 7) {                                           // -log s_{c*}
+#pragma unroll
+    for (int k = 0; k < MK; ++k) if (k == cs) L = -s.l[k];
+    return L;
+  }
+  if (variant == 5) cr_gaps_recentre(w, s, K, t);
+#pragma unroll
+  for (int k = 0; k < MK; ++k)
+    if (k < K) {
+      if (variant == 5) L += cr_pdiff(w.p[k], s.p[k], t[k]) * t[k];           // (q - s)(lq - ls)
+      else {
+        float qm, sm;
+        cr_js_gaps(t[k], qm, sm);
+        L += w.p[k] * qm + s.p[k] * sm;                                       // q (lq - lm) + s (ls - lm)
+      }
+    }
+  return 0.5f * L;
+}
+// their gradients, f = g_cr * m / denominator, in closed form (no quotient of probabilities):
+//   bikl  dz_s[k] = f/2 [(s_k - q_k) - s_k (t_k - sum_c s_c t_c)]     dz_w[k] = f/2 [(q_k - s_k) + q_k (t_k - sum_c q_c t_c)]
+//   js    dz_s[k] = f/2 s_k ((ls - lm)_k - sum_c s_c (ls - lm)_c)      dz_w[k] likewise with q, lq
+//   hard  dz_s[k] = f (s_k - [k == c*]), nothing to the weak logits
+template <int MK>
+__device__ __forceinline__ void cr_grad_gap(const float (&vw)[MK], const float (&vs)[MK], const SM<MK>& w, const SM<MK>& s,
+                                            int K, int variant, bool weak_grad, float f, float (&dw)[MK], float (&ds)[MK]) {
+  float t[MK];
+  const int cs = cr_gaps(vw, vs, w, s, K, t);
+  if (variant == 7) {
+#pragma unroll
+    for (int k = 0; k < MK; ++k)
+      if (k < K) ds[k] = f * (s.p[k] - (k == cs ? 1.f : 0.f));
+    return;
+  }
+  // s_k (x_k - sum_c s_c x_c) does not change when a constant is added to x, but its rounding does: in a confident pixel s_a -> 1,
+  // x_a and the sum are the same number, and their difference -- of the size of the runner-up's probability -- is lost below
+  // 1e-7 |x_a|.  So x is taken relative to its value at the arg-max a of the distribution it is weighted with (x_a = 0 exactly).
+  int as = 0;
+  {
+    float mx = vs[0];
+#pragma unroll
+    for (int k = 1; k < MK; ++k)
+      if (k < K && vs[k] > mx) { mx = vs[k]; as = k; }
+  }
+  const float hf = 0.5f * f;
+  if (variant == 5) {
+    cr_gaps_recentre(w, s, K, t);
+    float tw = 0.f, ts = 0.f;
+#pragma unroll
+    for (int k = 0; k < MK; ++k) { if (k == cs) tw = t[k]; if (k == as) ts = t[k]; }
+    float qt = 0.f, st = 0.f;
+#pragma unroll
+    for (int k = 0; k < MK; ++k)
+      if (k < K) { qt += w.p[k] * (t[k] - tw); st += s.p[k] * (t[k] - ts); }
+#pragma unroll
+    for (int k = 0; k < MK; ++k)
+      if (k < K) {
+        const float d = cr_pdiff(w.p[k], s.p[k], t[k]);
+        if (weak_grad) dw[k] += hf * (d + w.p[k] * ((t[k] - tw) - qt));
+        ds[k] = -hf * (d + s.p[k] * ((t[k] - ts) - st));
+      }
+    return;
+  }
+  float qm0 = 0.f, sm0 = 0.f;
+#pragma unroll
+  for (int k = 0; k < MK; ++k) {
+    float qm, sm;
+    if (k == cs) { cr_js_gaps(t[k], qm, sm); qm0 = qm; }
+    if (k == as) { cr_js_gaps(t[k], qm, sm); sm0 = sm; }
+  }
+  float qa = 0.f, sa = 0.f;
+#pragma unroll
+  for (int k = 0; k < MK; ++k)
+    if (k < K) {
+      float qm, sm;
+      cr_js_gaps(t[k], qm, sm);
+      qa += w.p[k] * (qm - qm0);
+      sa += s.p[k] * (sm - sm0);
+    }
+#pragma unroll
+  for (int k = 0; k < MK; ++k)
+    if (k < K) {
+      float qm, sm;
+      cr_js_gaps(t[k], qm, sm);
+      if (weak_grad) dw[k] += hf * w.p[k] * ((qm - qm0) - qa);
+      ds[k] = hf * s.p[k] * ((sm - sm0) - sa);
+    }
+}
+
 // sums[0]=pce_sum [1]=n_labelled [2]=ent_sum [3]=ent_den [4]=cr_sum [5]=cr_den   (double)
 struct SegAcc { float pce, n, ent, cr, m; };
-template <int MK>
+// GAP: the instantiation for the variants >= 5 (host-side choice).  They are kept out of the kernels of the variants 0 - 4, whose
+// code -- and register count: the t[] of cr_gaps costs 20 - 90 VGPRs and one to two waves of occupancy -- stays what it was.
+template <int MK, bool GAP>
 __device__ __forceinline__ void seg_fwd_pixel(const float (&vw)[MK], const float (&vs)[MK], long long t, float m, int K,
                                               int ignore_index, int do_ent, int variant, SegAcc& a) {
   SM<MK> w;
@@ -112,7 +263,8 @@ __device__ __forceinline__ void seg_fwd_pixel(const float (&vw)[MK], const float
   if (variant) {
     SM<MK> s;
     softmax_vals(vs, K, s);
-    a.cr += cr_value(w, s, K, variant) * m;
+    if constexpr (GAP) a.cr += cr_value_gap(vw, vs, w, s, K, variant) * m;
+    else a.cr += cr_value(w, s, K, variant) * m;
   }
 }
 
@@ -125,7 +277,7 @@ __device__ __forceinline__ void seg_acc_store(const SegAcc& a, float* sh, double
   }
 }
 
-template <int MK>
+template <int MK, bool GAP>
 __global__ __launch_bounds__(LS_THREADS) void seg_losses_partial_kernel(
     const float* __restrict__ zw, const float* __restrict__ zs, const long long* __restrict__ target,
     const float* __restrict__ mask, int N, int K, int HW, int ignore_index, int do_ent, int variant,
@@ -143,7 +295,7 @@ __global__ __launch_bounds__(LS_THREADS) void seg_losses_partial_kernel(
       vw[k] = k < K ? zw[off + (size_t)k * HW] : 0.f;
       vs[k] = (k < K && variant) ? zs[off + (size_t)k * HW] : 0.f;
     }
-    seg_fwd_pixel(vw, vs, target[p], mask ? mask[p] : 1.f, K, ignore_index, do_ent, variant, a);
+    seg_fwd_pixel<MK, GAP>(vw, vs, target[p], mask ? mask[p] : 1.f, K, ignore_index, do_ent, variant, a);
   }
   seg_acc_store(a, sh, partial);
 }
@@ -153,7 +305,7 @@ __global__ __launch_bounds__(LS_THREADS) void seg_losses_partial_kernel(
 // two dependent rounds of ten 4-byte loads per thread).  The per-pixel arithmetic is the same function in the same order; the
 // per-thread and per-block partial sums group the pixels differently, so the SUMS agree to rounding, not bit for bit.
 // Host side: HW % 4 == 0, pointers 16-byte aligned, K in {2, 4, 5} (the three data sets), P < 2^31.
-template <int KC>
+template <int KC, bool GAP>
 __global__ __launch_bounds__(LS_THREADS) void seg_losses_partial_v4_kernel(
     const float* __restrict__ zw, const float* __restrict__ zs, const long long* __restrict__ target,
     const float* __restrict__ mask, int N, int HW, int ignore_index, int do_ent, int variant,
@@ -181,7 +333,7 @@ __global__ __launch_bounds__(LS_THREADS) void seg_losses_partial_v4_kernel(
       float vw[LS_MAXK], vs[LS_MAXK];
 #pragma unroll
       for (int k = 0; k < LS_MAXK; ++k) { vw[k] = k < K ? w4[k < K ? k : 0][j] : 0.f; vs[k] = (k < K && variant) ? s4[k < K ? k : 0][j] : 0.f; }
-      seg_fwd_pixel(vw, vs, j < 2 ? t01[j] : t23[j - 2], m4[j], K, ignore_index, do_ent, variant, a);
+      seg_fwd_pixel<LS_MAXK, GAP>(vw, vs, j < 2 ? t01[j] : t23[j - 2], m4[j], K, ignore_index, do_ent, variant, a);
     }
   }
   seg_acc_store(a, sh, partial);
@@ -232,7 +384,7 @@ extern "C" int pp_seg_losses_fwd(const float* logits_w, const float* logits_s, c
                                  void* stream) {
   hipStream_t s = (hipStream_t)stream;
   PP_CHECK_ARG(logits_w && target && sums && workspace, "seg_losses_fwd: null pointer");
-  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && cr_variant >= 0 && cr_variant <= 4, "seg_losses_fwd: K=%d (1..%d) variant=%d", K, PP_MAXK, cr_variant);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && cr_variant >= 0 && cr_variant <= 7, "seg_losses_fwd: K=%d (1..%d) variant=%d", K, PP_MAXK, cr_variant);
   PP_CHECK_ARG(cr_variant == 0 || logits_s, "seg_losses_fwd: consistency loss needs the strong logits");
   if (workspace_bytes < pp_seg_losses_workspace(N, HW)) {
     pp_set_error("seg_losses_fwd: workspace too small");
@@ -241,20 +393,26 @@ extern "C" int pp_seg_losses_fwd(const float* logits_w, const float* logits_s, c
   const int blocks = ls_blocks((long long)N * HW, 1024);
   const double P = (double)N * HW;
   const double den_ent = P * K;                                       // loss.mean() over (N,K,H,W)
-  const double den_cr = (cr_variant == 2 || cr_variant == 3) ? P : P * K;   // l1/l2 reduce channels first
+  // l1 / l2 / js / hard_ce reduce channels first
+  const double den_cr = (cr_variant == 2 || cr_variant == 3 || cr_variant == 6 || cr_variant == 7) ? P : P * K;
   pp_prof_begin(PP_K_LOSS, 0.0, P * (8.0 * K + 12.0), s);
   const bool v4 = seg_v4_ok(logits_w, logits_s, target, valid_mask, nullptr, nullptr, N, K, HW);
-#define SEG_FWD_V4(KC) hipLaunchKernelGGL(seg_losses_partial_v4_kernel<KC>, dim3(blocks), dim3(LS_THREADS), 0, s, logits_w, logits_s, \
+  const bool gap = cr_variant >= 5;
+#define SEG_FWD_V4_(KC, GAP) hipLaunchKernelGGL((seg_losses_partial_v4_kernel<KC, GAP>), dim3(blocks), dim3(LS_THREADS), 0, s, logits_w, logits_s, \
                      (const long long*)target, valid_mask, N, HW, ignore_index, do_ent, cr_variant, (double*)workspace)
+#define SEG_FWD_V4(KC) do { if (gap) SEG_FWD_V4_(KC, true); else SEG_FWD_V4_(KC, false); } while (0)
   if (v4 && K == 5) SEG_FWD_V4(5);
   else if (v4 && K == 4) SEG_FWD_V4(4);
   else if (v4 && K == 2) SEG_FWD_V4(2);
   else
     pp_by_class_bound(K, [&](auto mk) {
-      hipLaunchKernelGGL(seg_losses_partial_kernel<decltype(mk)::value>, dim3(blocks), dim3(LS_THREADS), 0, s, logits_w, logits_s,
+      constexpr int MK = decltype(mk)::value;
+      auto kern = gap ? seg_losses_partial_kernel<MK, true> : seg_losses_partial_kernel<MK, false>;
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(LS_THREADS), 0, s, logits_w, logits_s,
                          (const long long*)target, valid_mask, N, K, HW, ignore_index, do_ent, cr_variant, (double*)workspace);
     });
 #undef SEG_FWD_V4
+#undef SEG_FWD_V4_
   hipLaunchKernelGGL(seg_losses_reduce_kernel, dim3(1), dim3(64), 0, s, (const double*)workspace, blocks,
                      valid_mask ? 1 : 0, cr_variant, den_ent, den_cr, sums);
   pp_prof_end(s);
@@ -282,7 +440,7 @@ __device__ __forceinline__ SegG seg_bwd_scales(const double* __restrict__ sums, 
   g.gc = (variant && g_cr) ? (float)((double)(*g_cr * grad_scale) / dc) : 0.f;
   return g;
 }
-template <int MK>
+template <int MK, bool GAP>
 __device__ __forceinline__ void seg_bwd_pixel(const float (&vw)[MK], const float (&vs)[MK], long long t, float m, int K,
                                               int ignore_index, int do_ent, int variant, int detach_weak, const SegG& g,
                                               float (&dw)[MK], float (&ds)[MK]) {
@@ -306,6 +464,10 @@ __device__ __forceinline__ void seg_bwd_pixel(const float (&vw)[MK], const float
   if (variant) {
     SM<MK> s;
     softmax_vals(vs, K, s);
+    if constexpr (GAP) {     // bikl_loss / js_loss honour detach_weak; hard_ce_loss has no weak-view gradient at all
+      cr_grad_gap(vw, vs, w, s, K, variant, !detach_weak, g.gc * m, dw, ds);
+      return;
+    }
     float u[MK], v[MK];
     float qu = 0.f, sv = 0.f;
 #pragma unroll
@@ -337,7 +499,7 @@ __device__ __forceinline__ void seg_bwd_pixel(const float (&vw)[MK], const float
   }
 }
 
-template <int MK>
+template <int MK, bool GAP>
 __global__ __launch_bounds__(LS_THREADS) void seg_losses_bwd_kernel(
     const float* __restrict__ zw, const float* __restrict__ zs, const long long* __restrict__ target,
     const float* __restrict__ mask, int N, int K, int HW, int ignore_index, int do_ent, int variant, int detach_weak,
@@ -355,7 +517,7 @@ __global__ __launch_bounds__(LS_THREADS) void seg_losses_bwd_kernel(
       vw[k] = k < K ? zw[off + (size_t)k * HW] : 0.f;
       vs[k] = (k < K && variant) ? zs[off + (size_t)k * HW] : 0.f;
     }
-    seg_bwd_pixel(vw, vs, target[p], mask ? mask[p] : 1.f, K, ignore_index, do_ent, variant, detach_weak, g, dw, ds);
+    seg_bwd_pixel<MK, GAP>(vw, vs, target[p], mask ? mask[p] : 1.f, K, ignore_index, do_ent, variant, detach_weak, g, dw, ds);
 #pragma unroll
     for (int k = 0; k < MK; ++k)
       if (k < K) {
@@ -366,7 +528,7 @@ __global__ __launch_bounds__(LS_THREADS) void seg_losses_bwd_kernel(
 }
 
 // four consecutive pixels per thread, compile-time K (see seg_losses_partial_v4_kernel): bit-identical gradients
-template <int KC>
+template <int KC, bool GAP>
 __global__ __launch_bounds__(LS_THREADS) void seg_losses_bwd_v4_kernel(
     const float* __restrict__ zw, const float* __restrict__ zs, const long long* __restrict__ target,
     const float* __restrict__ mask, int N, int HW, int ignore_index, int do_ent, int variant, int detach_weak,
@@ -394,7 +556,7 @@ __global__ __launch_bounds__(LS_THREADS) void seg_losses_bwd_v4_kernel(
       float vw[LS_MAXK], vs[LS_MAXK], dw[LS_MAXK], ds[LS_MAXK];
 #pragma unroll
       for (int k = 0; k < LS_MAXK; ++k) { vw[k] = k < K ? w4[k < K ? k : 0][j] : 0.f; vs[k] = (k < K && variant) ? s4[k < K ? k : 0][j] : 0.f; }
-      seg_bwd_pixel(vw, vs, j < 2 ? t01[j] : t23[j - 2], m4[j], K, ignore_index, do_ent, variant, detach_weak, g, dw, ds);
+      seg_bwd_pixel<LS_MAXK, GAP>(vw, vs, j < 2 ? t01[j] : t23[j - 2], m4[j], K, ignore_index, do_ent, variant, detach_weak, g, dw, ds);
 #pragma unroll
       for (int k = 0; k < K; ++k) { dw4[k][j] = dw[k]; ds4[k][j] = ds[k]; }
     }
@@ -413,24 +575,29 @@ extern "C" int pp_seg_losses_bwd(const float* logits_w, const float* logits_s, c
                                  float* dlogits_s, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   PP_CHECK_ARG(logits_w && target && sums && dlogits_w, "seg_losses_bwd: null pointer");
-  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && cr_variant >= 0 && cr_variant <= 4, "seg_losses_bwd: K=%d (1..%d) variant=%d", K, PP_MAXK, cr_variant);
+  PP_CHECK_ARG(K >= 1 && K <= PP_MAXK && cr_variant >= 0 && cr_variant <= 7, "seg_losses_bwd: K=%d (1..%d) variant=%d", K, PP_MAXK, cr_variant);
   PP_CHECK_ARG(cr_variant == 0 || (logits_s && dlogits_s), "seg_losses_bwd: consistency loss needs the strong logits");
   const double P = (double)N * HW;
   pp_prof_begin(PP_K_LOSS, 0.0, P * (16.0 * K + 12.0), s);
   const bool v4 = seg_v4_ok(logits_w, logits_s, target, valid_mask, dlogits_w, dlogits_s, N, K, HW);
-#define SEG_BWD_V4(KC) hipLaunchKernelGGL(seg_losses_bwd_v4_kernel<KC>, dim3(ls_blocks((long long)N * HW / 4, 8192)), dim3(LS_THREADS), 0, s, \
+  const bool gap = cr_variant >= 5;
+#define SEG_BWD_V4_(KC, GAP) hipLaunchKernelGGL((seg_losses_bwd_v4_kernel<KC, GAP>), dim3(ls_blocks((long long)N * HW / 4, 8192)), dim3(LS_THREADS), 0, s, \
                      logits_w, logits_s, (const long long*)target, valid_mask, N, HW, ignore_index, do_ent, cr_variant,        \
                      detach_weak, sums, valid_mask ? 1 : 0, g_pce, g_ent, g_cr, grad_scale, dlogits_w, dlogits_s)
+#define SEG_BWD_V4(KC) do { if (gap) SEG_BWD_V4_(KC, true); else SEG_BWD_V4_(KC, false); } while (0)
   if (v4 && K == 5) SEG_BWD_V4(5);
   else if (v4 && K == 4) SEG_BWD_V4(4);
   else if (v4 && K == 2) SEG_BWD_V4(2);
   else
     pp_by_class_bound(K, [&](auto mk) {
-      hipLaunchKernelGGL(seg_losses_bwd_kernel<decltype(mk)::value>, dim3(ls_blocks((long long)N * HW)), dim3(LS_THREADS), 0, s, logits_w,
+      constexpr int MK = decltype(mk)::value;
+      auto kern = gap ? seg_losses_bwd_kernel<MK, true> : seg_losses_bwd_kernel<MK, false>;
+      hipLaunchKernelGGL(kern, dim3(ls_blocks((long long)N * HW)), dim3(LS_THREADS), 0, s, logits_w,
                          logits_s, (const long long*)target, valid_mask, N, K, HW, ignore_index, do_ent, cr_variant,
                          detach_weak, sums, valid_mask ? 1 : 0, g_pce, g_ent, g_cr, grad_scale, dlogits_w, dlogits_s);
     });
 #undef SEG_BWD_V4
+#undef SEG_BWD_V4_
   pp_prof_end(s);
   return pp_launch_status("seg_losses_bwd");
 }

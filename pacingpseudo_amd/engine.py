@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from ._lib import PpBnCoefItem, PpLazyIn, PpPackItem, PpWinoPackItem, lib, lib_for, prof_range, stream_ptr
 from .convop import ConvOp, select as conv_select
-from .losses.losses import check_crf_params, check_ms_params, check_nc_params
+from .losses.losses import _VARIANT, check_crf_params, check_ms_params, check_nc_params
 
 WINO_ENABLED = os.environ.get('PP_WINO', '1') != '0'      # A/B switch for the Winograd path
 # split-fp16 ("f16x3") direct convolution for the non-Winograd layers with at least this many output channels
@@ -84,7 +84,7 @@ WINO_MIN_COUT = 64
 SLOPE = 1e-2
 BN_EPS = 1e-5
 BN_MOM = 0.1
-CR_VARIANTS = {'ce_loss': 1, 'l1_loss': 2, 'l2_loss': 3, 'kl_loss': 4}
+CR_VARIANTS = _VARIANT      # --loss_cr_variants name -> cr_variant code of pp_seg_losses_*: the functional API's table, one object
 
 class View:
     """NHWC view: element (n,y,x,c) lives at ptr + es*(((n*H+y)*W+x)*ld + c), es = bytes per element (4: fp32, 2: the fp16

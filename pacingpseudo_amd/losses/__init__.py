@@ -1,1 +1,2 @@
-from .losses import mumford_shah_loss, normalized_cut_loss  # noqa: F401
+from .losses import (bidirectional_kl_loss, hard_label_cross_entropy_loss, js_loss, mumford_shah_loss,  # noqa: F401
+                     normalized_cut_loss)

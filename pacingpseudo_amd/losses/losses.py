@@ -19,7 +19,8 @@ import torch
 
 from .._lib import lib, stream_ptr
 
-_VARIANT = {'ce_loss': 1, 'l1_loss': 2, 'l2_loss': 3, 'kl_loss': 4}
+# cr_variant codes of pp_seg_losses_fwd / _bwd (include/pacingpseudo_hip.h); engine.CR_VARIANTS is this table
+_VARIANT = {'ce_loss': 1, 'l1_loss': 2, 'l2_loss': 3, 'kl_loss': 4, 'bikl_loss': 5, 'js_loss': 6, 'hard_ce_loss': 7}
 
 
 def _check(t, name):
@@ -160,6 +161,25 @@ def kl_loss(input, target, valid_mask=None):
     """KL(softmax(target) || softmax(input)) element-wise, masked mean; both arguments are logits and both
     receive gradients (losses/losses.py:98-116)."""
     return _consistency(input, target, valid_mask, 'kl_loss', False)
+
+
+def bidirectional_kl_loss(input, target, valid_mask=None):
+    """(KL(softmax(target) || softmax(input)) + KL(softmax(input) || softmax(target))) / 2 element-wise, masked mean; both
+    arguments are logits and both receive gradients (losses/losses.py:118-145)."""
+    return _consistency(input, target, valid_mask, 'bikl_loss', False)
+
+
+def js_loss(input, target, valid_mask=None):
+    """Jensen-Shannon divergence of softmax(input) and softmax(target) per pixel (in [0, ln 2]), masked mean over the pixels (this
+    implementation's addition; the reference has no such loss); both arguments are logits and both receive gradients."""
+    return _consistency(input, target, valid_mask, 'js_loss', False)
+
+
+def hard_label_cross_entropy_loss(input, target, valid_mask=None):
+    """Cross entropy of softmax(input) against the arg-max over the channels of `target` (first maximum, as torch.argmax), masked
+    mean over the pixels (this implementation's addition; the reference has no such loss).  `target` is a constant: it gets a zero
+    gradient."""
+    return _consistency(input, target.detach() if torch.is_tensor(target) else target, valid_mask, 'hard_ce_loss', True)
 
 
 class _DiceLoss(torch.autograd.Function):

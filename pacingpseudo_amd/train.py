@@ -94,8 +94,9 @@ _flags('decoder consistency', '128-145', [
     ('do_decoder_consistency', dict(default=False, help='second (strong-view) pass + consistency loss between the two predictions', **_on)),
     ('ramp_up_loss_cr', dict(default=True, help='Gaussian ramp-up of its weight', **_on)),
     ('detach_weak_cr', dict(default=False, help='treat the weak-view probabilities as a constant target', **_on)),
-    ('loss_cr_variants', dict(type=str, default='ce_loss', choices=['ce_loss', 'l1_loss', 'l2_loss', 'kl_loss'],
-                              help='form of the consistency loss (all four in pp_seg_losses_*)')),
+    ('loss_cr_variants', dict(type=str, default='ce_loss', choices=['ce_loss', 'l1_loss', 'l2_loss', 'kl_loss', 'bikl_loss', 'js_loss', 'hard_ce_loss'],
+                              help='form of the consistency loss (all seven in pp_seg_losses_*; the last three -- symmetric KL, '
+                                   'Jensen-Shannon, cross entropy against the weak arg-max -- are additions to the reference)')),
     ('strength', dict(type=float, default=1., choices=[0.125, 0.25, 0.5, 1.], help='range of the strong view\'s colour transforms')),
     ('loss_cr_weight', dict(type=float, default=1., help='weight of the consistency loss')),
 ])

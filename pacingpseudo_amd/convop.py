@@ -1,7 +1,7 @@
 """Which 3x3-convolution kernel family a layer runs on, and the one object per layer and plan that calls it.
 
 `select` decides once per (layer, shape, storage); `ConvOp` turns "this operation, these operands" into the one C-ABI call of that
-family.  Streams, events, the choice of workspace and everything BatchNorm / GroupNorm stay in the engine.
+family.  Streams, events and the choice of workspace stay in the engine; everything BatchNorm / GroupNorm is normop.py's.
 """
 from __future__ import annotations
 

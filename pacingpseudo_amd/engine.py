@@ -30,6 +30,7 @@ import torch.nn as nn
 
 from ._lib import PpBnCoefItem, PpLazyIn, PpPackItem, PpWinoPackItem, lib, lib_for, prof_range, stream_ptr
 from .convop import ConvOp, select as conv_select
+from .normop import NormOp
 from .losses.losses import _VARIANT, check_crf_params, check_ms_params, check_nc_params
 
 WINO_ENABLED = os.environ.get('PP_WINO', '1') != '0'      # A/B switch for the Winograd path
@@ -178,8 +179,6 @@ class _Layer:
         # per-plan state (set by _Plan)
         self.x: Optional[View] = None
         self.y: Optional[View] = None
-        self.z = None
-        self.coef = None
         self.groups = 1
 
 
@@ -262,13 +261,10 @@ class _Plan:
         self.mid: Dict[str, View] = {}
         self.zbuf: Dict[str, torch.Tensor] = {}
         self.coef: Dict[str, torch.Tensor] = {}
-        self.bn_sums: Dict[str, torch.Tensor] = {}
         self.conv: Dict[str, ConvOp] = {}  # per layer: its kernel family (.sel) and packed weights, bound to self.K
+        self.norm: Dict[str, NormOp] = {}  # per layer: its BatchNorm / GroupNorm launches, bound to self.K and the buffers above
         self.wino_ws = 0
         self.wg_ws_bytes = 0               # workspace of the weight-gradient calls alone (they may run on a second stream)
-        # stride-2 convolutions run as stride-1 convolutions at the input resolution: full-resolution z and (zero-stuffed) dz
-        self.zfull: Dict[str, torch.Tensor] = {}
-        self.dzfull: Dict[str, torch.Tensor] = {}
         self.ct_ws = 0                     # ConvTranspose2d weight-gradient workspace (--is_trans_conv)
 
         # ---- which layer outputs stay LAZY in train-mode BN (static per plan): every consumer of the tensor must have a
@@ -321,16 +317,17 @@ class _Plan:
             if not (self.lazy_out[L.name] and FUSE_BN):
                 self.zbuf[L.name] = act(n, h, w, L.cout)[0]
             # GroupNorm: [mean, invstd, scale, shift, xbar] rows per IMAGE (pp_gn_stats), whatever the statistics groups
-            self.coef[L.name] = torch.empty((5, n, L.cout) if L.gn else (4, groups, L.cout), **f32)
+            coef = self.coef[L.name] = torch.empty((5, n, L.cout) if L.gn else (4, groups, L.cout), **f32)
             # per-channel sums of the split (synchronised) BatchNorm calls: [0] forward, [1] backward local, [2] backward global
-            self.bn_sums[L.name] = torch.zeros((3, groups, 2, L.cout), device=dev, dtype=torch.float64)
-            if L.stride == 2:                  # (h, w) = output size; the convolution itself runs at (2 h, 2 w)
-                self.zfull[L.name] = act(n, 2 * h, 2 * w, L.cout)[0]
-                if trainable:
-                    self.dzfull[L.name] = act(n, 2 * h, 2 * w, L.cout)[0]
-                conv_bufs(L, n, 2 * h, 2 * w)
-            else:
-                conv_bufs(L, n, h, w)
+            sums = torch.zeros((3, groups, 2, L.cout), device=dev, dtype=torch.float64)
+            # a stride-2 convolution runs as a stride-1 convolution at the input resolution, (2 h, 2 w) for the output size (h, w):
+            # full-resolution z and (zero-stuffed) dz
+            s = L.stride
+            zfull = act(n, 2 * h, 2 * w, L.cout)[0] if s == 2 else None
+            dzfull = act(n, 2 * h, 2 * w, L.cout)[0] if (s == 2 and trainable) else None
+            conv_bufs(L, n, s * h, s * w)
+            self.norm[L.name] = NormOp(self.K, L, SLOPE, BN_EPS, BN_MOM, coef, self.zbuf.get(L.name), self.lazy_out[L.name], sums,
+                                       zfull, dzfull, self.conv[L.name].amax)
 
         cur = self.x0
         for k, e in enumerate(encs, start=1):
@@ -399,11 +396,7 @@ class _Plan:
                 a['in'] = act(B, ha, wa, LA.cin_pad)[1]
                 if trainable:
                     a['din'] = act(B, ha, wa, LA.cin_pad)[1]
-            self.bn_stats_bytes = max(self.bn_stats_bytes, lib.pp_conv3x3_bn_stats_bytes(LA.cout, B, ha, wa, 1))
-            self.zbuf[LA.name] = act(B, ha, wa, LA.cout)[0]          # the aux features are always materialised (memory_update reads them)
-            self.coef[LA.name] = torch.empty((4, 1, LA.cout), **f32)
-            self.bn_sums[LA.name] = torch.zeros((3, 1, 2, LA.cout), device=dev, dtype=torch.float64)
-            conv_bufs(LA, B, ha, wa)
+            layer_bufs(LA, B, ha, wa, 1)        # (never lazy: the aux features are always materialised, memory_update reads them)
             a['feat'] = act(B, ha, wa, LA.cout)[1]
             if trainable:
                 a['dfeat'] = act(B, ha, wa, LA.cout)[1]
@@ -782,139 +775,68 @@ class StepEngine:
                     'enc_block1 .. enc_block<n> as a whole')
         return n
 
+    def _sync(self, training) -> bool:
+        """Synchronised BatchNorm applies: train-mode statistics of a data-parallel run over the GLOBAL batch."""
+        return bool(training and self.comm is not None and self.sync_bn)
+
     def _convbn_fwd(self, plan, L: _Layer, x: View, y: View, groups, training, st, pool_out: Optional[View] = None,
                     record: bool = True):
         """conv3x3 + BatchNorm + LeakyReLU of one layer.  pool_out: where the 2x2 max-pooled copy of the output goes when the
         caller wants it from the same pass; returns True when it was written (train-mode apply pass), else the caller pools.
         record=False: a layer of a frozen stage -- nothing is kept for a backward pass."""
-        coef = plan.coef[L.name]
-        op = plan.conv[L.name]
-        C = L.cout
+        op, nop = plan.conv[L.name], plan.norm[L.name]
         assert x.C == L.cin_pad, (L.name, x.C, L.cin_pad)
-        ppg = (x.N // groups) * (x.H // L.stride) * (x.W // L.stride)        # pixels of the OUTPUT per group
-        mean, invstd, scale, shift = (coef[i].data_ptr() for i in range(4))
-        bn = L.bn
-        sync = training and self.comm is not None and self.sync_bn
         # LAZY output (train-mode BN): z goes straight into the buffer of y, the finalize writes the layer's (scale, shift,
         # slope) rows next to it and the separate normalise + activate pass (pp_bn_lrelu_fwd) does not run: the consumers
         # of the tensor evaluate y while they load it (plan.lazy_out guarantees that each of them can)
-        lazy = bool(training and plan.lazy_out[L.name])
-        zptr, zld = (y.ptr, y.ld) if lazy else ((plan.zbuf[L.name].data_ptr(), C) if L.name in plan.zbuf else (None, C))
+        lazy = bool(training and nop.lazy)
+        zptr, zld = nop.z_dest(y, lazy)
         L.x, L.y, L.groups = x, y, groups
         if self._rec is not None and record:
             # what this step's backward reads (kept with the step, not the layer): input view (+ whether it was lazy),
             # output view, groups, whether the output is lazy (then the output buffer holds z)
             self._rec[L.name] = (x, y, groups, lazy, x.lazy)
-        if L.gn:
-            return self._convgn_fwd(plan, L, x, y, zptr, zld, st, pool_out)
-
-        def finalize(sums_ptr, rows, n_per_group):
-            args = (sums_ptr, rows, C, n_per_group, groups, BN_EPS, BN_MOM, bn.weight.data_ptr(), bn.bias.data_ptr(),
-                    bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr(),
-                    mean, invstd, scale, shift)
-            if lazy:
-                plan.K.pp_bn_train_finalize_lazy(*args, y.cptr, y.ld, SLOPE, st)
-                y.flag[0] = True
-            else:
-                plan.K.pp_bn_train_finalize(*args, st)
-
+        ws = plan.ws_args()
+        stats = None        # (pointer, rows per group) of the statistics a fused convolution epilogue left
         if L.stride == 2:
             assert not lazy
-            # stride-2 / padding-1 convolution = the stride-1 convolution sampled at the even pixels (pp_spatial.hip)
-            zf = plan.zfull[L.name]
-            op.fwd(x, zf.data_ptr(), C, plan.ws_args(), st)
-            plan.K.pp_stride2_gather(zf.data_ptr(), C, zptr, C, C, x.N, x.H // 2, x.W // 2, st)
-        elif FUSE_BN:
-            if training:
-                # z + per-block (sum, sum of squares) from the conv epilogue -> finalize -> y = lrelu(z*scale + shift)
-                rows = op.fwd_bn(x, zptr, zld, groups, 1, None, None, plan.stats_args(), plan.ws_args(), plan.rows_out, st)
-                if sync:
-                    # reference semantics under sharding: statistics of the WHOLE batch (models/unet.py:189) -- the local
-                    # sums are taken again in ONE row per group (the epilogue's per-block rows are not all-reduced)
-                    sums = plan.bn_sums[L.name][0]
-                    plan.K.pp_bn_stats_sums(zptr, zld, C, ppg, groups, sums.data_ptr(), *plan.ws_args(), st)
-                    self.comm.allreduce_sums(sums)
-                    finalize(sums.data_ptr(), 1, ppg * self.world)
-                else:
-                    finalize(plan.stats_args()[0], rows, ppg)
-                if not lazy:
-                    if pool_out is not None and FUSE_POOL_FWD:
-                        plan.K.pp_bn_lrelu_fwd_pool(zptr, zld, scale, shift, y.ptr, y.ld, pool_out.ptr, pool_out.ld, C, y.N, y.H, y.W,
-                                                 groups, SLOPE, st)
-                        return True
-                    plan.K.pp_bn_lrelu_fwd(zptr, zld, scale, shift, y.ptr, y.ld, C, ppg, groups, SLOPE, st)
-            else:
-                # running statistics are known before the convolution: the epilogue writes y, z never exists.  (The backbone's
-                # coefficient rows were written by ONE launch at the start of the forward: _eval_coeffs_batch.)
-                if L.name not in self._coefs_ready:
-                    plan.K.pp_bn_eval_coeffs(C, groups, BN_EPS, bn.weight.data_ptr(), bn.bias.data_ptr(),
-                                          bn.running_mean.data_ptr(), bn.running_var.data_ptr(), mean, invstd, scale, shift, st)
-                op.fwd_bn(x, y.ptr, y.ld, groups, 2, scale, shift, plan.stats_args(), plan.ws_args(), plan.rows_out, st)
-            return
-        else:               # (PP_FUSE_BN=0 implies PP_LAZY_BN=0: no input is lazy here)
-            op.fwd(x, zptr, zld, plan.ws_args(), st)
-        if sync:
-            # reference semantics under sharding: statistics of the WHOLE batch (models/unet.py:189)
-            sums = plan.bn_sums[L.name][0]
-            plan.K.pp_bn_stats_sums(zptr, zld, C, ppg, groups, sums.data_ptr(), *plan.ws_args(), st)
-            self.comm.allreduce_sums(sums)
-            finalize(sums.data_ptr(), 1, ppg * self.world)
+            # stride-2 / padding-1 convolution = the stride-1 convolution sampled at the even pixels (NormOp.fwd gathers them)
+            op.fwd(x, nop.zfull.data_ptr(), L.cout, ws, st)
+        elif not FUSE_BN or L.gn:       # (PP_FUSE_BN=0 implies PP_LAZY_BN=0: no input is lazy here)
+            op.fwd(x, zptr, zld, ws, st)
         elif training:
-            assert not lazy
-            plan.K.pp_bn_train_stats(zptr, zld, C, ppg, groups, BN_EPS, BN_MOM, bn.weight.data_ptr(),
-                                  bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                  bn.num_batches_tracked.data_ptr(), mean, invstd, scale, shift,
-                                  *plan.ws_args(), st)
+            # z + per-block (sum, sum of squares) from the conv epilogue -> finalize -> y = lrelu(z*scale + shift)
+            rows = op.fwd_bn(x, zptr, zld, groups, 1, None, None, plan.stats_args(), ws, plan.rows_out, st)
+            stats = (plan.stats_args()[0], rows)
         else:
-            plan.K.pp_bn_eval_coeffs(C, groups, BN_EPS, bn.weight.data_ptr(), bn.bias.data_ptr(),
-                                  bn.running_mean.data_ptr(), bn.running_var.data_ptr(), mean, invstd, scale, shift, st)
-        if not lazy:
-            plan.K.pp_bn_lrelu_fwd(zptr, zld, scale, shift, y.ptr, y.ld, C, ppg, groups, SLOPE, st)
-
-    def _convgn_fwd(self, plan, L: _Layer, x: View, y: View, zptr, zld, st, pool_out: Optional[View] = None):
-        """conv3x3 + GroupNorm + LeakyReLU of one layer, the same in train and eval mode: z = conv(x) (no fused epilogue),
-        per-(image, group) statistics (pp_gn_stats), then the BatchNorm apply pass with one coefficient row per image."""
-        C, gn = L.cout, L.bn
-        assert L.stride == 1
-        plan.conv[L.name].fwd(x, zptr, zld, plan.ws_args(), st)
-        coef = plan.coef[L.name]
-        mean, invstd, scale, shift, xbar = (coef[i].data_ptr() for i in range(5))
-        N, HW = x.N, x.H * x.W
-        plan.K.pp_gn_stats(zptr, zld, C, HW, N, gn.num_groups, float(gn.eps), gn.weight.data_ptr(), gn.bias.data_ptr(),
-                           mean, invstd, xbar, scale, shift, *plan.ws_args(), st)
-        if pool_out is not None and FUSE_POOL_FWD:
-            plan.K.pp_bn_lrelu_fwd_pool(zptr, zld, scale, shift, y.ptr, y.ld, pool_out.ptr, pool_out.ld, C, N, y.H, y.W, N, SLOPE, st)
-            return True
-        plan.K.pp_bn_lrelu_fwd(zptr, zld, scale, shift, y.ptr, y.ld, C, HW, N, SLOPE, st)
-        return False
+            # running statistics are known before the convolution: the epilogue writes y, z never exists.  (The backbone's
+            # coefficient rows were written by ONE launch at the start of the forward: _eval_coeffs_batch.)
+            if L.name not in self._coefs_ready:
+                nop.eval_coeffs(groups, st)
+            op.fwd_bn(x, y.ptr, y.ld, groups, 2, *nop.rows[2:], plan.stats_args(), ws, plan.rows_out, st)
+            return False
+        # the max-pooled copy comes from the apply pass behind a fused epilogue or GroupNorm statistics
+        pool_out = pool_out if (FUSE_POOL_FWD and (stats is not None or L.gn)) else None
+        return nop.fwd(zptr, zld, y, groups, training, lazy, stats, self._sync(training), self.comm, self.world, pool_out, ws, st)
 
     def _convbn_bwd(self, plan, L: _Layer, dy: View, dx: Optional[View], dx_accumulate, training, grads, st, pool: Optional[View] = None):
         """dy: gradient wrt the layer output.  Writes parameter gradients, and dx (+)= data gradient.  pool: gradient of the
         2x2-max-pooled copy of the layer output (half the size of dy), added to each window's winner inside the BatchNorm backward."""
-        coef = plan.coef[L.name]
-        C = L.cout
-        x, y_rec, groups, lazy_out, x_lazy = self._bwd_rec[L.name]
-        # pre-BatchNorm output of the forward: in the layer's own z buffer, or -- lazy layer -- in the buffer of its output
-        zptr, zld = (y_rec.ptr, y_rec.ld) if lazy_out else ((plan.zbuf[L.name].data_ptr(), C) if L.name in plan.zbuf else (None, C))
-        op = plan.conv[L.name]
+        # (y: the forward's output view; lazy_out: its buffer holds the pre-BatchNorm z instead)
+        x, y, groups, lazy_out, x_lazy = self._bwd_rec[L.name]
+        op, nop = plan.conv[L.name], plan.norm[L.name]
         kind = op.sel.kind
         xlz = x.lazy_arg() if (x_lazy and kind != 'wino') else None      # (Winograd: the kept V was made from y already)
         assert not x_lazy or kind == 'wino' or (xlz is not None and kind == 'f16x3'), f'{L.name}: lazy input without a lazy weight gradient'
-        ppg = (x.N // groups) * (x.H // L.stride) * (x.W // L.stride)        # pixels of the layer OUTPUT per group
-        mean, invstd, scale, shift = (coef[i].data_ptr() for i in range(4))
-        gw, gb, gg, gbeta = grads[L.conv.weight], grads[L.conv.bias], grads[L.bn.weight], grads[L.bn.bias]
+        gw = grads[L.conv.weight]
+        pg = (grads[L.bn.weight].data_ptr(), grads[L.bn.bias].data_ptr(), grads[L.conv.bias].data_ptr())
+        sync = self._sync(training)
+        eval_fused = FUSE_BN and not training       # eval-mode BN: the forward epilogue wrote y only
+        ws = (plan.ws.data_ptr(), plan.ws_bytes)
         if (FUSE_WG1 and not L.gn and dx is None and pool is None and L.cin == 1 and L.stride == 1 and L.dil == 1 and not x_lazy
-                and kind == 'fp32' and not (training and self.comm is not None and self.sync_bn)):
-            # the first layer: dz has one reader, the weight gradient -- formed and consumed in one pass, never written
-            if FUSE_BN and not training:
-                plan.K.pp_bn_lrelu_bwd_eval_wgrad_c1(dy.ptr, dy.ld, y_rec.ptr, y_rec.ld, scale, L.bn.weight.data_ptr(), L.bn.bias.data_ptr(),
-                                                  x.ptr, x.ld, x.H, x.W, gw.data_ptr(), 0, gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(),
-                                                  0, C, ppg * groups, SLOPE, plan.ws.data_ptr(), plan.ws_bytes, st)
-            else:
-                plan.K.pp_bn_lrelu_bwd_wgrad_c1(dy.ptr, dy.ld, zptr, zld, scale, shift, mean, invstd, L.bn.weight.data_ptr(),
-                                             1 if training else 0, x.ptr, x.ld, x.H, x.W, gw.data_ptr(), 0, gg.data_ptr(),
-                                             gbeta.data_ptr(), gb.data_ptr(), 0, C, ppg, groups, SLOPE, plan.ws.data_ptr(),
-                                             plan.ws_bytes, st)
+                and kind == 'fp32' and not sync):
+            # the first layer: dz has one reader, the weight gradient
+            nop.bwd_wgrad_c1(dy, y, lazy_out, x, groups, gw.data_ptr(), pg, training, eval_fused, ws, st)
             return
         side = self._side_stream(plan)
         slot = 0
@@ -923,65 +845,14 @@ class StepEngine:
             plan.dz_slot ^= 1
             if plan.wg_pending[slot]:                   # the weight gradient that last read this dz buffer (two layers ago)
                 torch.cuda.current_stream().wait_event(plan.wg_done[slot])
-        dz = (plan.s1b if slot else plan.s1).data_ptr()
-        am = op.amax.data_ptr() if op.amax is not None else None      # split-fp16 consumers scale dz by a power of two from max |dz|
-        if L.gn:
-            # GroupNorm: statistics of this forward per (image, group), whatever `training` and sync_bn say
-            xbar, gn = coef[4].data_ptr(), L.bn
-            if pool is not None:
-                y = y_rec
-                plan.K.pp_gn_lrelu_bwd_pool(dy.ptr, dy.ld, pool.ptr, pool.ld, zptr, zld, scale, shift, mean, invstd, xbar,
-                                            gn.weight.data_ptr(), dz, C, gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C, y.N,
-                                            y.H, y.W, gn.num_groups, SLOPE, plan.ws.data_ptr(), plan.ws_bytes, am, st)
-            else:
-                plan.K.pp_gn_lrelu_bwd(dy.ptr, dy.ld, zptr, zld, scale, shift, mean, invstd, xbar, gn.weight.data_ptr(), dz, C,
-                                       gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C, x.H * x.W, x.N, gn.num_groups, SLOPE,
-                                       plan.ws.data_ptr(), plan.ws_bytes, am, st)
-        elif pool is not None:
-            y = y_rec
-            if FUSE_BN and not training:
-                plan.K.pp_bn_lrelu_bwd_eval_pool(dy.ptr, dy.ld, pool.ptr, pool.ld, y.ptr, y.ld, scale, L.bn.weight.data_ptr(),
-                                              L.bn.bias.data_ptr(), dz, C, gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C,
-                                              y.N, y.H, y.W, SLOPE, plan.ws.data_ptr(), plan.ws_bytes, am, st)
-            else:
-                plan.K.pp_bn_lrelu_bwd_pool(dy.ptr, dy.ld, pool.ptr, pool.ld, zptr, zld, scale, shift, mean, invstd,
-                                         L.bn.weight.data_ptr(), 1 if training else 0, dz, C, gg.data_ptr(), gbeta.data_ptr(),
-                                         gb.data_ptr(), 0, C, y.N, y.H, y.W, groups, SLOPE, plan.ws.data_ptr(), plan.ws_bytes, am, st)
-        elif FUSE_BN and not training:
-            # eval-mode BN: the forward epilogue wrote y only; one pass over dy and y (pp_bn_lrelu_bwd_eval)
-            y = y_rec
-            plan.K.pp_bn_lrelu_bwd_eval(dy.ptr, dy.ld, y.ptr, y.ld, scale, L.bn.weight.data_ptr(), L.bn.bias.data_ptr(), dz, C,
-                                     gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C, ppg * groups, SLOPE,
-                                     plan.ws.data_ptr(), plan.ws_bytes, am, st)
-        elif training and self.comm is not None and self.sync_bn:
-            loc, glob = plan.bn_sums[L.name][1], plan.bn_sums[L.name][2]
-            plan.K.pp_bn_lrelu_bwd_sums(dy.ptr, dy.ld, zptr, zld, scale, shift, mean, invstd, C, ppg, groups, SLOPE,
-                                     loc.data_ptr(), plan.ws.data_ptr(), plan.ws_bytes, st)
-            glob.copy_(loc)
-            self.comm.allreduce_sums(glob)
-            plan.K.pp_bn_lrelu_bwd_apply(dy.ptr, dy.ld, zptr, zld, scale, shift, mean, invstd, L.bn.weight.data_ptr(), 1,
-                                      loc.data_ptr(), glob.data_ptr(), ppg * self.world, dz, C, gg.data_ptr(),
-                                      gbeta.data_ptr(), gb.data_ptr(), 0, C, ppg, groups, SLOPE, plan.ws.data_ptr(),
-                                      plan.ws_bytes, am, st)
-        elif am is not None:
-            plan.K.pp_bn_lrelu_bwd_amax(dy.ptr, dy.ld, zptr, zld, scale, shift, mean, invstd, L.bn.weight.data_ptr(),
-                                     1 if training else 0, dz, C, gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C, ppg,
-                                     groups, SLOPE, plan.ws.data_ptr(), plan.ws_bytes, am, st)
-        else:
-            plan.K.pp_bn_lrelu_bwd(dy.ptr, dy.ld, zptr, zld, scale, shift, mean, invstd, L.bn.weight.data_ptr(),
-                                1 if training else 0, dz, C, gg.data_ptr(), gbeta.data_ptr(), gb.data_ptr(), 0, C, ppg,
-                                groups, SLOPE, plan.ws.data_ptr(), plan.ws_bytes, st)
-        if L.stride == 2:
-            # gradients of the stride-2 convolution = those of the stride-1 convolution for dz scattered to the even pixels
-            dzf = plan.dzfull[L.name]
-            plan.K.pp_stride2_scatter(dz, C, dzf.data_ptr(), C, C, x.N, x.H // 2, x.W // 2, st)
-            dz = dzf.data_ptr()
+        # (stride 2: the gradients are those of the stride-1 convolution for dz scattered to the even pixels; dz is that buffer then)
+        dz = nop.bwd(dy, y, lazy_out, groups, pg, (plan.s1b if slot else plan.s1).data_ptr(), pool, training, eval_fused, sync,
+                     self.comm, self.world, ws, st)
 
         # Order on two streams: the weight gradient starts WITH the data gradient.  (Round 5 measured the alternative -- the weight
         # gradient enqueued behind the data gradient, so that it runs beside the HBM-bound BatchNorm backward of the next layer
         # instead of beside another matrix kernel: 31.9 -> 32.9 ms, the BatchNorm family 7.5 -> 9.7 ms.  The direct weight
         # gradients read 2 - 2.5 GB per launch themselves; profiles/r05_experiments/wgrad_behind_dgrad.log.)
-        ws = (plan.ws.data_ptr(), plan.ws_bytes)
         if side is None:
             op.bwd_weight(dz, x, gw.data_ptr(), ws, xlz, st)
         else:       # on the second stream, with its own workspace: it waits for everything the main stream has enqueued so far
@@ -1021,11 +892,7 @@ class StepEngine:
             return frozenset()
         key = tuple((L.bn.weight.data_ptr(), L.bn.running_mean.data_ptr(), plan.coef[L.name].data_ptr()) for L in layers)
         if getattr(plan, 'coef_batch_key', None) != key:
-            items = []
-            for L in layers:
-                coef, bn = plan.coef[L.name], L.bn
-                items.append(PpBnCoefItem(L.cout, coef.shape[1], bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                                          bn.running_var.data_ptr(), *(coef[i].data_ptr() for i in range(4))))
+            items = [PpBnCoefItem(L.cout, plan.coef[L.name].shape[1], *plan.norm[L.name].params(), *plan.norm[L.name].rows) for L in layers]
             plan.coef_batch = ((PpBnCoefItem * len(items))(*items), len(items), frozenset(L.name for L in layers))
             plan.coef_batch_key = key
         arr, n, names = plan.coef_batch
@@ -1142,7 +1009,7 @@ class StepEngine:
         encs = self.backbone.enc_blocks()
         # the pooled-tensor gradient of stage k + 1, when it is folded into this stage's BatchNorm backward instead of being
         # added to the skip-gradient buffer by pp_maxpool2_bwd (not under synchronised BatchNorm: its split calls have no such form)
-        fuse_pool = FUSE_POOL_BWD and not (training and self.comm is not None and self.sync_bn)
+        fuse_pool = FUSE_POOL_BWD and not self._sync(training)
         pool_grad = None
         for k in range(6, frozen, -1):
             e = encs[k - 1]
@@ -1405,7 +1272,7 @@ class StepEngine:
         # joined behind the segmentation losses: ~0.4 ms of small, latency-bound launches beside the decoder's forward pass.
         # Own workspace and statistics rows (plan.res); same kernels on the same data: bit-identical to the in-line order.
         side = self._side_stream(plan) if (AUX_SIDE and do_aux and need_grad and plan.bn_stats_side is not None
-                                           and not (self.comm is not None and self.sync_bn)) else None
+                                           and not self._sync(True)) else None
         if do_aux:
             A['logits_aux'] = torch.empty((B, K, H, W), device=dev, dtype=torch.float32)
 

@@ -45,16 +45,19 @@ class ConvOp:
     """One conv layer of one plan, bound to its kernel family.  K: the plan's entry-point table; wf / wb: packed forward / data-
     gradient weights (wb None: no data gradient, the first layer); vkeep: transformed input kept for the Winograd weight gradient
     (None in forward-only plans); amax: max |dz| of the step for the split-fp16 gradient kernels (None where nothing reads it).
+    woff / boff: byte offsets added to the addresses of the layer's weight / bias wherever they are read -- 0: the live parameters;
+    a teacher plan: the distance from the parameter slab to the optimizer's shadow slab (forward-only: the gradient calls ignore them).
     `ws` arguments are (pointer, bytes) of the workspace of the stream `st`."""
-    __slots__ = ('sel', 'conv', 'cin', 'cin_pad', 'cout', 'dil', 'K', 'slope', 'wf', 'wb', 'vkeep', 'amax')
+    __slots__ = ('sel', 'conv', 'cin', 'cin_pad', 'cout', 'dil', 'K', 'slope', 'wf', 'wb', 'vkeep', 'amax', 'woff', 'boff')
 
-    def __init__(self, sel: ConvSel, L, K, slope, wf, wb, vkeep, amax):
+    def __init__(self, sel: ConvSel, L, K, slope, wf, wb, vkeep, amax, woff=0, boff=0):
         self.sel, self.conv, self.K, self.slope = sel, L.conv, K, slope
+        self.woff, self.boff = woff, boff
         self.cin, self.cin_pad, self.cout, self.dil = L.cin, L.cin_pad, L.cout, L.dil
         self.wf, self.wb, self.vkeep, self.amax = wf, wb, vkeep, amax
 
     def _pack_args(self):
-        return (self.conv.weight.data_ptr(), self.cout, self.cin, self.sel.tile if self.sel.kind == 'wino' else self.cin_pad,
+        return (self.conv.weight.data_ptr() + self.woff, self.cout, self.cin, self.sel.tile if self.sel.kind == 'wino' else self.cin_pad,
                 self.wf.data_ptr(), self.wb.data_ptr() if self.wb is not None else None)
 
     def pack_item(self):
@@ -74,7 +77,7 @@ class ConvOp:
         fn(*self._pack_args(), st)
 
     def _fwd_args(self, x, out_ptr, ld_out):
-        return (x.ptr, x.ld, x.C, self.wf.data_ptr(), self.conv.bias.data_ptr(), out_ptr, ld_out, self.cout,
+        return (x.ptr, x.ld, x.C, self.wf.data_ptr(), self.conv.bias.data_ptr() + self.boff, out_ptr, ld_out, self.cout,
                 x.N, x.H, x.W, self.dil)
 
     def fwd(self, x, out_ptr, ld_out, ws, st):

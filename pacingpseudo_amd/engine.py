@@ -185,11 +185,18 @@ class _Layer:
 class _Plan:
     """All HBM buffers for one (batch per group, H, W, groups) shape."""
 
-    def __init__(self, eng: 'StepEngine', B: int, H: int, W: int, G: int, trainable: bool = True, storage: str = 'fp32'):
+    def __init__(self, eng: 'StepEngine', B: int, H: int, W: int, G: int, trainable: bool = True, storage: str = 'fp32',
+                 teacher=None):
         # trainable = False: a forward-only ("light") plan for no-grad calls -- validation / inference at native slice
         # sizes creates one plan per shape, and those need no gradient buffers, kept Winograd inputs or scratch slabs
+        # teacher = callable(parameter) -> byte offset: a forward-only plan of the BACKBONE whose ops read every parameter at
+        # `address + offset` -- the optimizer's shadow slab (--cr_teacher ema).  Owned by the training plan it serves
+        # (_Plan.teacher_plan), never in StepEngine.plans; no auxiliary path, no loss buffers of its own.
         self.B, self.H, self.W, self.G = B, H, W, G
         self.trainable = trainable
+        self.teacher = teacher
+        self.teacher_plan = None                      # (a training plan: its teacher plan, StepEngine._teacher_plan_for)
+        off = teacher if teacher is not None else (lambda p: 0)
         # 16-bit storage (BASELINE config 5): every NHWC activation / activation-gradient buffer of this plan is fp16 and the
         # launches go to the _h16 entry points (include/pacingpseudo_hip_h16.h); weights, logits, statistics, parameter
         # gradients and workspaces stay fp32.  The loss gradients are multiplied by a static power-of-two scale so that the
@@ -305,7 +312,7 @@ class _Plan:
                 wb = torch.empty((L.cin, 9, L.cout), **f32) if L.cin_pad == L.cin else None
             if trainable and (sel.kind == 'f16x3' or sel.split):
                 amax = torch.zeros(1, **f32)                    # max |dz| of the step, written by the BN backward
-            self.conv[L.name] = ConvOp(sel, L, self.K, SLOPE, wf, wb, vkeep, amax)
+            self.conv[L.name] = ConvOp(sel, L, self.K, SLOPE, wf, wb, vkeep, amax, off(L.conv.weight), off(L.conv.bias))
             max_elems = max(max_elems, n * h * w * max(L.cout, L.cin_pad))
 
         self.bn_stats_bytes = 0
@@ -327,7 +334,7 @@ class _Plan:
             dzfull = act(n, 2 * h, 2 * w, L.cout)[0] if (s == 2 and trainable) else None
             conv_bufs(L, n, s * h, s * w)
             self.norm[L.name] = NormOp(self.K, L, SLOPE, BN_EPS, BN_MOM, coef, self.zbuf.get(L.name), self.lazy_out[L.name], sums,
-                                       zfull, dzfull, self.conv[L.name].amax)
+                                       zfull, dzfull, self.conv[L.name].amax, off(L.bn.weight), off(L.bn.bias))
 
         cur = self.x0
         for k, e in enumerate(encs, start=1):
@@ -386,7 +393,7 @@ class _Plan:
             # the reference fails in torch.cat here (aux_path_memory.py:49) -- but only when the path is used
             self.aux_error = ('Sizes of tensors must match except in dimension 1: the auxiliary path concatenates '
                               f'stages {eng.aux.feat_stage} of different spatial size')
-        if eng.aux is not None and self.aux_error is None:
+        if eng.aux is not None and self.aux_error is None and teacher is None:
             ax = eng.aux
             ha, wa = sorted(hs)[0]
             LA = eng.aux_layer
@@ -479,16 +486,26 @@ class _Plan:
         # exists, else at [6:8], and the auxiliary pair behind it; [0:reg_end] is what a step without the auxiliary path reduces.
         # The Mumford-Shah loss (--do_loss_ms) likewise: its pair (pp_ms_loss_fwd: energy, denominator) directly behind the NC pair when
         # that exists, else behind the CRF pair, else at [6:8]; the auxiliary pair follows last.
+        # --cr_teacher ema: the six sums of the teacher's pp_seg_losses_fwd call (student-strong against teacher-weak) sit BEHIND
+        # the auxiliary pair in the same allocation -- all_sums keeps its length, and a data-parallel step with the teacher on
+        # reduces sums_store whole, still one collective.
         self.crf = self.nc = self.ms = None
-        self.all_sums = torch.zeros(8 + 2 * sum(x is not None for x in (eng.crf, eng.nc, eng.ms)), device=dev, dtype=torch.float64)
+        n_sums = 8 + 2 * sum(x is not None for x in (eng.crf, eng.nc, eng.ms))
+        self.sums_store = torch.zeros(n_sums + 6, device=dev, dtype=torch.float64)
+        self.all_sums = self.sums_store[:n_sums]
+        self.sums_teacher = self.sums_store[n_sums:]
+        # parameters the forward reads outside the ConvOp / NormOp objects: the 1x1 head, the transposed convolutions
+        fc = net.final_conv
+        self.head_off = (off(fc.weight), off(fc.bias))
+        self.up_off = {k: off(d.up_samp.weight) for k, d in decs.items() if d.trans}
         self.reg_end = 6
-        if eng.crf is not None:
+        if eng.crf is not None and teacher is None:
             check_crf_params(K=net.num_classes, C=net.input_ch, **eng.crf)
             nws = lib.pp_crf_loss_workspace(B, H, W)
             self.crf = dict(sums=self.all_sums[6:8], ws=torch.empty(nws, device=dev, dtype=torch.uint8), ws_bytes=nws,
                             unit=torch.empty((B, net.num_classes, H, W), **f32) if trainable else None)
             self.reg_end = 8
-        if eng.nc is not None:
+        if eng.nc is not None and teacher is None:
             check_nc_params(K=net.num_classes, C=net.input_ch, **eng.nc)
             nws = lib.pp_nc_loss_workspace(B, net.num_classes, H, W)
             s0 = self.reg_end
@@ -497,7 +514,7 @@ class _Plan:
                            ws_bytes=nws, assoc_vol=torch.zeros((B, net.num_classes, 2), device=dev, dtype=torch.float64),
                            unit=torch.empty((B, net.num_classes, H, W), **f32) if trainable else None)
             self.reg_end = s0 + 2
-        if eng.ms is not None:
+        if eng.ms is not None and teacher is None:
             check_ms_params(K=net.num_classes, C=net.input_ch, **eng.ms)
             nws = lib.pp_ms_loss_workspace(B, net.num_classes, net.input_ch, H, W)
             s0 = self.reg_end
@@ -633,6 +650,10 @@ class StepEngine:
         self._coefs_ready = frozenset()  # layers whose eval-mode coefficient rows the running forward has written in one batch
         self._bwd_plan = None            # plan of the backward pass in flight
         self._frozen = 0                 # frozen encoder stages of the forward in flight (backbone.frozen_stages, checked per forward)
+        # --cr_teacher ema (ConsistencyRegulr.attach_teacher): {id(FlatSlab): (FlatSlab, shadow slab)} -- the weak view's prediction
+        # of the consistency term comes from a forward-only pass that reads the optimizer's EMA shadow.  None: the step as it was.
+        self.teacher = None
+        self.teacher_resync = None       # callable: shadow := parameters wherever the optimizer has not averaged yet (invalidate_packed)
         # 16-bit storage of activations / activation gradients for TRAINING plans (`--storage fp16`, BASELINE config 5; PP_ACT_H16=1
         # forces it for A/B runs).  Forward-only plans (validation, inference at native slice sizes) stay fp32.
         # --do_loss_crf: the gated-CRF regulariser on the weak logits; its parameters are constants of the run (checked here, before
@@ -724,6 +745,70 @@ class StepEngine:
         inference.load_backbone is covered too).  tests/test_gpu_round5.py: a ``.data`` write + this call re-packs."""
         for p in self.plans.values():
             p.packed_key = None
+        if self.teacher_resync is not None:      # weights written in place behind the shadow's creation (--init_from, load_state_dict)
+            self.teacher_resync()
+
+    # ------------------------------------------------------------------ the EMA teacher of the consistency term
+    def set_teacher(self, slabs, resync=None) -> None:
+        """slabs: {id(FlatSlab): (FlatSlab, shadow slab of its parameters)} or None (off).  Existing teacher plans are dropped
+        with their key (teacher_key), so a captured step is captured again."""
+        self.teacher = dict(slabs) if slabs else None
+        self.teacher_resync = resync if self.teacher is not None else None
+        for p in self.plans.values():
+            p.teacher_plan = None
+
+    def teacher_key(self):
+        """What a teacher plan bakes in: which slabs, where their shadows live (part of GraphedStep's capture key)."""
+        if self.teacher is None:
+            return None
+        return tuple((i, f.params.data_ptr(), e.data_ptr()) for i, (f, e) in sorted(self.teacher.items()))
+
+    def _teacher_offset(self, p) -> int:
+        """Bytes from parameter `p` to its averaged copy.  A parameter outside every slab the optimizer updates (a frozen encoder
+        stage: released from the slab, never averaged) reads as its live value: offset 0."""
+        flat = getattr(p, '_pp_flat', None)
+        if flat is None:
+            return 0
+        ent = self.teacher.get(id(flat))
+        if ent is None or not flat.owns(p):
+            raise RuntimeError('the EMA teacher was attached to another parameter slab (the model was re-flattened: .cuda() / '
+                               'freeze_encoder after attach_teacher); call attach_teacher(optimizer) again')
+        return ent[1].data_ptr() - flat.params.data_ptr()
+
+    def _teacher_plan_for(self, plan: _Plan) -> _Plan:
+        """The teacher plan of training plan `plan`: B images, one statistics group, fp32, forward-only.  It is an attribute of
+        the training plan -- not an entry of self.plans -- so it lives exactly as long as the plan whose captured graph holds its
+        buffers, the LRU of validation plans cannot evict it and no forward-only plan of the same shape (live weights) is mistaken
+        for it."""
+        key = self.teacher_key()
+        tp = plan.teacher_plan
+        if tp is None or tp.teacher_key != key:
+            tp = _Plan(self, plan.B, plan.H, plan.W, 1, False, 'fp32', teacher=self._teacher_offset)
+            tp.teacher_key = key
+            dev = self.device
+            # what the training plan's loss calls need beside it: the gradient wrt the teacher logits (written, never read) and
+            # the zero upstream gradient of the teacher call's partial-CE slot
+            tp.dlogits_discard = torch.empty((plan.B, self.backbone.num_classes, plan.H, plan.W), device=dev, dtype=torch.float32)
+            tp.zero = torch.zeros(1, device=dev, dtype=torch.float32)
+            plan.teacher_plan = tp
+        return tp
+
+    def _teacher_forward(self, plan: _Plan, image, st) -> torch.Tensor:
+        """Logits (B,K,H,W) of the backbone under the averaged weights for the weak images, on the main stream: eval-mode
+        BatchNorm from the model's live running statistics, nothing recorded for a backward pass, no parameter or buffer written.
+        The packs are rebuilt in every step (no packed_key shortcut: a host decision a hipGraph replay would skip)."""
+        tp = self._teacher_plan_for(plan)
+        B, Cin, H, W = image.shape
+        tp.begin_forward((False, False, self._frozen))
+        rec, self._rec = self._rec, None
+        try:
+            self._pack_weights(tp, st, need_grad=True)
+            tp.K.pp_pack_image_nchw_to_nhwc(image.data_ptr(), B, Cin, H, W, tp.x0.ptr, tp.x0.ld, tp.x0.C, st)
+            logits = torch.empty((B, self.backbone.num_classes, H, W), device=image.device, dtype=torch.float32)
+            self._unet_forward(tp, False, st, logits)
+        finally:
+            self._rec = rec
+        return logits
 
     def _pack_weights(self, plan: _Plan, st, need_grad: bool = True):
         """Kernel-side weight layouts of every layer (split-fp16 operands, Winograd-domain U).  Forward operands on the main
@@ -739,7 +824,7 @@ class StepEngine:
         if PACK_BATCH:
             # one launch per family for all layers (the per-layer launches are 5 - 50 us each behind one another at the start of every
             # step); the item tables are rebuilt when a weight or a packed buffer moved
-            bkey = tuple(L.conv.weight.data_ptr() for L in layers)
+            bkey = tuple(L.conv.weight.data_ptr() + plan.conv[L.name].woff for L in layers)
             if getattr(plan, 'pack_batch_key', None) != bkey:
                 direct, wino, single = [], [], []
                 for L in layers:
@@ -890,7 +975,7 @@ class StepEngine:
         layers = [L for L in self.layers if L.stride == 1 and not L.gn]
         if not layers:                  # a GroupNorm backbone: no BatchNorm coefficient rows to write
             return frozenset()
-        key = tuple((L.bn.weight.data_ptr(), L.bn.running_mean.data_ptr(), plan.coef[L.name].data_ptr()) for L in layers)
+        key = tuple((L.bn.weight.data_ptr() + plan.norm[L.name].goff, L.bn.running_mean.data_ptr(), plan.coef[L.name].data_ptr()) for L in layers)
         if getattr(plan, 'coef_batch_key', None) != key:
             items = [PpBnCoefItem(L.cout, plan.coef[L.name].shape[1], *plan.norm[L.name].params(), *plan.norm[L.name].rows) for L in layers]
             plan.coef_batch = ((PpBnCoefItem * len(items))(*items), len(items), frozenset(L.name for L in layers))
@@ -933,7 +1018,7 @@ class StepEngine:
                 src = plan.low_src[k]
                 dst = _sub(cat, 0, d.up_ch)
                 if d.trans:                   # nn.ConvTranspose2d(lower, skip, k, k, bias=False), unet.py:140,149
-                    plan.K.pp_convtranspose_fwd(src.ptr, src.ld, src.C, d.up_samp.weight.data_ptr(), dst.ptr, dst.ld, d.up_ch,
+                    plan.K.pp_convtranspose_fwd(src.ptr, src.ld, src.C, d.up_samp.weight.data_ptr() + plan.up_off[k], dst.ptr, dst.ld, d.up_ch,
                                              d.scale, src.N, src.H, src.W, st)
                 else:
                     assert not src.lazy
@@ -943,12 +1028,13 @@ class StepEngine:
             self._convbn_fwd(plan, L2, plan.mid[L1.name], plan.dec_out[k], G, training, st)
         d1 = plan.dec_out[1]
         fc = net.final_conv
+        fcw, fcb = fc.weight.data_ptr() + plan.head_off[0], fc.bias.data_ptr() + plan.head_off[1]
         lz = d1.lazy_arg()
         if lz is not None:
-            plan.K.pp_conv1x1_nhwc_to_nchw_fwd_lazy(d1.ptr, d1.ld, d1.C, fc.weight.data_ptr(), fc.bias.data_ptr(),
+            plan.K.pp_conv1x1_nhwc_to_nchw_fwd_lazy(d1.ptr, d1.ld, d1.C, fcw, fcb,
                                                  logits.data_ptr(), net.num_classes, d1.N, d1.H * d1.W, ctypes.byref(lz), st)
         else:
-            plan.K.pp_conv1x1_nhwc_to_nchw_fwd(d1.ptr, d1.ld, d1.C, fc.weight.data_ptr(), fc.bias.data_ptr(),
+            plan.K.pp_conv1x1_nhwc_to_nchw_fwd(d1.ptr, d1.ld, d1.C, fcw, fcb,
                                             logits.data_ptr(), net.num_classes, d1.N, d1.H * d1.W, st)
 
     def _unet_backward_decoder(self, plan: _Plan, training, grads, st, need_g6: bool = True):
@@ -1208,6 +1294,14 @@ class StepEngine:
         bn_training = self.backbone.training
         dev = image.device
 
+        # --cr_teacher ema: the weak view's side of the consistency term is the averaged weights' prediction.  Its pass runs in
+        # FRONT of the student's, so the per-layer records the student's forward leaves (L.x / L.y, the coefficient rows in flight)
+        # are those of the student, as without a teacher.
+        do_teacher = bool(do_cr and self.teacher is not None)
+        logits_t = None
+        if do_teacher:
+            with prof_range('forward: teacher (EMA weights, weak view)'):
+                logits_t = self._teacher_forward(plan, image, st)
         plan.begin_forward((bool(bn_training), bool(self.aux.training) if self.aux is not None else False, self._frozen))
         self._rec = {} if need_grad else None
         with prof_range('pack weights + images'):
@@ -1295,9 +1389,20 @@ class StepEngine:
             valid_mask = self._check_input(valid_mask, 'valid_mask')
         mask_ptr = valid_mask.data_ptr() if (valid_mask is not None and (do_ent or do_cr)) else None
         zs = logits[B:] if do_cr else None
-        plan.K.pp_seg_losses_fwd(logits.data_ptr(), zs.data_ptr() if do_cr else None, plan.target.data_ptr(), mask_ptr,
-                              B, K, H * W, args.ignored_index, int(do_ent), variant, plan.sums.data_ptr(),
-                              plan.ws.data_ptr(), plan.ws_bytes, st)
+        if do_teacher:
+            # two calls of the same kernels, each sum with one writer: the student's weak logits give partial CE and entropy
+            # (variant 0: the strong logits are not read), the teacher's logits against the student's strong logits give the
+            # consistency sums (slots [4:6] of sums_teacher; its partial-CE slots are computed and ignored)
+            plan.K.pp_seg_losses_fwd(logits.data_ptr(), None, plan.target.data_ptr(), mask_ptr,
+                                  B, K, H * W, args.ignored_index, int(do_ent), 0, plan.sums.data_ptr(),
+                                  plan.ws.data_ptr(), plan.ws_bytes, st)
+            plan.K.pp_seg_losses_fwd(logits_t.data_ptr(), zs.data_ptr(), plan.target.data_ptr(), mask_ptr,
+                                  B, K, H * W, args.ignored_index, 0, variant, plan.sums_teacher.data_ptr(),
+                                  plan.ws.data_ptr(), plan.ws_bytes, st)
+        else:
+            plan.K.pp_seg_losses_fwd(logits.data_ptr(), zs.data_ptr() if do_cr else None, plan.target.data_ptr(), mask_ptr,
+                                  B, K, H * W, args.ignored_index, int(do_ent), variant, plan.sums.data_ptr(),
+                                  plan.ws.data_ptr(), plan.ws_bytes, st)
         do_crf_loss = bool(train and plan.crf is not None)
         crf_mask = valid_mask if do_crf_loss else None      # the mask applies whenever the batch has one, entropy / consistency on or off
         if do_crf_loss:
@@ -1325,14 +1430,18 @@ class StepEngine:
                 aux_forward(st)
             ax, a = self.aux, plan.aux
             drop, feat, wfc, logits_aux = A['drop'], A['feat'], A['wfc'], A['logits_aux']
-        if self.comm is not None:
+        if self.comm is not None and do_teacher:
+            self.comm.allreduce_sums(plan.sums_store)      # every pair of the step and the teacher call's six sums: one collective
+        elif self.comm is not None:
             self.comm.allreduce_sums(plan.all_sums if do_aux else (plan.all_sums[:plan.reg_end] if (do_crf_loss or do_nc_loss or do_ms_loss) else plan.sums))
         out = {}
         loss_pce = torch.empty((), device=dev, dtype=torch.float32)
         loss_ent = torch.empty((), device=dev, dtype=torch.float32) if do_ent else None
         loss_cr = torch.empty((), device=dev, dtype=torch.float32) if do_cr else None
         plan.K.pp_losses_finalize(plan.sums.data_ptr(), 1 if mask_ptr else 0, loss_pce.data_ptr(),
-                               loss_ent.data_ptr() if do_ent else None, loss_cr.data_ptr() if do_cr else None, st)
+                               loss_ent.data_ptr() if do_ent else None, loss_cr.data_ptr() if (do_cr and not do_teacher) else None, st)
+        if do_teacher:
+            plan.K.pp_losses_finalize(plan.sums_teacher.data_ptr(), 1 if mask_ptr else 0, None, None, loss_cr.data_ptr(), st)
         out['segmentation/logits'] = logits[:B]
         out['loss_pce'] = loss_pce
         if do_ent:
@@ -1340,6 +1449,8 @@ class StepEngine:
         if do_cr:
             out['loss_cr'] = loss_cr
             out['segmentation/logits_strong'] = logits[B:]
+            if do_teacher:
+                out['segmentation/logits_teacher'] = logits_t
         if do_crf_loss:
             # numerator / max(denominator, 1e-8): the masked-ratio slot of pp_losses_finalize reads sums[2] / sums[3]
             loss_crf = torch.empty((), device=dev, dtype=torch.float32)
@@ -1385,6 +1496,8 @@ class StepEngine:
                 self.last.update(do_nc=True)
             if do_ms_loss:
                 self.last.update(do_ms=True, ms_mask=valid_mask is not None)
+            if do_teacher:
+                self.last.update(teacher=plan.teacher_plan, logits_teacher=logits_t)
         return out
 
     def _aux_input(self, plan, aux_group, st) -> View:
@@ -1469,10 +1582,24 @@ class StepEngine:
         B, H, W, K = S['B'], S['H'], S['W'], S['K']
         logits = S['logits']
         with prof_range('backward: losses'):
-            plan.K.pp_seg_losses_bwd(logits.data_ptr(), zs_ptr, plan.target.data_ptr(), mask.data_ptr() if mask is not None else None,
-                                  B, K, H * W, args.ignored_index, int(S['do_ent']), S['variant'],
-                                  1 if getattr(args, 'detach_weak_cr', False) else 0, plan.sums.data_ptr(),
-                                  gp('loss_pce'), gp('loss_ent'), gp('loss_cr'), plan.loss_scale, plan.dlogits.data_ptr(), dzs_ptr, st)
+            tp = S.get('teacher')
+            mptr = mask.data_ptr() if mask is not None else None
+            if tp is not None:
+                # the student call (variant 0) writes dlogits[:B] and leaves the strong half alone: both kernels store dzs under
+                # `if (variant)` only (pp_loss.hip, seg_losses_bwd_kernel / seg_losses_bwd_v4_kernel).  The teacher call -- upstream
+                # partial-CE gradient a device zero, no entropy, weak side detached -- writes the strong half, and its gradient wrt
+                # the teacher logits into a buffer nobody reads.
+                plan.K.pp_seg_losses_bwd(logits.data_ptr(), None, plan.target.data_ptr(), mptr, B, K, H * W, args.ignored_index,
+                                      int(S['do_ent']), 0, 1, plan.sums.data_ptr(), gp('loss_pce'), gp('loss_ent'), None,
+                                      plan.loss_scale, plan.dlogits.data_ptr(), None, st)
+                plan.K.pp_seg_losses_bwd(S['logits_teacher'].data_ptr(), zs_ptr, plan.target.data_ptr(), mptr, B, K, H * W,
+                                      args.ignored_index, 0, S['variant'], 1, plan.sums_teacher.data_ptr(), tp.zero.data_ptr(), None,
+                                      gp('loss_cr'), plan.loss_scale, tp.dlogits_discard.data_ptr(), dzs_ptr, st)
+            else:
+                plan.K.pp_seg_losses_bwd(logits.data_ptr(), zs_ptr, plan.target.data_ptr(), mptr,
+                                      B, K, H * W, args.ignored_index, int(S['do_ent']), S['variant'],
+                                      1 if getattr(args, 'detach_weak_cr', False) else 0, plan.sums.data_ptr(),
+                                      gp('loss_pce'), gp('loss_ent'), gp('loss_cr'), plan.loss_scale, plan.dlogits.data_ptr(), dzs_ptr, st)
             if S.get('do_crf') and gp('loss_crf') is not None:
                 # streaming add of the unit gradient the forward left, behind the kernel that WRITES dlogits[:B]
                 plan.K.pp_crf_loss_bwd(plan.crf['unit'].data_ptr(), plan.crf['sums'].data_ptr(), 1 if S['crf_mask'] is not None else 0,

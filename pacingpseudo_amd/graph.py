@@ -61,7 +61,10 @@ class GraphedStep:
                 # device objects baked into a capture: the engine's training plans (their buffers), the learning-rate
                 # scalars and the parameter slab -- a rebuilt plan, a re-created scalar or a re-flattened model captures again
                 tuple(id(p) for p in eng.plans.values() if p.trainable), self.opt.hyper_ptrs() if hasattr(self.opt, 'hyper_ptrs') else (),
-                id(getattr(m, 'flat', None)))
+                id(getattr(m, 'flat', None)),
+                # --cr_teacher ema: teacher on / off, the shadow slab's address, and the teacher plans whose buffers a capture bakes in
+                eng.teacher_key() if hasattr(eng, 'teacher_key') else None,
+                tuple(id(p.teacher_plan) for p in eng.plans.values() if p.trainable and p.teacher_plan is not None))
 
     def _capture(self, batch, epoch, key):
         comm = self.model.engine.comm

@@ -182,6 +182,60 @@ def hard_label_cross_entropy_loss(input, target, valid_mask=None):
     return _consistency(input, target.detach() if torch.is_tensor(target) else target, valid_mask, 'hard_ce_loss', True)
 
 
+class _TeacherLoss(torch.autograd.Function):
+    """The consistency term of a mean-teacher step, as StepEngine runs it (--cr_teacher ema): the TEACHER call of the two-call
+    composition -- pp_seg_losses_fwd(teacher, student, ..., do_ent 0, variant) for the sums, pp_seg_losses_bwd with the partial-CE
+    slot's upstream gradient a device zero, no entropy and the weak side detached for the gradient wrt the student logits; the
+    gradient wrt the teacher logits lands in a buffer that is dropped."""
+
+    @staticmethod
+    def forward(ctx, zs, zt, mask, variant):
+        N, K, H, W = zs.shape
+        st = stream_ptr()
+        dev = zs.device
+        sums = torch.zeros(6, device=dev, dtype=torch.float64)
+        nws = lib.pp_seg_losses_workspace(N, H * W)
+        ws = torch.empty(nws + 64, device=dev, dtype=torch.uint8)
+        target = torch.full((N, H, W), -100, device=dev, dtype=torch.int64)
+        lib.pp_seg_losses_fwd(zt.data_ptr(), zs.data_ptr(), target.data_ptr(), mask.data_ptr() if mask is not None else None,
+                              N, K, H * W, -100, 0, variant, sums.data_ptr(), ws.data_ptr(), nws, st)
+        out = torch.empty((), device=dev, dtype=torch.float32)
+        lib.pp_losses_finalize(sums.data_ptr(), 1 if mask is not None else 0, None, None, out.data_ptr(), st)
+        ctx.save_for_backward(zs, zt, target, mask if mask is not None else zs, sums)
+        ctx.cfg = (mask is not None, variant)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        zs, zt, target, mask, sums = ctx.saved_tensors
+        has_m, variant = ctx.cfg
+        N, K, H, W = zs.shape
+        g = g.to(torch.float32).contiguous()
+        zero = torch.zeros(1, device=zs.device, dtype=torch.float32)
+        dzs, discard = torch.empty_like(zs), torch.empty_like(zt)
+        lib.pp_seg_losses_bwd(zt.data_ptr(), zs.data_ptr(), target.data_ptr(), mask.data_ptr() if has_m else None, N, K, H * W,
+                              -100, 0, variant, 1, sums.data_ptr(), zero.data_ptr(), None, g.data_ptr(), 1.0, discard.data_ptr(),
+                              dzs.data_ptr(), stream_ptr())
+        return dzs, None, None, None
+
+
+def teacher_consistency_loss(student_logits, teacher_logits, variant='ce_loss', valid_mask=None):
+    """Consistency of a student's (strong-view) logits with a teacher's (weak-view) logits, the teacher a constant (mean teacher):
+    the form `variant` of --loss_cr_variants with softmax(teacher_logits) -- hard_ce_loss: its arg-max -- as the target, masked
+    mean.  Returns the 0-dim loss; differentiable in `student_logits` only (the teacher's ``.grad`` stays None)."""
+    zs, zt = _check(student_logits, 'student_logits'), _check(teacher_logits, 'teacher_logits')
+    if variant not in _VARIANT:
+        raise ValueError(f'variant must be one of {sorted(_VARIANT)}, got {variant!r}')
+    if zs.shape != zt.shape:
+        raise ValueError(f'student_logits {tuple(zs.shape)} and teacher_logits {tuple(zt.shape)} must have the same shape')
+    m = None
+    if valid_mask is not None:
+        m = _check(valid_mask, 'valid_mask')
+        if tuple(m.shape) != (zs.shape[0], 1) + tuple(zs.shape[2:]):
+            raise ValueError(f'valid_mask must be {(zs.shape[0], 1) + tuple(zs.shape[2:])}, got {tuple(m.shape)}')
+    return _TeacherLoss.apply(zs, zt.detach(), m, _VARIANT[variant])
+
+
 class _DiceLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, label):

@@ -89,6 +89,27 @@ class ConsistencyRegulr(nn.Module):
         self.engine.invalidate_packed()
         return self
 
+    # ---- mean teacher --------------------------------------------------------------------------
+    def attach_teacher(self, optimizer):
+        """``--cr_teacher ema``: from now on the consistency term pulls the student's strong-view prediction towards what the
+        optimizer's EMA weights predict for the weak view (mean teacher); no gradient reaches the teacher, and ``--detach_weak_cr``
+        has nothing left to do.  The optimizer creates its shadow slab now (not at its first step) and the engine reads every
+        teacher parameter at ``live address + (shadow - parameter slab)``; parameters outside the slab (frozen encoder stages)
+        read as their live values.  Training-mode outputs gain ``segmentation/logits_teacher``.  ``attach_teacher(None)`` detaches.
+        Call it again after anything that re-flattens the model (``.cuda()``, ``freeze_encoder``)."""
+        if optimizer is None:
+            self.engine.set_teacher(None)
+            return self
+        if not getattr(self.args, 'do_decoder_consistency', False):
+            raise ValueError('the EMA teacher is the weak side of the consistency term: it needs --do_decoder_consistency')
+        if not self.backbone.final_conv.weight.is_cuda:
+            raise RuntimeError('attach_teacher: call model.cuda() first')
+        flat = self._ensure_flat()
+        shadow = optimizer.ema_shadow(flat)          # ValueError when ema_decay is off
+        optimizer.ema_resync(flat)
+        self.engine.set_teacher({id(flat): (flat, shadow)}, resync=lambda: optimizer.ema_resync(flat))
+        return self
+
     def _flatten(self):
         segs = [('backbone', [p for p in self.backbone.parameters() if p.requires_grad]),
                 ('aux_path', [p for p in self.aux_path.parameters() if p.requires_grad])]
@@ -123,6 +144,8 @@ class ConsistencyRegulr(nn.Module):
                 keys.append('loss_ent')
             if a.do_decoder_consistency:
                 keys += ['loss_cr', 'segmentation/logits_strong']
+                if getattr(getattr(self, 'engine', None), 'teacher', None) is not None:
+                    keys.append('segmentation/logits_teacher')
             if getattr(a, 'do_loss_crf', False):
                 keys.append('loss_crf')
             if getattr(a, 'do_loss_nc', False):

@@ -12,11 +12,14 @@ class NormOp:
     """One layer's normalisation in one plan.  coef: its rows [mean, invstd, scale, shift] per statistics group (GroupNorm: per
     image, + xbar); z: the layer's own buffer for the pre-norm convolution output or None; lazy: the output stays lazy in train-
     mode BatchNorm; sums: per-channel sums of the split (synchronised) BatchNorm calls, [0] forward, [1] backward local, [2]
-    backward global; zfull / dzfull: full-resolution z and zero-stuffed dz of a stride-2 layer; amax: the ConvOp's max |dz| cell."""
-    __slots__ = ('K', 'C', 'gn', 'bn', 'slope', 'eps', 'mom', 'rows', 'xbar', 'z', 'lazy', 'sums', 'zfull', 'dzfull', 'am')
+    backward global; zfull / dzfull: full-resolution z and zero-stuffed dz of a stride-2 layer; amax: the ConvOp's max |dz| cell.
+    goff / boff: byte offsets added to the addresses of gamma / beta in the FORWARD calls -- 0: the live parameters; a teacher plan:
+    the distance to the optimizer's shadow slab.  Running statistics are always the module's own."""
+    __slots__ = ('K', 'C', 'gn', 'bn', 'slope', 'eps', 'mom', 'rows', 'xbar', 'z', 'lazy', 'sums', 'zfull', 'dzfull', 'am', 'goff', 'boff')
 
-    def __init__(self, K, L, slope, eps, mom, coef, z, lazy, sums, zfull, dzfull, amax):
+    def __init__(self, K, L, slope, eps, mom, coef, z, lazy, sums, zfull, dzfull, amax, goff=0, boff=0):
         self.K, self.C, self.gn, self.bn, self.slope = K, L.cout, L.gn, L.bn, slope
+        self.goff, self.boff = goff, boff
         self.eps, self.mom = float(L.bn.eps) if L.gn else eps, mom
         self.rows = tuple(coef[i].data_ptr() for i in range(4))     # mean, invstd, scale, shift
         self.xbar = coef[4].data_ptr() if L.gn else None
@@ -30,7 +33,7 @@ class NormOp:
 
     def params(self):
         bn = self.bn
-        return bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+        return bn.weight.data_ptr() + self.goff, bn.bias.data_ptr() + self.boff, bn.running_mean.data_ptr(), bn.running_var.data_ptr()
 
     def eval_coeffs(self, groups, st):
         self.K.pp_bn_eval_coeffs(self.C, groups, self.eps, *self.params(), *self.rows, st)
@@ -47,7 +50,7 @@ class NormOp:
         n = ppg = (y.N // groups) * y.H * y.W
         if self.gn:                     # the same in train and eval mode: one coefficient row per image
             groups, ppg, gn = y.N, y.H * y.W, self.bn
-            K.pp_gn_stats(zptr, zld, C, ppg, groups, gn.num_groups, self.eps, gn.weight.data_ptr(), gn.bias.data_ptr(),
+            K.pp_gn_stats(zptr, zld, C, ppg, groups, gn.num_groups, self.eps, gn.weight.data_ptr() + self.goff, gn.bias.data_ptr() + self.boff,
                           mean, invstd, self.xbar, scale, shift, *ws, st)
         else:
             if sync:

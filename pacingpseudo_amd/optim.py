@@ -314,6 +314,52 @@ class _SlabOptimizer(torch.optim.Optimizer):
         vals = [int(steps.get(name, 0)) for name in state['names']]
         state['steps_dev'].copy_(torch.tensor(vals, dtype=torch.int32))
 
+    def _state_for(self, flat) -> dict:
+        """The optimiser state of one parameter slab, created on first use: zero moments and step counts -- or what
+        load_state_dict left pending -- and, with ``ema_decay``, the shadow slab."""
+        state = self._slabs.get(id(flat))
+        if state is None:
+            state = {k: torch.zeros_like(flat.params) for k in self.STATE_KEYS}
+            state['names'] = list(flat.segments)
+            state['steps_dev'] = torch.zeros(len(state['names']), device=flat.params.device, dtype=torch.int32)
+            state['flat'] = flat
+            if self._pending is not None:
+                for k in self.STATE_KEYS:
+                    state[k].copy_(self._pending[k].to(flat.params.device))
+                self._set_steps(state, self._pending['steps'])
+            if self._ema_on():
+                self._ema_slab(state, None if self._pending is None else self._pending.get('ema'))
+            self._pending = None
+            self._slabs[id(flat)] = state
+        return state
+
+    def ema_shadow(self, flat) -> torch.Tensor:
+        """The shadow slab of `flat`, created NOW if no step has run yet (a mean-teacher forward reads it before the first
+        update: ConsistencyRegulr.attach_teacher).  Same layout as ``flat.params``; allocated once."""
+        if not self._ema_on():
+            raise ValueError('ema_shadow(): ema_decay is off (the EMA teacher needs --ema_decay > 0)')
+        if not any(p in flat.offsets for g in self.param_groups for p in g['params']):
+            raise ValueError('ema_shadow(): this optimizer updates no parameter of that slab')
+        if self._slabs and id(flat) not in self._slabs:
+            raise RuntimeError('the model was re-flattened after the first optimiser step: the optimiser state belongs to the '
+                               'old parameter slab; rebuild the optimiser')
+        return self._ema_slab(self._state_for(flat))
+
+    def ema_resync(self, flat) -> None:
+        """shadow := parameters on every segment of `flat` the optimizer has not updated yet (step count 0: the average has not
+        started there, and ``ema_weights()`` would not swap it in either).  For weights written in place after the shadow was
+        created -- ``load_state_dict``, ``--init_from`` -- so that a reader of the shadow sees them.  Reads the step counts on
+        the host: not for the training loop."""
+        state = self._slabs.get(id(flat))
+        if state is None or 'ema' not in state or getattr(self, '_ema_swapped', False):
+            return
+        done = self._steps_host(state)
+        with torch.no_grad():
+            for name in state['names']:
+                if name not in done:
+                    a, b = flat.segments[name]
+                    state['ema'][a:b].copy_(flat.params[a:b])
+
     def _segments_with_grads(self, group):
         todo = {}
         for p in group['params']:
@@ -329,20 +375,7 @@ class _SlabOptimizer(torch.optim.Optimizer):
                 raise RuntimeError('the model was re-flattened (.cuda()/.to() after the first optimiser step): the '
                                    'optimiser state belongs to the old parameter slab; rebuild the optimiser or carry '
                                    'the state over with state_dict() / load_state_dict()')
-            state = self._slabs.get(id(flat))
-            if state is None:
-                state = {k: torch.zeros_like(flat.params) for k in self.STATE_KEYS}
-                state['names'] = list(flat.segments)
-                state['steps_dev'] = torch.zeros(len(state['names']), device=flat.params.device, dtype=torch.int32)
-                state['flat'] = flat
-                if self._pending is not None:
-                    for k in self.STATE_KEYS:
-                        state[k].copy_(self._pending[k].to(flat.params.device))
-                    self._set_steps(state, self._pending['steps'])
-                if self._ema_on():
-                    self._ema_slab(state, None if self._pending is None else self._pending.get('ema'))
-                self._pending = None
-                self._slabs[id(flat)] = state
+            state = self._state_for(flat)
             active = []
             for i, (name, (a, b)) in enumerate(flat.segments.items()):
                 ps = flat.seg_params[name]

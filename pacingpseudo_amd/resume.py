@@ -34,7 +34,7 @@ MAY_DIFFER = frozenset({'gpu', 'num_workers', 'graph_step', 'resume', 'state_int
                         'ema_val_interval', 'init_from', 'init_reset_head'})
 # flags that are younger than the state-file format, with their parser defaults: a state file written before the flag existed
 # lacks the key, and the run it describes computed what the default computes
-ABSENT_DEFAULTS = {'clip_grad_norm': 0.0, 'ema_decay': 0.0, 'ema_val_interval': 1,
+ABSENT_DEFAULTS = {'clip_grad_norm': 0.0, 'ema_decay': 0.0, 'ema_val_interval': 1, 'cr_teacher': 'none',
                    'do_loss_crf': False, 'loss_crf_weight': 0.1, 'ramp_up_loss_crf': False, 'crf_radius': 5, 'crf_dilation': 1,
                    'crf_sigma_xy': 6.0, 'crf_sigma_rgb': 0.1,
                    'do_loss_nc': False, 'loss_nc_weight': 0.1, 'ramp_up_loss_nc': False, 'nc_radius': 5, 'nc_dilation': 1,

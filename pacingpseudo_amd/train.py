@@ -178,6 +178,12 @@ parser.add_argument('--loss_ms_weight', type=float, default=0.1, help='its weigh
 parser.add_argument('--ramp_up_loss_ms', action='store_true', help='Gaussian ramp-up of that weight over the epochs (--ramp_up_scale)')
 parser.add_argument('--ms_tv_weight', type=float, default=1.0,
                     help='weight of the total-variation term inside that loss, >= 0 (an untuned first value)')
+# mean teacher: the weak side of the consistency term from the EMA weights (engine.py: a forward-only pass reading the optimizer's
+# shadow slab); the reference has no such option
+parser.add_argument('--cr_teacher', type=str, default='none', choices=['none', 'ema'],
+                    help='ema: the consistency loss pulls the strong-view prediction towards the prediction of the EMA weights for the '
+                         'weak view (mean teacher; needs --do_decoder_consistency and --ema_decay > 0; the teacher gets no gradient, '
+                         'so --detach_weak_cr has nothing to do); none: towards the weak-view prediction of the same weights')
 add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
 add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
@@ -234,6 +240,11 @@ def parse_args(argv=None):
         check_ms_params(args.ms_tv_weight)
     except (ValueError, NotImplementedError) as e:
         parser.error(f'--ms_tv_weight: {e}')
+    if args.cr_teacher == 'ema':
+        if not args.do_decoder_consistency:
+            parser.error('--cr_teacher ema: the teacher is the weak side of the consistency term; add --do_decoder_consistency')
+        if not args.ema_decay > 0.0:
+            parser.error('--cr_teacher ema: the teacher is the EMA of the weights; set --ema_decay D with 0 < D < 1')
     return args
 
 
@@ -280,6 +291,8 @@ def train_interface(args, resume_state=None):
                              max_grad_norm=args.clip_grad_norm or None, ema_decay=args.ema_decay or None)
     else:
         raise ValueError('Unimplemented optimizer')
+    if args.cr_teacher == 'ema':                  # the shadow slab exists from here on (resume.restore then loads the saved one)
+        model.attach_teacher(optimizer)
 
     args.gpu_augment = not args.cpu_input          # the reference's recipe is the default; --cpu_input opts out
     if args.augmentations != 'TransformsColor' and not args.gpu_augment:

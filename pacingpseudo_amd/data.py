@@ -110,7 +110,13 @@ class NpzSlices(Dataset):
     def __len__(self):
         return len(self.files)
 
+    # --rw_scribbles (utils/random_walker.expand_dataset): a per-index list of uint8 (h, w) maps that stand in for the slice's `scb`
+    # in every kind of item, raw or not; None = the scribbles as read
+    scribble_override = None
+
     def _sample(self, img, lab, scb):
+        if self.scribble_override is not None:
+            scb = self.scribble_override[self._index]
         if self.raw:
             return {'img': img.astype(np.float32), 'lab': lab.astype(np.int32), 'scb': scb.astype(np.int32)}
         img = img.astype(np.float32)
@@ -144,10 +150,14 @@ class NpzSlices(Dataset):
     # candidate partner slice, drawn here, which the device pipeline uses when its own draw lets Mixup fire for the sample
     mix_partner = False
 
+    def raw_arrays(self, i):
+        """(img, lab, scb) of slice i as stored, before normalisation, cropping and any override."""
+        z = np.load(self.files[i])
+        return z['img'], z['lab'], z['scb']
+
     def __getitem__(self, i):
         self._index = int(i)
-        z = np.load(self.files[i])
-        d = self._sample(z['img'], z['lab'], z['scb'])
+        d = self._sample(*self.raw_arrays(i))
         if self.raw and self.mix_partner:
             rng = np.random.default_rng([self.seed, self.epoch, self._index, 77])
             d['mix'] = np.load(self.files[int(rng.integers(len(self.files)))])['img'].astype(np.float32)
@@ -248,8 +258,7 @@ class SyntheticPhantoms(NpzSlices):
         super().__init__([None] * n, num_classes, size, do_strong, strength, train, seed, raw, native, compact)
         self.base_seed = seed + (0 if train else 10_000)
 
-    def __getitem__(self, i):
-        self._index = int(i)
+    def raw_arrays(self, i):
         rng = np.random.default_rng(self.base_seed * 100_003 + i)
         S, K = self.size, self.K
         yy, xx = np.mgrid[0:S, 0:S].astype(np.float32)
@@ -272,4 +281,8 @@ class SyntheticPhantoms(NpzSlices):
                 x = min(S - 1, x0 + t)
                 if lab[y0, x] == c:
                     scb[y0, x] = c
-        return self._sample(img, lab, scb)
+        return img, lab, scb
+
+    def __getitem__(self, i):
+        self._index = int(i)
+        return self._sample(*self.raw_arrays(i))

@@ -40,7 +40,8 @@ ABSENT_DEFAULTS = {'clip_grad_norm': 0.0, 'ema_decay': 0.0, 'ema_val_interval': 
                    'do_loss_nc': False, 'loss_nc_weight': 0.1, 'ramp_up_loss_nc': False, 'nc_radius': 5, 'nc_dilation': 1,
                    'nc_sigma_xy': 6.0, 'nc_sigma_rgb': 0.1,
                    'do_loss_ms': False, 'loss_ms_weight': 0.1, 'ramp_up_loss_ms': False, 'ms_tv_weight': 1.0,
-                   'freeze_encoder': 0, 'init_from': None, 'init_reset_head': False}
+                   'freeze_encoder': 0, 'init_from': None, 'init_reset_head': False,
+                   'rw_scribbles': False, 'rw_beta': 13.0, 'rw_threshold': 0.9, 'rw_eps': 1e-4, 'rw_tol': 1e-6, 'rw_max_iters': 10000}
 # attributes the drivers add to the namespace after parsing (not flags)
 _DERIVED = frozenset({'child', 'train_ls', 'val_ls'})
 

@@ -31,6 +31,7 @@ import torch
 from . import finetune, resume
 from .losses.losses import check_crf_params, check_ms_params, check_nc_params
 from .optim import add_clip_flag, add_ema_flags, log_clip_stats, positive_float, positive_int
+from .utils.random_walker import add_rw_flags, check_rw_params
 
 parser = argparse.ArgumentParser(description='PacingPseudo training on MI355X (flag surface of the reference driver)')
 
@@ -188,6 +189,9 @@ add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo
 add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
 finetune.add_flags(parser)                    # --freeze_encoder N / --init_from PATH / --init_reset_head (pacingpseudo_amd/finetune.py)
+# random-walker expansion of the training scribbles, once before the first step (libpacingpseudo_prep.so); the
+# reference has no such stage.  It acts on the labels, not on a loss: everything downstream sees an ordinary scribble map
+add_rw_flags(parser)                          # --rw_scribbles / --rw_beta / --rw_threshold / --rw_eps / --rw_tol / --rw_max_iters
 
 
 # The reference ships ONE driver (train_chaos.py) and three dataset packages that differ only in class tables and
@@ -240,6 +244,10 @@ def parse_args(argv=None):
         check_ms_params(args.ms_tv_weight)
     except (ValueError, NotImplementedError) as e:
         parser.error(f'--ms_tv_weight: {e}')
+    try:
+        check_rw_params(args.rw_beta, args.rw_eps, args.rw_tol, args.rw_max_iters, args.rw_threshold)
+    except (ValueError, NotImplementedError) as e:
+        parser.error(f'--rw_beta / --rw_eps / --rw_tol / --rw_max_iters / --rw_threshold: {e}')
     if args.cr_teacher == 'ema':
         if not args.do_decoder_consistency:
             parser.error('--cr_teacher ema: the teacher is the weak side of the consistency term; add --do_decoder_consistency')
@@ -318,6 +326,20 @@ def train_interface(args, resume_state=None):
         val_dataset = dataset_class(args.dataset)(args.val_ls, train=False, native=True, compact=True, **ds_kw)
         # Mixup blends with a slice drawn from the whole training list (datasets/augmentations.py:66): the loader draws it
         train_dataset.mix_partner = bool(args.gpu_augment and args.augmentations == 'TransformsColorMixup')
+    rw_summary = None
+    if getattr(args, 'rw_scribbles', False):
+        # every training slice once, before any loader worker exists; every rank computes the full list (the same bits on each),
+        # a resumed run recomputes it.  Validation data are not touched.
+        from .utils.random_walker import expand_dataset, summarize, summary_line
+        prm = check_rw_params(args.rw_beta, args.rw_eps, args.rw_tol, args.rw_max_iters, args.rw_threshold, K=args.num_classes)
+        train_dataset.scribble_override, rw_report = expand_dataset(train_dataset, args.num_classes, device, prm)
+        rw_summary = summarize(rw_report)
+        if rank == 0:
+            logging.info(summary_line(rw_summary))
+            if rw_summary['unconverged']:
+                logging.warning('random-walker scribbles: %d systems stopped at --rw_max_iters %d before --rw_tol %g, first slices: %s',
+                                rw_summary['unconverged'], prm['max_iters'], prm['tol'], rw_summary['unconverged_slices'][:8])
+            np.savez(os.path.join(args.child, 'rw_scribbles.npz'), **rw_report, **{'param_' + k: v for k, v in prm.items()})
     sampler = torch.utils.data.distributed.DistributedSampler(train_dataset, world, rank, shuffle=True,
                                                               seed=args.seed, drop_last=True) if world > 1 else None
     train_loader = torch.utils.data.DataLoader(train_dataset, batch_size=args.batch_size, shuffle=sampler is None,
@@ -337,6 +359,9 @@ def train_interface(args, resume_state=None):
                                              multiprocessing_context=loader_context(args.num_workers))
     names = _class_names(args.num_classes, args.dataset)
     scalars = ScalarLog(os.path.join(args.child, 'tb_summary', 'scalars.jsonl')) if rank == 0 else None
+    if scalars is not None and rw_summary is not None and resume_state is None:      # a resumed run keeps the first run's two lines
+        scalars.add('RW/coverage', rw_summary['coverage_after'], 0)
+        scalars.add('RW/agreement', rw_summary['agreement'], 0)
     valdice = np.zeros(args.epoch)
     # --ema_decay: the same bookkeeping a second time for the averaged weights (epochs without an EMA validation pass stay 0)
     ema_on = bool(args.ema_decay)

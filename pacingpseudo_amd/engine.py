@@ -31,7 +31,8 @@ import torch.nn as nn
 from ._lib import PpBnCoefItem, PpLazyIn, PpPackItem, PpWinoPackItem, lib, lib_for, prof_range, stream_ptr
 from .convop import ConvOp, select as conv_select
 from .normop import NormOp
-from .losses.losses import _VARIANT, check_crf_params, check_ms_params, check_nc_params
+from .regop import REGULARISERS, RegOp, active_regularisers
+from .losses.losses import _VARIANT
 
 WINO_ENABLED = os.environ.get('PP_WINO', '1') != '0'      # A/B switch for the Winograd path
 # split-fp16 ("f16x3") direct convolution for the non-Winograd layers with at least this many output channels
@@ -480,17 +481,12 @@ class _Plan:
                 self.aux_fork, self.aux_join = torch.cuda.Event(), torch.cuda.Event()
         # loss denominators / numerators, packed so that data-parallel runs all-reduce them ONCE per step:
         # [0:6] segmentation losses (pp_seg_losses_fwd), [6:8] auxiliary partial CE (pp_aux_pce_fwd)
-        # With the gated-CRF loss (--do_loss_crf) its two sums sit between them, [6:8] (pp_crf_loss_fwd), and the auxiliary pair at
-        # [8:10]: a step without the auxiliary path still reduces one contiguous block.  Its buffers exist in such plans only.
-        # The normalised-cut loss (--do_loss_nc) likewise: its pair (pp_nc_loss_fwd: sum NC, N K) directly behind the CRF pair when that
-        # exists, else at [6:8], and the auxiliary pair behind it; [0:reg_end] is what a step without the auxiliary path reduces.
-        # The Mumford-Shah loss (--do_loss_ms) likewise: its pair (pp_ms_loss_fwd: energy, denominator) directly behind the NC pair when
-        # that exists, else behind the CRF pair, else at [6:8]; the auxiliary pair follows last.
+        # The pairs of the regularisers that are on (regop.REGULARISERS, in its order) sit between them from [6:8] on, the auxiliary
+        # pair last: a step without the auxiliary path still reduces one contiguous block, [0:6 + 2 * len(regs)].
         # --cr_teacher ema: the six sums of the teacher's pp_seg_losses_fwd call (student-strong against teacher-weak) sit BEHIND
         # the auxiliary pair in the same allocation -- all_sums keeps its length, and a data-parallel step with the teacher on
         # reduces sums_store whole, still one collective.
-        self.crf = self.nc = self.ms = None
-        n_sums = 8 + 2 * sum(x is not None for x in (eng.crf, eng.nc, eng.ms))
+        n_sums = 8 + 2 * len(eng.regs)
         self.sums_store = torch.zeros(n_sums + 6, device=dev, dtype=torch.float64)
         self.all_sums = self.sums_store[:n_sums]
         self.sums_teacher = self.sums_store[n_sums:]
@@ -498,33 +494,16 @@ class _Plan:
         fc = net.final_conv
         self.head_off = (off(fc.weight), off(fc.bias))
         self.up_off = {k: off(d.up_samp.weight) for k, d in decs.items() if d.trans}
-        self.reg_end = 6
-        if eng.crf is not None and teacher is None:
-            check_crf_params(K=net.num_classes, C=net.input_ch, **eng.crf)
-            nws = lib.pp_crf_loss_workspace(B, H, W)
-            self.crf = dict(sums=self.all_sums[6:8], ws=torch.empty(nws, device=dev, dtype=torch.uint8), ws_bytes=nws,
-                            unit=torch.empty((B, net.num_classes, H, W), **f32) if trainable else None)
-            self.reg_end = 8
-        if eng.nc is not None and teacher is None:
-            check_nc_params(K=net.num_classes, C=net.input_ch, **eng.nc)
-            nws = lib.pp_nc_loss_workspace(B, net.num_classes, H, W)
-            s0 = self.reg_end
-            # fin: where pp_losses_finalize's ratio slot (sums[2] / sums[3]) finds the pair
-            self.nc = dict(sums=self.all_sums[s0:s0 + 2], fin=self.all_sums[s0 - 2:], ws=torch.empty(nws, device=dev, dtype=torch.uint8),
-                           ws_bytes=nws, assoc_vol=torch.zeros((B, net.num_classes, 2), device=dev, dtype=torch.float64),
-                           unit=torch.empty((B, net.num_classes, H, W), **f32) if trainable else None)
-            self.reg_end = s0 + 2
-        if eng.ms is not None and teacher is None:
-            check_ms_params(K=net.num_classes, C=net.input_ch, **eng.ms)
-            nws = lib.pp_ms_loss_workspace(B, net.num_classes, net.input_ch, H, W)
-            s0 = self.reg_end
-            self.ms = dict(sums=self.all_sums[s0:s0 + 2], fin=self.all_sums[s0 - 2:], ws=torch.empty(nws, device=dev, dtype=torch.uint8),
-                           ws_bytes=nws, stats=torch.zeros((B, net.num_classes, 1 + net.input_ch), device=dev, dtype=torch.float64),
-                           unit=torch.empty((B, net.num_classes, H, W), **f32) if trainable else None)
-            self.reg_end = s0 + 2
+        self.regs = {}                   # {name: RegOp}; a teacher plan evaluates no loss
+        for i, (name, prm) in enumerate(eng.regs.items() if teacher is None else ()):
+            REGULARISERS[name].check(K=net.num_classes, C=net.input_ch, **prm)
+            s0 = 6 + 2 * i
+            self.regs[name] = RegOp.alloc(self.K, REGULARISERS[name], prm, self.all_sums[s0:s0 + 2], self.all_sums[s0 - 2:], B,
+                                          net.num_classes, net.input_ch, H, W, trainable)
         self.sums = self.all_sums[:6]
         if self.aux is not None:
-            self.aux['sums'] = self.all_sums[self.reg_end:self.reg_end + 2]
+            s0 = 6 + 2 * len(self.regs)
+            self.aux['sums'] = self.all_sums[s0:s0 + 2]
         self.target = torch.empty((B, H, W), device=dev, dtype=torch.int64)
 
     def ws_args(self):
@@ -656,23 +635,9 @@ class StepEngine:
         self.teacher_resync = None       # callable: shadow := parameters wherever the optimizer has not averaged yet (invalidate_packed)
         # 16-bit storage of activations / activation gradients for TRAINING plans (`--storage fp16`, BASELINE config 5; PP_ACT_H16=1
         # forces it for A/B runs).  Forward-only plans (validation, inference at native slice sizes) stay fp32.
-        # --do_loss_crf: the gated-CRF regulariser on the weak logits; its parameters are constants of the run (checked here, before
-        # any launch).  None: no launch, no buffer, no output key.
-        self.crf = None
-        if getattr(args, 'do_loss_crf', False):
-            self.crf = check_crf_params(radius=getattr(args, 'crf_radius', 5), dilation=getattr(args, 'crf_dilation', 1),
-                                        sigma_xy=getattr(args, 'crf_sigma_xy', 6.0), sigma_rgb=getattr(args, 'crf_sigma_rgb', 0.1),
-                                        K=backbone.num_classes)
-        # --do_loss_nc: the normalised cut on the weak logits, handled as the CRF loss is
-        self.nc = None
-        if getattr(args, 'do_loss_nc', False):
-            self.nc = check_nc_params(radius=getattr(args, 'nc_radius', 5), dilation=getattr(args, 'nc_dilation', 1),
-                                      sigma_xy=getattr(args, 'nc_sigma_xy', 6.0), sigma_rgb=getattr(args, 'nc_sigma_rgb', 0.1),
-                                      K=backbone.num_classes)
-        # --do_loss_ms: the Mumford-Shah level-set loss on the weak logits, handled as the CRF loss is
-        self.ms = None
-        if getattr(args, 'do_loss_ms', False):
-            self.ms = check_ms_params(tv_weight=getattr(args, 'ms_tv_weight', 1.0), K=backbone.num_classes)
+        # the regularisers on the weak logits that are switched on: {name: parameters}, constants of the run (checked here, before
+        # any launch).  Absent: no launch, no buffer, no output key.
+        self.regs = {r.name: r.check(K=backbone.num_classes, **r.args_params(args)) for r in active_regularisers(args)}
         self.storage = getattr(args, 'storage', 'fp32') or 'fp32'
         if os.environ.get('PP_ACT_H16', '0') == '1' and self.storage == 'fp32':
             self.storage = 'fp16'
@@ -1403,26 +1368,10 @@ class StepEngine:
             plan.K.pp_seg_losses_fwd(logits.data_ptr(), zs.data_ptr() if do_cr else None, plan.target.data_ptr(), mask_ptr,
                                   B, K, H * W, args.ignored_index, int(do_ent), variant, plan.sums.data_ptr(),
                                   plan.ws.data_ptr(), plan.ws_bytes, st)
-        do_crf_loss = bool(train and plan.crf is not None)
-        crf_mask = valid_mask if do_crf_loss else None      # the mask applies whenever the batch has one, entropy / consistency on or off
-        if do_crf_loss:
-            c = self.crf
-            plan.K.pp_crf_loss_fwd(logits.data_ptr(), image.data_ptr(), crf_mask.data_ptr() if crf_mask is not None else None,
-                                   B, K, Cin, H, W, c['radius'], c['dilation'], c['sigma_xy'], c['sigma_rgb'],
-                                   plan.crf['unit'].data_ptr() if need_grad else None, plan.crf['sums'].data_ptr(),
-                                   plan.crf['ws'].data_ptr(), plan.crf['ws_bytes'], st)
-        do_nc_loss = bool(train and plan.nc is not None)
-        if do_nc_loss:
-            c = self.nc
-            plan.K.pp_nc_loss_fwd(logits.data_ptr(), image.data_ptr(), valid_mask.data_ptr() if valid_mask is not None else None,
-                                  B, K, Cin, H, W, c['radius'], c['dilation'], c['sigma_xy'], c['sigma_rgb'],
-                                  plan.nc['unit'].data_ptr() if need_grad else None, plan.nc['assoc_vol'].data_ptr(),
-                                  plan.nc['sums'].data_ptr(), plan.nc['ws'].data_ptr(), plan.nc['ws_bytes'], st)
-        do_ms_loss = bool(train and plan.ms is not None)
-        if do_ms_loss:                                      # (the mask as for the CRF loss: whenever the batch has one)
-            plan.K.pp_ms_loss_fwd(logits.data_ptr(), image.data_ptr(), valid_mask.data_ptr() if valid_mask is not None else None,
-                                  B, K, Cin, H, W, self.ms['tv_weight'], plan.ms['unit'].data_ptr() if need_grad else None,
-                                  plan.ms['stats'].data_ptr(), plan.ms['sums'].data_ptr(), plan.ms['ws'].data_ptr(), plan.ms['ws_bytes'], st)
+        regs = plan.regs if train else {}
+        reg_mptr = valid_mask.data_ptr() if valid_mask is not None else None      # whenever the batch has one, entropy / consistency on or off
+        for op in regs.values():
+            op.fwd(logits.data_ptr(), image.data_ptr(), reg_mptr, B, K, Cin, H, W, need_grad, st)
         if do_aux:
             if side is not None:
                 torch.cuda.current_stream().wait_event(plan.aux_join)
@@ -1433,7 +1382,7 @@ class StepEngine:
         if self.comm is not None and do_teacher:
             self.comm.allreduce_sums(plan.sums_store)      # every pair of the step and the teacher call's six sums: one collective
         elif self.comm is not None:
-            self.comm.allreduce_sums(plan.all_sums if do_aux else (plan.all_sums[:plan.reg_end] if (do_crf_loss or do_nc_loss or do_ms_loss) else plan.sums))
+            self.comm.allreduce_sums(plan.all_sums if do_aux else (plan.all_sums[:6 + 2 * len(regs)] if regs else plan.sums))
         out = {}
         loss_pce = torch.empty((), device=dev, dtype=torch.float32)
         loss_ent = torch.empty((), device=dev, dtype=torch.float32) if do_ent else None
@@ -1451,21 +1400,9 @@ class StepEngine:
             out['segmentation/logits_strong'] = logits[B:]
             if do_teacher:
                 out['segmentation/logits_teacher'] = logits_t
-        if do_crf_loss:
-            # numerator / max(denominator, 1e-8): the masked-ratio slot of pp_losses_finalize reads sums[2] / sums[3]
-            loss_crf = torch.empty((), device=dev, dtype=torch.float32)
-            plan.K.pp_losses_finalize(plan.all_sums[4:].data_ptr(), 1 if crf_mask is not None else 0, None, loss_crf.data_ptr(), None, st)
-            out['loss_crf'] = loss_crf
-        if do_nc_loss:
-            # sum NC / (N K) over the ranks: the unmasked ratio slot (the count is never 0)
-            loss_nc = torch.empty((), device=dev, dtype=torch.float32)
-            plan.K.pp_losses_finalize(plan.nc['fin'].data_ptr(), 0, None, loss_nc.data_ptr(), None, st)
-            out['loss_nc'] = loss_nc
-        if do_ms_loss:
-            # energy / D over the ranks: the masked-ratio slot, D = max(sum m, 1e-8) with a mask
-            loss_ms = torch.empty((), device=dev, dtype=torch.float32)
-            plan.K.pp_losses_finalize(plan.ms['fin'].data_ptr(), 1 if valid_mask is not None else 0, None, loss_ms.data_ptr(), None, st)
-            out['loss_ms'] = loss_ms
+        for op in regs.values():     # the ratio of each pair, summed over the ranks by now
+            out[op.reg.key] = torch.empty((), device=dev, dtype=torch.float32)
+            op.finalize(out[op.reg.key].data_ptr(), reg_mptr is not None, st)
 
         if do_aux:
             loss_aux = torch.empty((), device=dev, dtype=torch.float32)
@@ -1489,13 +1426,7 @@ class StepEngine:
                              do_ent=do_ent, do_cr=do_cr, do_aux=do_aux, do_mem=do_mem, variant=variant,
                              bn_training=bn_training, aux_training=self.aux.training if self.aux is not None else False,
                              aux_group=aux_group, logits_aux=out.get('logits_aux_cls'), frozen=self._frozen,
-                             drop=self.last_drop_masks if do_aux else None)
-            if do_crf_loss:
-                self.last.update(do_crf=True, crf_mask=crf_mask)
-            if do_nc_loss:
-                self.last.update(do_nc=True)
-            if do_ms_loss:
-                self.last.update(do_ms=True, ms_mask=valid_mask is not None)
+                             drop=self.last_drop_masks if do_aux else None, regs=tuple(regs), reg_mask=reg_mptr is not None)
             if do_teacher:
                 self.last.update(teacher=plan.teacher_plan, logits_teacher=logits_t)
         return out
@@ -1600,16 +1531,10 @@ class StepEngine:
                                       B, K, H * W, args.ignored_index, int(S['do_ent']), S['variant'],
                                       1 if getattr(args, 'detach_weak_cr', False) else 0, plan.sums.data_ptr(),
                                       gp('loss_pce'), gp('loss_ent'), gp('loss_cr'), plan.loss_scale, plan.dlogits.data_ptr(), dzs_ptr, st)
-            if S.get('do_crf') and gp('loss_crf') is not None:
-                # streaming add of the unit gradient the forward left, behind the kernel that WRITES dlogits[:B]
-                plan.K.pp_crf_loss_bwd(plan.crf['unit'].data_ptr(), plan.crf['sums'].data_ptr(), 1 if S['crf_mask'] is not None else 0,
-                                       gp('loss_crf'), plan.loss_scale, plan.dlogits.data_ptr(), B * K * H * W, st)
-            if S.get('do_nc') and gp('loss_nc') is not None:
-                plan.K.pp_nc_loss_bwd(plan.nc['unit'].data_ptr(), plan.nc['sums'].data_ptr(), gp('loss_nc'), plan.loss_scale,
-                                      plan.dlogits.data_ptr(), B * K * H * W, st)
-            if S.get('do_ms') and gp('loss_ms') is not None:
-                plan.K.pp_ms_loss_bwd(plan.ms['unit'].data_ptr(), plan.ms['sums'].data_ptr(), 1 if S['ms_mask'] else 0, gp('loss_ms'),
-                                      plan.loss_scale, plan.dlogits.data_ptr(), B * K * H * W, st)
+            for name in S['regs']:       # streaming adds of the unit gradients the forward left, behind the kernel that WRITES dlogits[:B]
+                op = plan.regs[name]
+                if gp(op.reg.key) is not None:
+                    op.bwd(gp(op.reg.key), S['reg_mask'], plan.loss_scale, plan.dlogits.data_ptr(), B * K * H * W, st)
         with prof_range('backward: decoder'):
             g6 = self._unet_backward_decoder(plan, S['bn_training'], grads, st, need_g6=S['frozen'] < 6)
         if S['do_aux']:

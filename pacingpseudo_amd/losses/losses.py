@@ -18,6 +18,8 @@ from __future__ import annotations
 import torch
 
 from .._lib import lib, stream_ptr
+from ..regop import (CRF_MAX_CHANNELS, CRF_MAX_CLASSES, CRF_MAX_DILATION, CRF_MAX_HALO, CRF_MAX_RADIUS, MS_MAX_CHANNELS,  # noqa: F401
+                     MS_MAX_CLASSES, REGULARISERS, RegOp, check_crf_params, check_ms_params, check_nc_params)
 
 # cr_variant codes of pp_seg_losses_fwd / _bwd (include/pacingpseudo_hip.h); engine.CR_VARIANTS is this table
 _VARIANT = {'ce_loss': 1, 'l1_loss': 2, 'l2_loss': 3, 'kl_loss': 4, 'bikl_loss': 5, 'js_loss': 6, 'hard_ce_loss': 7}
@@ -266,59 +268,43 @@ def dice_loss_fn(input, target):
     return _DiceLoss.apply(_check(input, 'input'), _check(target, 'target'))
 
 
-CRF_MAX_RADIUS, CRF_MAX_DILATION, CRF_MAX_HALO, CRF_MAX_CHANNELS, CRF_MAX_CLASSES = 8, 4, 16, 4, 32
+class _RegLoss(torch.autograd.Function):
+    """One regulariser of regop.REGULARISERS on its own: a RegOp over buffers of this call."""
 
-
-def check_crf_params(radius=5, dilation=1, sigma_xy=6.0, sigma_rgb=0.1, K=None, C=None) -> dict:
-    """The accepted ranges of the gated-CRF loss (include/pacingpseudo_hip.h: pp_crf_loss_fwd), checked before any launch:
-    ValueError for values that are no neighbourhood / no kernel width at all, NotImplementedError for sizes beyond what the
-    kernel stages in LDS.  Returns the normalised parameters."""
-    import math
-    if int(radius) != radius or int(dilation) != dilation:
-        raise ValueError(f'gated CRF: radius and dilation must be integers (got {radius!r}, {dilation!r})')
-    radius, dilation, sigma_xy, sigma_rgb = int(radius), int(dilation), float(sigma_xy), float(sigma_rgb)
-    if radius < 1 or dilation < 1:
-        raise ValueError(f'gated CRF: radius and dilation must be >= 1 (got {radius}, {dilation})')
-    for name, v in (('sigma_xy', sigma_xy), ('sigma_rgb', sigma_rgb)):
-        if not (v > 0.0 and math.isfinite(v)):
-            raise ValueError(f'gated CRF: {name} must be a positive finite number (got {v!r})')
-    if radius > CRF_MAX_RADIUS or dilation > CRF_MAX_DILATION or radius * dilation > CRF_MAX_HALO:
-        raise NotImplementedError(f'gated CRF: radius <= {CRF_MAX_RADIUS}, dilation <= {CRF_MAX_DILATION} and radius * dilation <= '
-                                  f'{CRF_MAX_HALO} (got {radius}, {dilation})')
-    if K is not None and not 1 <= K <= CRF_MAX_CLASSES:
-        raise NotImplementedError(f'gated CRF: 1 .. {CRF_MAX_CLASSES} classes (got {K})')
-    if C is not None and not 1 <= C <= CRF_MAX_CHANNELS:
-        raise NotImplementedError(f'gated CRF: 1 .. {CRF_MAX_CHANNELS} image channels (got {C})')
-    return dict(radius=radius, dilation=dilation, sigma_xy=sigma_xy, sigma_rgb=sigma_rgb)
-
-
-class _CrfLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, z, image, mask, prm):
+    def forward(ctx, z, image, mask, reg, prm):
         N, K, H, W = z.shape
         st = stream_ptr()
-        dev = z.device
-        # [2:4] = numerator, denominator: where pp_losses_finalize's masked-ratio slot reads them
-        sums = torch.zeros(4, device=dev, dtype=torch.float64)
-        nws = lib.pp_crf_loss_workspace(N, H, W)
-        ws = torch.empty(nws, device=dev, dtype=torch.uint8)
-        unit = torch.empty_like(z) if ctx.needs_input_grad[0] else None
-        lib.pp_crf_loss_fwd(z.data_ptr(), image.data_ptr(), mask.data_ptr() if mask is not None else None, N, K, image.shape[1], H, W,
-                            prm['radius'], prm['dilation'], prm['sigma_xy'], prm['sigma_rgb'],
-                            unit.data_ptr() if unit is not None else None, sums[2:].data_ptr(), ws.data_ptr(), nws, st)
-        out = torch.empty((), device=dev, dtype=torch.float32)
-        lib.pp_losses_finalize(sums.data_ptr(), 1 if mask is not None else 0, None, out.data_ptr(), None, st)
-        ctx.unit, ctx.sums, ctx.has_mask = unit, sums, mask is not None
+        # [2:4] = the regulariser's pair: where pp_losses_finalize's ratio slot reads it
+        sums = torch.zeros(4, device=z.device, dtype=torch.float64)
+        op = RegOp.alloc(lib, reg, prm, sums[2:], sums, N, K, image.shape[1], H, W, ctx.needs_input_grad[0])
+        op.fwd(z.data_ptr(), image.data_ptr(), mask.data_ptr() if mask is not None else None, N, K, image.shape[1], H, W,
+               op.unit is not None, st)
+        out = torch.empty((), device=z.device, dtype=torch.float32)
+        op.finalize(out.data_ptr(), mask is not None, st)
+        ctx.op, ctx.has_mask = op, mask is not None
         return out
 
     @staticmethod
     def backward(ctx, g):
-        unit = ctx.unit
         g = g.to(torch.float32).contiguous()
-        dz = torch.zeros_like(unit)
-        lib.pp_crf_loss_bwd(unit.data_ptr(), ctx.sums[2:].data_ptr(), 1 if ctx.has_mask else 0, g.data_ptr(), 1.0, dz.data_ptr(),
-                            unit.numel(), stream_ptr())
-        return dz, None, None, None
+        dz = torch.zeros_like(ctx.op.unit)
+        ctx.op.bwd(g.data_ptr(), ctx.has_mask, 1.0, dz.data_ptr(), dz.numel(), stream_ptr())
+        return dz, None, None, None, None
+
+
+def _reg_loss(name, input, image, valid_mask, **prm):
+    z, x = _check(input, 'input'), _check(image, 'image')
+    N, K, H, W = z.shape
+    if x.shape[0] != N or tuple(x.shape[2:]) != (H, W):
+        raise ValueError(f'image must be (N,C,H,W) with the N, H, W of input {tuple(z.shape)}, got {tuple(x.shape)}')
+    m = None
+    if valid_mask is not None:
+        m = _check(valid_mask, 'valid_mask')
+        if tuple(m.shape) != (N, 1, H, W):
+            raise ValueError(f'valid_mask must be {(N, 1, H, W)}, got {tuple(m.shape)}')
+    reg = REGULARISERS[name]
+    return _RegLoss.apply(z, x, m, reg, reg.check(K=K, C=x.shape[1], **prm))
 
 
 def gated_crf_loss(input, image, valid_mask=None, radius=5, dilation=1, sigma_xy=6.0, sigma_rgb=0.1):
@@ -326,55 +312,7 @@ def gated_crf_loss(input, image, valid_mask=None, radius=5, dilation=1, sigma_xy
     (1/D) sum_i sum_j m_i m_j k_ij (1 - <p_i, p_j>) with p = softmax(input), j = i + (dy, dx) * dilation over dy, dx in
     [-radius, radius] \\ (0, 0) inside the image, k_ij = exp(-(dy^2 + dx^2) / (2 sigma_xy^2)) exp(-|x_i - x_j|^2 / (2 sigma_rgb^2))
     on the `image` channels, D = N H W or max(sum(valid_mask), 1e-8).  Differentiable in `input` only."""
-    z, x = _check(input, 'input'), _check(image, 'image')
-    N, K, H, W = z.shape
-    if x.shape[0] != N or tuple(x.shape[2:]) != (H, W):
-        raise ValueError(f'image must be (N,C,H,W) with the N, H, W of input {tuple(z.shape)}, got {tuple(x.shape)}')
-    m = None
-    if valid_mask is not None:
-        m = _check(valid_mask, 'valid_mask')
-        if tuple(m.shape) != (N, 1, H, W):
-            raise ValueError(f'valid_mask must be {(N, 1, H, W)}, got {tuple(m.shape)}')
-    prm = check_crf_params(radius, dilation, sigma_xy, sigma_rgb, K=K, C=x.shape[1])
-    return _CrfLoss.apply(z, x, m, prm)
-
-
-def check_nc_params(radius=5, dilation=1, sigma_xy=6.0, sigma_rgb=0.1, K=None, C=None) -> dict:
-    """The accepted ranges of the normalised-cut loss (include/pacingpseudo_hip.h: pp_nc_loss_fwd) -- those of check_crf_params: the
-    two losses walk the same window -- checked before any launch.  Returns the normalised parameters."""
-    try:
-        return check_crf_params(radius, dilation, sigma_xy, sigma_rgb, K=K, C=C)
-    except (ValueError, NotImplementedError) as e:
-        raise type(e)(str(e).replace('gated CRF', 'normalised cut', 1)) from None
-
-
-class _NcLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, z, image, mask, prm):
-        N, K, H, W = z.shape
-        st = stream_ptr()
-        dev = z.device
-        # [2:4] = sum NC, N K: where pp_losses_finalize's ratio slot reads them (the unmasked form: the count is never 0)
-        sums = torch.zeros(4, device=dev, dtype=torch.float64)
-        assoc_vol = torch.empty((N, K, 2), device=dev, dtype=torch.float64)
-        nws = lib.pp_nc_loss_workspace(N, K, H, W)
-        ws = torch.empty(nws, device=dev, dtype=torch.uint8)
-        unit = torch.empty_like(z) if ctx.needs_input_grad[0] else None
-        lib.pp_nc_loss_fwd(z.data_ptr(), image.data_ptr(), mask.data_ptr() if mask is not None else None, N, K, image.shape[1], H, W,
-                           prm['radius'], prm['dilation'], prm['sigma_xy'], prm['sigma_rgb'],
-                           unit.data_ptr() if unit is not None else None, assoc_vol.data_ptr(), sums[2:].data_ptr(), ws.data_ptr(), nws, st)
-        out = torch.empty((), device=dev, dtype=torch.float32)
-        lib.pp_losses_finalize(sums.data_ptr(), 0, None, out.data_ptr(), None, st)
-        ctx.unit, ctx.sums = unit, sums
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        unit = ctx.unit
-        g = g.to(torch.float32).contiguous()
-        dz = torch.zeros_like(unit)
-        lib.pp_nc_loss_bwd(unit.data_ptr(), ctx.sums[2:].data_ptr(), g.data_ptr(), 1.0, dz.data_ptr(), unit.numel(), stream_ptr())
-        return dz, None, None, None
+    return _reg_loss('crf', input, image, valid_mask, radius=radius, dilation=dilation, sigma_xy=sigma_xy, sigma_rgb=sigma_rgb)
 
 
 def normalized_cut_loss(input, image, valid_mask=None, radius=5, dilation=1, sigma_xy=6.0, sigma_rgb=0.1):
@@ -382,69 +320,7 @@ def normalized_cut_loss(input, image, valid_mask=None, radius=5, dilation=1, sig
     loss): (1/(N K)) sum_n sum_c (1 - A_nc / V_nc) with p = softmax(input), q_ic = sum_j m_j k_ij p_jc, d_i = sum_j m_j k_ij,
     A_nc = sum_i m_i p_ic q_ic, V_nc = sum_i m_i p_ic d_i; a class with V_nc <= 1e-6 in an image adds 0 and gets no gradient.
     Differentiable in `input` only."""
-    z, x = _check(input, 'input'), _check(image, 'image')
-    N, K, H, W = z.shape
-    if x.shape[0] != N or tuple(x.shape[2:]) != (H, W):
-        raise ValueError(f'image must be (N,C,H,W) with the N, H, W of input {tuple(z.shape)}, got {tuple(x.shape)}')
-    m = None
-    if valid_mask is not None:
-        m = _check(valid_mask, 'valid_mask')
-        if tuple(m.shape) != (N, 1, H, W):
-            raise ValueError(f'valid_mask must be {(N, 1, H, W)}, got {tuple(m.shape)}')
-    prm = check_nc_params(radius, dilation, sigma_xy, sigma_rgb, K=K, C=x.shape[1])
-    return _NcLoss.apply(z, x, m, prm)
-
-
-MS_MAX_CHANNELS, MS_MAX_CLASSES = 4, 32
-
-
-def check_ms_params(tv_weight=1.0, K=None, C=None) -> dict:
-    """The accepted ranges of the Mumford-Shah level-set loss (include/pacingpseudo_hip.h: pp_ms_loss_fwd), checked before any
-    launch: ValueError for a total-variation weight that is negative or not finite, NotImplementedError for more classes or image
-    channels than the kernels take.  Returns the normalised parameters."""
-    import math
-    try:
-        tv_weight = float(tv_weight)
-    except (TypeError, ValueError):
-        raise ValueError(f'Mumford-Shah: tv_weight must be a number (got {tv_weight!r})') from None
-    if not (tv_weight >= 0.0 and math.isfinite(tv_weight)):
-        raise ValueError(f'Mumford-Shah: tv_weight must be >= 0 and finite (got {tv_weight!r})')
-    if K is not None and not 1 <= K <= MS_MAX_CLASSES:
-        raise NotImplementedError(f'Mumford-Shah: 1 .. {MS_MAX_CLASSES} classes (got {K})')
-    if C is not None and not 1 <= C <= MS_MAX_CHANNELS:
-        raise NotImplementedError(f'Mumford-Shah: 1 .. {MS_MAX_CHANNELS} image channels (got {C})')
-    return dict(tv_weight=tv_weight)
-
-
-class _MsLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, z, image, mask, prm):
-        N, K, H, W = z.shape
-        C = image.shape[1]
-        st = stream_ptr()
-        dev = z.device
-        # [2:4] = energy, denominator: where pp_losses_finalize's masked-ratio slot reads them
-        sums = torch.zeros(4, device=dev, dtype=torch.float64)
-        stats = torch.empty((N, K, 1 + C), device=dev, dtype=torch.float64)
-        nws = lib.pp_ms_loss_workspace(N, K, C, H, W)
-        ws = torch.empty(nws, device=dev, dtype=torch.uint8)
-        unit = torch.empty_like(z) if ctx.needs_input_grad[0] else None
-        lib.pp_ms_loss_fwd(z.data_ptr(), image.data_ptr(), mask.data_ptr() if mask is not None else None, N, K, C, H, W,
-                           prm['tv_weight'], unit.data_ptr() if unit is not None else None, stats.data_ptr(), sums[2:].data_ptr(),
-                           ws.data_ptr(), nws, st)
-        out = torch.empty((), device=dev, dtype=torch.float32)
-        lib.pp_losses_finalize(sums.data_ptr(), 1 if mask is not None else 0, None, out.data_ptr(), None, st)
-        ctx.unit, ctx.sums, ctx.has_mask = unit, sums, mask is not None
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        unit = ctx.unit
-        g = g.to(torch.float32).contiguous()
-        dz = torch.zeros_like(unit)
-        lib.pp_ms_loss_bwd(unit.data_ptr(), ctx.sums[2:].data_ptr(), 1 if ctx.has_mask else 0, g.data_ptr(), 1.0, dz.data_ptr(),
-                           unit.numel(), stream_ptr())
-        return dz, None, None, None
+    return _reg_loss('nc', input, image, valid_mask, radius=radius, dilation=dilation, sigma_xy=sigma_xy, sigma_rgb=sigma_rgb)
 
 
 def mumford_shah_loss(input, image, valid_mask=None, tv_weight=1.0):
@@ -453,17 +329,7 @@ def mumford_shah_loss(input, image, valid_mask=None, tv_weight=1.0):
     mu_nc the m p-weighted mean of the `image` channels over image n (a class with sum_i m_i p_ic <= 1e-6 in an image adds no
     level-set term), (i, j) the vertical and horizontal neighbour pairs, D = N H W or max(sum(valid_mask), 1e-8).  Differentiable
     in `input` only."""
-    z, x = _check(input, 'input'), _check(image, 'image')
-    N, K, H, W = z.shape
-    if x.shape[0] != N or tuple(x.shape[2:]) != (H, W):
-        raise ValueError(f'image must be (N,C,H,W) with the N, H, W of input {tuple(z.shape)}, got {tuple(x.shape)}')
-    m = None
-    if valid_mask is not None:
-        m = _check(valid_mask, 'valid_mask')
-        if tuple(m.shape) != (N, 1, H, W):
-            raise ValueError(f'valid_mask must be {(N, 1, H, W)}, got {tuple(m.shape)}')
-    prm = check_ms_params(tv_weight, K=K, C=x.shape[1])
-    return _MsLoss.apply(z, x, m, prm)
+    return _reg_loss('ms', input, image, valid_mask, tv_weight=tv_weight)
 
 
 class _WeightedSum(torch.autograd.Function):

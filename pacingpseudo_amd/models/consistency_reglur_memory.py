@@ -25,8 +25,9 @@ from .unet import UNet, release_from_slab
 from .aux_path_memory import AuxPath
 from ..engine import StepEngine
 from ..flat import FlatSlab
+from ..regop import REGULARISERS, active_regularisers
 
-_LOSS_KEYS = ('loss_pce', 'loss_ent', 'loss_cr', 'loss_crf', 'loss_nc', 'loss_ms', 'loss_aux_cls', 'loss_memory')
+_LOSS_KEYS = ('loss_pce', 'loss_ent', 'loss_cr', *(r.key for r in REGULARISERS.values()), 'loss_aux_cls', 'loss_memory')
 
 
 class _StepFunction(torch.autograd.Function):
@@ -146,12 +147,7 @@ class ConsistencyRegulr(nn.Module):
                 keys += ['loss_cr', 'segmentation/logits_strong']
                 if getattr(getattr(self, 'engine', None), 'teacher', None) is not None:
                     keys.append('segmentation/logits_teacher')
-            if getattr(a, 'do_loss_crf', False):
-                keys.append('loss_crf')
-            if getattr(a, 'do_loss_nc', False):
-                keys.append('loss_nc')
-            if getattr(a, 'do_loss_ms', False):
-                keys.append('loss_ms')
+            keys += [r.key for r in active_regularisers(a)]
             if a.do_aux_path:
                 keys += ['logits_aux_cls', 'loss_aux_cls']
                 if a.do_memory:

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import finetune, resume
-from .losses.losses import check_crf_params, check_ms_params, check_nc_params
+from .regop import REGULARISERS, active_regularisers
 from .optim import add_clip_flag, add_ema_flags, log_clip_stats, positive_float, positive_int
 from .utils.random_walker import add_rw_flags, check_rw_params
 
@@ -232,18 +232,11 @@ def apply_dataset_preset(args, argv=None):
 def parse_args(argv=None):
     """parser.parse_args plus the checks that span several flags (argparse errors: exit status 2)."""
     args = parser.parse_args(argv)
-    try:
-        check_crf_params(args.crf_radius, args.crf_dilation, args.crf_sigma_xy, args.crf_sigma_rgb)
-    except (ValueError, NotImplementedError) as e:
-        parser.error(f'--crf_radius / --crf_dilation / --crf_sigma_xy / --crf_sigma_rgb: {e}')
-    try:
-        check_nc_params(args.nc_radius, args.nc_dilation, args.nc_sigma_xy, args.nc_sigma_rgb)
-    except (ValueError, NotImplementedError) as e:
-        parser.error(f'--nc_radius / --nc_dilation / --nc_sigma_xy / --nc_sigma_rgb: {e}')
-    try:
-        check_ms_params(args.ms_tv_weight)
-    except (ValueError, NotImplementedError) as e:
-        parser.error(f'--ms_tv_weight: {e}')
+    for r in REGULARISERS.values():
+        try:
+            r.check(**r.args_params(args))
+        except (ValueError, NotImplementedError) as e:
+            parser.error(' / '.join(f'--{r.name}_{p}' for p in r.params) + f': {e}')
     try:
         check_rw_params(args.rw_beta, args.rw_eps, args.rw_tol, args.rw_max_iters, args.rw_threshold)
     except (ValueError, NotImplementedError) as e:
@@ -407,9 +400,10 @@ def train_interface(args, resume_state=None):
 
         # loss meters live on the GPU: [sum pce*n, sum ent*n, sum cr*n, sum aux*n, sum mem, n, iterations]
         acc = torch.zeros(7, device=device, dtype=torch.float64)
-        acc_crf = torch.zeros(1, device=device, dtype=torch.float64) if args.do_loss_crf else None      # sum crf*n (--do_loss_crf only)
-        acc_nc = torch.zeros(1, device=device, dtype=torch.float64) if args.do_loss_nc else None        # sum nc*n (--do_loss_nc only)
-        acc_ms = torch.zeros(1, device=device, dtype=torch.float64) if args.do_loss_ms else None        # sum ms*n (--do_loss_ms only)
+        # the regularisers that are on, in the table's order, as (output key, weight of this epoch); their meters: sum loss*n each
+        regs = [(r.key, gaussian_ramp_up(t=curr_epoch, base_value=getattr(args, r.weight), scale=args.ramp_up_scale)
+                 if getattr(args, r.ramp) else getattr(args, r.weight)) for r in active_regularisers(args)]
+        acc_reg = torch.zeros(len(regs), device=device, dtype=torch.float64)
         n_img = 0
         for idx, batch in enumerate(train_loader):
             if args.max_iters and idx >= args.max_iters:
@@ -426,12 +420,6 @@ def train_interface(args, resume_state=None):
             # loss assembly of train_chaos.py:273-310; the ramp-up weights depend on the epoch only
             w_ent = gaussian_ramp_up(t=curr_epoch, base_value=args.loss_ent_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_ent else 1.0
             w_cr = gaussian_ramp_up(t=curr_epoch, base_value=args.loss_cr_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_cr else 1.0
-            w_crf = (gaussian_ramp_up(t=curr_epoch, base_value=args.loss_crf_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_crf
-                     else args.loss_crf_weight)
-            w_nc = (gaussian_ramp_up(t=curr_epoch, base_value=args.loss_nc_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_nc
-                    else args.loss_nc_weight)
-            w_ms = (gaussian_ramp_up(t=curr_epoch, base_value=args.loss_ms_weight, scale=args.ramp_up_scale) if args.ramp_up_loss_ms
-                    else args.loss_ms_weight)
 
             def assemble(out, _epoch=None):
                 # train_chaos.py:273-310: pce + ent * w_ent + cr * w_cr + aux * w_aux + memory * w_mem -- one launch each way
@@ -445,12 +433,8 @@ def train_interface(args, resume_state=None):
                     terms.append(out['loss_aux_cls']); weights.append(args.loss_aux_weight)
                     if args.do_memory:
                         terms.append(out['loss_memory']); weights.append(args.loss_memory_weight)
-                if args.do_loss_crf:
-                    terms.append(out['loss_crf']); weights.append(w_crf)
-                if args.do_loss_nc:
-                    terms.append(out['loss_nc']); weights.append(w_nc)
-                if args.do_loss_ms:
-                    terms.append(out['loss_ms']); weights.append(w_ms)
+                for key, w in regs:
+                    terms.append(out[key]); weights.append(w)
                 return weighted_loss_sum(terms, weights)
             if args.graph_step and n == args.batch_size:      # (a ragged last batch runs eagerly: another shape, another plan)
                 if graph_step is None:
@@ -473,17 +457,12 @@ def train_interface(args, resume_state=None):
                 acc[3] += net_outputs['loss_aux_cls'].detach() * (args.loss_aux_weight * n)
                 if args.do_memory:
                     acc[4] += net_outputs['loss_memory'].detach() * args.loss_memory_weight
-            if args.do_loss_crf:
-                acc_crf[0] += net_outputs['loss_crf'].detach() * (w_crf * n)
-            if args.do_loss_nc:
-                acc_nc[0] += net_outputs['loss_nc'].detach() * (w_nc * n)
-            if args.do_loss_ms:
-                acc_ms[0] += net_outputs['loss_ms'].detach() * (w_ms * n)
+            for i, (key, w) in enumerate(regs):
+                acc_reg[i] += net_outputs[key].detach() * (w * n)
             acc[5] += n
             acc[6] += 1
             n_img += n
-        extra = [t for t in (acc_crf, acc_nc, acc_ms) if t is not None]                # [7] crf when on, nc behind it, ms last
-        a = (torch.cat([acc] + extra) if extra else acc).cpu().numpy()      # the one host sync of the epoch
+        a = (torch.cat([acc, acc_reg]) if regs else acc).cpu().numpy()      # the one host sync of the epoch; [7 + i]: regs[i]
         epoch_toc = time.time()
         cnt, its = max(a[5], 1), max(a[6], 1)
         # 16-bit storage: optimizer steps the overflow guard skipped this epoch (a static loss scale that keeps
@@ -506,16 +485,10 @@ def train_interface(args, resume_state=None):
                     raise FloatingPointError('every optimizer step of the epoch was skipped even at loss scale < 1: the gradients '
                                              'themselves are not finite')
         if rank == 0:
-            crf_col = ", loss_crf: {:.6f}".format(a[7] / cnt) if args.do_loss_crf else ""
-            i_nc = 8 if args.do_loss_crf else 7
-            if args.do_loss_nc:
-                crf_col += ", loss_nc: {:.6f}".format(a[i_nc] / cnt)
-            i_ms = i_nc + (1 if args.do_loss_nc else 0)
-            if args.do_loss_ms:
-                crf_col += ", loss_ms: {:.6f}".format(a[i_ms] / cnt)
+            reg_cols = "".join(", {}: {:.6f}".format(key, a[7 + i] / cnt) for i, (key, _) in enumerate(regs))
             logging.info("epoch: {:03d}, lr: {:.6f}, loss_pce: {:.6f}, loss_ent: {:.6f}, loss_cr: {:.6f}, loss_aux_cls: {:.6f}, "
                          "loss_memory: {:.6f}{}, {:.2f} s/epoch".format(curr_epoch, new_lr, a[0] / cnt, a[1] / cnt, a[2] / cnt,
-                                                                       a[3] / cnt, a[4] / its, crf_col, epoch_toc - epoch_tic))
+                                                                       a[3] / cnt, a[4] / its, reg_cols, epoch_toc - epoch_tic))
             logging.info("throughput: {:.1f} images/sec ({} GPU)".format(n_img * world / max(epoch_toc - epoch_tic, 1e-9), world))
         # --clip_grad_norm: the epoch's gradient-norm statistics (every rank holds the same ones: the norm is taken behind the
         # all-reduce), read behind the sync above; every rank starts them over
@@ -539,12 +512,8 @@ def train_interface(args, resume_state=None):
             scalars.add('losses/loss_ent', a[1] / cnt, curr_epoch)
             scalars.add('losses/loss_aux_cls', a[3] / cnt, curr_epoch)
             scalars.add('losses/loss_memory', a[4] / its, curr_epoch)
-            if args.do_loss_crf:
-                scalars.add('train/loss_crf', a[7] / cnt, curr_epoch)
-            if args.do_loss_nc:
-                scalars.add('train/loss_nc', a[i_nc] / cnt, curr_epoch)
-            if args.do_loss_ms:
-                scalars.add('train/loss_ms', a[i_ms] / cnt, curr_epoch)
+            for i, (key, _) in enumerate(regs):
+                scalars.add(f'train/{key}', a[7 + i] / cnt, curr_epoch)
             scalars.add('lr/current_lr', new_lr, curr_epoch)
             scalars.add('losses/loss_pce_val', loss_pce_val, curr_epoch)
             for i, nm in enumerate(names):

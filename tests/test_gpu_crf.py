@@ -288,7 +288,7 @@ def test_mask_applies_without_entropy_or_consistency():
     # train mode without a graph (no_grad): the loss is still evaluated, from a forward-only plan without a unit-gradient buffer
     with torch.no_grad():
         o = model(batch, mode='train', step=0)
-    assert abs(float(o['loss_crf']) - float(out['loss_crf'])) <= 1e-5 and model.engine.last_plan.crf['unit'] is None
+    assert abs(float(o['loss_crf']) - float(out['loss_crf'])) <= 1e-5 and model.engine.last_plan.regs['crf'].unit is None
     assert 'loss_crf' not in model(batch, mode='val')
 
 
@@ -306,7 +306,7 @@ def test_flag_off_is_the_parent_step():
         sum(out[k] * wt for k, wt in O.loss_weights(args, 3).items()).backward()
         torch.cuda.synchronize()
         plan = model.engine.last_plan
-        assert plan.crf is None and model.engine.crf is None and plan.all_sums.numel() == 8
+        assert 'crf' not in plan.regs and 'crf' not in model.engine.regs and plan.all_sums.numel() == 8
         runs[tag] = (list(out), {k: v.detach().clone() for k, v in out.items()}, model.flat.grads.clone(), plan.dlogits.clone())
     a, b = runs['absent'], runs['off']
     assert a[0] == b[0] and 'loss_crf' not in a[0]

@@ -344,10 +344,10 @@ def _whole_step(storage, with_others):
     plan = model.engine.last_plan
     scale = plan.loss_scale
     s0 = 10 if with_others else 6
-    assert plan.all_sums.numel() == s0 + 4 and plan.ms['sums'].data_ptr() == plan.all_sums[s0:].data_ptr()
+    assert plan.all_sums.numel() == s0 + 4 and plan.regs['ms'].sums.data_ptr() == plan.all_sums[s0:].data_ptr()
     assert plan.aux['sums'].data_ptr() == plan.all_sums[s0 + 2:].data_ptr()
     if with_others:
-        assert plan.crf['sums'].data_ptr() == plan.all_sums[6:].data_ptr() and plan.nc['sums'].data_ptr() == plan.all_sums[8:].data_ptr()
+        assert plan.regs['crf'].sums.data_ptr() == plan.all_sums[6:].data_ptr() and plan.regs['nc'].sums.data_ptr() == plan.all_sums[8:].data_ptr()
     zw = out['segmentation/logits']
     g, vals = _oracle_dlogits(args, batch, zw, out['segmentation/logits_strong'], w, with_others)
     tag = f'{storage}{" + crf + nc" if with_others else ""}'
@@ -408,9 +408,9 @@ def test_mask_applies_without_entropy_or_consistency():
     S1, _, _ = R.ms_stats(z, batch['image'].cpu(), None)
     ref = R.ms_loss_direct(z, batch['image'].cpu(), batch['valid_mask'].cpu())
     plan = model.engine.last_plan
-    st = plan.ms['stats'].cpu()
+    st = plan.regs['ms'].state.cpu()
     # (the block always ends with the auxiliary pair's slot: 8 doubles without a regulariser, 10 with this one)
-    assert plan.all_sums.numel() == 10 and plan.ms['sums'].data_ptr() == plan.all_sums[6:].data_ptr()
+    assert plan.all_sums.numel() == 10 and plan.regs['ms'].sums.data_ptr() == plan.all_sums[6:].data_ptr()
     assert float(((S1 - S) / S1).min()) > 0.1                               # the masked sums are not the unmasked ones ...
     assert float(((st[..., 0] - S).abs() / S).max()) <= 1e-6 and float(((st[..., 1:] - mu).abs() / mu).max()) <= 1e-6      # ... the device has the masked
     assert plan.all_sums[7].item() == float(batch['valid_mask'].sum())
@@ -419,7 +419,7 @@ def test_mask_applies_without_entropy_or_consistency():
     with torch.no_grad():
         o = model(batch, mode='train', step=0)
     assert list(o) == ['segmentation/logits', 'loss_pce', 'loss_ms']
-    assert abs(float(o['loss_ms']) - float(out['loss_ms'])) <= 1e-5 and model.engine.last_plan.ms['unit'] is None
+    assert abs(float(o['loss_ms']) - float(out['loss_ms'])) <= 1e-5 and model.engine.last_plan.regs['ms'].unit is None
     assert 'loss_ms' not in model(batch, mode='val')
 
 
@@ -437,7 +437,7 @@ def test_flag_off_is_the_parent_step():
         sum(out[k] * wt for k, wt in O.loss_weights(args, 3).items()).backward()
         torch.cuda.synchronize()
         plan = model.engine.last_plan
-        assert plan.ms is None and model.engine.ms is None and plan.nc is None and plan.crf is None and plan.all_sums.numel() == 8
+        assert 'ms' not in model.engine.regs and not plan.regs and plan.all_sums.numel() == 8
         assert plan.aux['sums'].data_ptr() == plan.all_sums[6:].data_ptr()
         runs[tag] = (list(out), {k: v.detach().clone() for k, v in out.items()}, model.flat.grads.clone(), plan.dlogits.clone())
     a, b = runs['absent'], runs['off']
@@ -449,7 +449,7 @@ def test_flag_off_is_the_parent_step():
     model = build_model(both)
     model.train()
     out = model(_step_batch(2, 64), mode='train', step=3)
-    assert 'loss_ms' not in out and model.engine.last_plan.all_sums.numel() == 12 and model.engine.last_plan.ms is None
+    assert 'loss_ms' not in out and model.engine.last_plan.all_sums.numel() == 12 and 'ms' not in model.engine.last_plan.regs
 
 
 def test_engine_rejects_bad_parameters_before_a_launch():
@@ -541,7 +541,7 @@ def _rank(rank, world, port, out_path):
     _assembled(args, out, 37)[0].backward()
     torch.cuda.synchronize()
     if rank == 0:
-        torch.save(dict(loss_ms=float(out['loss_ms']), D=float(model.engine.last_plan.ms['sums'][1]), valid=float(full['valid_mask'].sum()),
+        torch.save(dict(loss_ms=float(out['loss_ms']), D=float(model.engine.last_plan.regs['ms'].sums[1]), valid=float(full['valid_mask'].sum()),
                         grads=model.flat.grads.cpu()), out_path)
     if world > 1:
         dist.barrier()

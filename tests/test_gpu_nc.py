@@ -313,7 +313,7 @@ def _whole_step(storage, with_crf):
     torch.cuda.synchronize()
     plan = model.engine.last_plan
     scale = plan.loss_scale
-    assert plan.all_sums.numel() == (12 if with_crf else 10) and plan.nc['sums'].data_ptr() == plan.all_sums[8 if with_crf else 6:].data_ptr()
+    assert plan.all_sums.numel() == (12 if with_crf else 10) and plan.regs['nc'].sums.data_ptr() == plan.all_sums[8 if with_crf else 6:].data_ptr()
     g, vals = _oracle_dlogits(args, batch, out['segmentation/logits'], out['segmentation/logits_strong'], w, with_crf)
     ref_g = sum(g.values())
     got = float(out['loss_nc'])
@@ -367,7 +367,7 @@ def test_mask_applies_without_entropy_or_consistency():
     A, V = R.nc_assoc_vol(z, batch['image'].cpu(), batch['valid_mask'].cpu())
     A1, V1 = R.nc_assoc_vol(z, batch['image'].cpu(), None)
     ref = R.nc_terms(A, V).mean()
-    av = model.engine.last_plan.nc['assoc_vol'].cpu()
+    av = model.engine.last_plan.regs['nc'].state.cpu()
     assert float(((V1 - V) / V1).min()) > 0.1                               # the masked volumes are not the unmasked ones ...
     assert float(A.min()) > 0
     assert float(((av[..., 1] - V).abs() / V).max()) <= 1e-6 and float(((av[..., 0] - A).abs() / A).max()) <= 1e-6      # ... and the device has the masked
@@ -375,7 +375,7 @@ def test_mask_applies_without_entropy_or_consistency():
     # train mode without a graph (no_grad): the loss is still evaluated, from a forward-only plan without a unit-gradient buffer
     with torch.no_grad():
         o = model(batch, mode='train', step=0)
-    assert abs(float(o['loss_nc']) - float(out['loss_nc'])) <= 1e-5 and model.engine.last_plan.nc['unit'] is None
+    assert abs(float(o['loss_nc']) - float(out['loss_nc'])) <= 1e-5 and model.engine.last_plan.regs['nc'].unit is None
     assert 'loss_nc' not in model(batch, mode='val')
 
 
@@ -393,7 +393,7 @@ def test_flag_off_is_the_parent_step():
         sum(out[k] * wt for k, wt in O.loss_weights(args, 3).items()).backward()
         torch.cuda.synchronize()
         plan = model.engine.last_plan
-        assert plan.nc is None and model.engine.nc is None and plan.crf is None and plan.all_sums.numel() == 8
+        assert 'nc' not in plan.regs and 'nc' not in model.engine.regs and 'crf' not in plan.regs and plan.all_sums.numel() == 8
         assert plan.aux['sums'].data_ptr() == plan.all_sums[6:].data_ptr()
         runs[tag] = (list(out), {k: v.detach().clone() for k, v in out.items()}, model.flat.grads.clone(), plan.dlogits.clone())
     a, b = runs['absent'], runs['off']

@@ -111,12 +111,13 @@ class NpzSlices(Dataset):
         return len(self.files)
 
     # --rw_scribbles (utils/random_walker.expand_dataset): a per-index list of uint8 (h, w) maps that stand in for the slice's `scb`
-    # in every kind of item, raw or not; None = the scribbles as read
+    # in every kind of item, raw or not; None = the scribbles as read.  --rw_refresh installs a utils/random_walker.SharedMaps instead
+    # of a list: the same indexing over one shared-memory buffer, which the parent updates in place under persistent workers
     scribble_override = None
 
     def _sample(self, img, lab, scb):
         if self.scribble_override is not None:
-            scb = self.scribble_override[self._index]
+            scb = np.asarray(self.scribble_override[self._index])
         if self.raw:
             return {'img': img.astype(np.float32), 'lab': lab.astype(np.int32), 'scb': scb.astype(np.int32)}
         img = img.astype(np.float32)

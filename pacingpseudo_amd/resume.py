@@ -41,7 +41,8 @@ ABSENT_DEFAULTS = {'clip_grad_norm': 0.0, 'ema_decay': 0.0, 'ema_val_interval': 
                    'nc_sigma_xy': 6.0, 'nc_sigma_rgb': 0.1,
                    'do_loss_ms': False, 'loss_ms_weight': 0.1, 'ramp_up_loss_ms': False, 'ms_tv_weight': 1.0,
                    'freeze_encoder': 0, 'init_from': None, 'init_reset_head': False,
-                   'rw_scribbles': False, 'rw_beta': 13.0, 'rw_threshold': 0.9, 'rw_eps': 1e-4, 'rw_tol': 1e-6, 'rw_max_iters': 10000}
+                   'rw_scribbles': False, 'rw_beta': 13.0, 'rw_threshold': 0.9, 'rw_eps': 1e-4, 'rw_tol': 1e-6, 'rw_max_iters': 10000,
+                   'rw_refresh': 0, 'rw_refresh_start': 0, 'rw_prior_gamma': 0.1}
 # attributes the drivers add to the namespace after parsing (not flags)
 _DERIVED = frozenset({'child', 'train_ls', 'val_ls'})
 
@@ -154,6 +155,58 @@ def truncate_scalars(path: str, last_epoch: int) -> None:
     with os.fdopen(fd, 'w') as f:
         f.writelines(keep)
     os.replace(tmp, path)
+
+
+# ---- --rw_refresh: the pseudo-label maps in force ---------------------------------------------------------------------------
+# The state file's format does not change: a refresh at epoch t leaves <run dir>/rw_refresh/maps_<t>.npz behind, and a run resumed
+# from state_<e> trains on the maps of the largest refresh epoch t <= e (a refresh due at e + 1 is recomputed from the restored
+# weights like any other work of that epoch).
+def refresh_maps_path(run_dir: str, epoch: int) -> str:
+    return os.path.join(run_dir, 'rw_refresh', f'maps_{epoch:d}.npz')
+
+
+def save_refresh_maps(path: str, maps, report: dict, params: dict) -> None:
+    """Compressed uint8 maps (one flat array + the (h, w) of every slice) with the refresh's report and parameters, through a
+    temporary file in the same directory + os.replace."""
+    d = os.path.dirname(os.path.abspath(path))
+    os.makedirs(d, exist_ok=True)
+    flat = np.concatenate([np.asarray(m, dtype=np.uint8).ravel() for m in maps]) if len(maps) else np.zeros(0, np.uint8)
+    shapes = np.asarray([m.shape for m in maps], dtype=np.int32).reshape(len(maps), 2)
+    fd, tmp = tempfile.mkstemp(prefix='.' + os.path.basename(path) + '.', suffix='.tmp', dir=d)
+    try:
+        with os.fdopen(fd, 'wb') as f:
+            np.savez_compressed(f, maps=flat, shapes=shapes, **{'report_' + k: v for k, v in report.items()},
+                                **{'param_' + k: v for k, v in params.items()})
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+
+
+def read_refresh_maps(path: str) -> list:
+    """The per-slice uint8 (h, w) maps of a file written by save_refresh_maps."""
+    with np.load(path) as z:
+        flat, shapes = z['maps'], z['shapes']
+    off = np.concatenate([[0], np.cumsum(shapes[:, 0].astype(np.int64) * shapes[:, 1])])
+    return [flat[off[i]:off[i + 1]].reshape(int(shapes[i, 0]), int(shapes[i, 1])) for i in range(len(shapes))]
+
+
+def load_refresh_maps(run_dir: str, epoch: int, every: int, start: int, shapes):
+    """The maps a run resumed from state_<epoch> trains on, or None when no refresh happened up to that epoch."""
+    if not every or epoch < start:
+        return None
+    t = start + (epoch - start) // every * every
+    path = refresh_maps_path(run_dir, t)
+    if not os.path.isfile(path):
+        raise ResumeError(f'--resume: {path} is missing: the pseudo-labels in force after epoch {epoch} were written there by the '
+                          f'refresh at epoch {t} (--rw_refresh {every}), and the run cannot be continued without them')
+    maps = read_refresh_maps(path)
+    if [tuple(m.shape) for m in maps] != [tuple(s) for s in shapes]:
+        raise ResumeError(f'--resume: {path} does not hold one map per training slice of this data set')
+    return maps
 
 
 # ---- random generators -----------------------------------------------------------------------------------------------------

@@ -31,7 +31,7 @@ import torch
 from . import finetune, resume
 from .regop import REGULARISERS, active_regularisers
 from .optim import add_clip_flag, add_ema_flags, log_clip_stats, positive_float, positive_int
-from .utils.random_walker import add_rw_flags, check_rw_params
+from .utils.random_walker import add_rw_flags, add_rw_refresh_flags, check_rw_params, check_rw_refresh_flags
 
 parser = argparse.ArgumentParser(description='PacingPseudo training on MI355X (flag surface of the reference driver)')
 
@@ -192,6 +192,9 @@ finetune.add_flags(parser)                    # --freeze_encoder N / --init_from
 # random-walker expansion of the training scribbles, once before the first step (libpacingpseudo_prep.so); the
 # reference has no such stage.  It acts on the labels, not on a loss: everything downstream sees an ordinary scribble map
 add_rw_flags(parser)                          # --rw_scribbles / --rw_beta / --rw_threshold / --rw_eps / --rw_tol / --rw_max_iters
+# ... and its second half: every N epochs the walker runs again with the network's own soft-max as a unary prior beside the seeds
+# (libpacingpseudo_rwp.so) and the pseudo-labels are replaced, between epochs, never inside a step
+add_rw_refresh_flags(parser)                  # --rw_refresh / --rw_refresh_start / --rw_prior_gamma
 
 
 # The reference ships ONE driver (train_chaos.py) and three dataset packages that differ only in class tables and
@@ -241,6 +244,10 @@ def parse_args(argv=None):
         check_rw_params(args.rw_beta, args.rw_eps, args.rw_tol, args.rw_max_iters, args.rw_threshold)
     except (ValueError, NotImplementedError) as e:
         parser.error(f'--rw_beta / --rw_eps / --rw_tol / --rw_max_iters / --rw_threshold: {e}')
+    try:
+        check_rw_refresh_flags(args.rw_refresh, args.rw_refresh_start, args.rw_prior_gamma)
+    except ValueError as e:
+        parser.error(f'--rw_refresh / --rw_refresh_start / --rw_prior_gamma: {e}')
     if args.cr_teacher == 'ema':
         if not args.do_decoder_consistency:
             parser.error('--cr_teacher ema: the teacher is the weak side of the consistency term; add --do_decoder_consistency')
@@ -333,6 +340,22 @@ def train_interface(args, resume_state=None):
                 logging.warning('random-walker scribbles: %d systems stopped at --rw_max_iters %d before --rw_tol %g, first slices: %s',
                                 rw_summary['unconverged'], prm['max_iters'], prm['tol'], rw_summary['unconverged_slices'][:8])
             np.savez(os.path.join(args.child, 'rw_scribbles.npz'), **rw_report, **{'param_' + k: v for k, v in prm.items()})
+    # --rw_refresh: the maps live in ONE shared-memory buffer from before the loaders exist, so that the persistent workers see what
+    # a refresh writes into it.  Until the first refresh it holds the --rw_scribbles expansion if given, else the scribbles on disk;
+    # a resumed run loads the maps of the last refresh the saved epoch had seen.
+    rw_every, rw_start, rw_gamma = check_rw_refresh_flags(args.rw_refresh, args.rw_refresh_start, args.rw_prior_gamma)
+    rw_shared = None
+    if rw_every:
+        from .utils.random_walker import SharedMaps
+        first = train_dataset.scribble_override
+        if first is None:
+            first = [np.asarray(train_dataset.raw_arrays(i)[2]).astype(np.uint8) for i in range(len(train_dataset))]
+        rw_shared = SharedMaps(first)
+        if resume_state is not None:
+            saved = resume.load_refresh_maps(args.child, resume_state['epoch'], rw_every, rw_start, rw_shared.shapes)
+            for i, m in enumerate(saved or ()):
+                rw_shared.update(i, m)
+        train_dataset.scribble_override = rw_shared
     sampler = torch.utils.data.distributed.DistributedSampler(train_dataset, world, rank, shuffle=True,
                                                               seed=args.seed, drop_last=True) if world > 1 else None
     train_loader = torch.utils.data.DataLoader(train_dataset, batch_size=args.batch_size, shuffle=sampler is None,
@@ -384,7 +407,29 @@ def train_interface(args, resume_state=None):
         dsc, loss_pce_val, _ = meters.result(parallel.all_reduce_sum if world > 1 else None)   # the one host sync
         return dsc, loss_pce_val
 
+    def rw_refresh(epoch):
+        """--rw_refresh: new pseudo-labels for every training slice from the live weights (every rank computes the whole set: the same
+        bits on each), written into the shared maps before this epoch's loader iterator exists.  Leaves nothing else behind."""
+        from .utils.random_walker import refresh_dataset, refresh_forward, refresh_summary_line, summarize
+        prm = dict(check_rw_params(args.rw_beta, args.rw_eps, args.rw_tol, args.rw_max_iters, args.rw_threshold, K=args.num_classes),
+                   gamma=rw_gamma)
+        tic = time.time()
+        maps, rep = refresh_dataset(train_dataset, refresh_forward(model, args.num_classes), args.num_classes, device, prm,
+                                    args.output_stride)
+        for i, m in enumerate(maps):
+            rw_shared.update(i, m)
+        if rank == 0:
+            s = summarize(rep)
+            skipped, changed = int(rep['skipped'].sum()), float(rep['changed'].mean())
+            logging.info(refresh_summary_line(s, epoch, skipped, changed) + ', {:.2f} s'.format(time.time() - tic))
+            scalars.add('RW/refresh_coverage', s['coverage_after'], epoch)
+            scalars.add('RW/refresh_agreement', s['agreement'], epoch)
+            scalars.add('RW/refresh_changed', changed, epoch)
+            resume.save_refresh_maps(resume.refresh_maps_path(args.child, epoch), maps, rep, prm)
+
     for curr_epoch in range(start_epoch, args.epoch):
+        if rw_every and curr_epoch >= rw_start and (curr_epoch - rw_start) % rw_every == 0:
+            rw_refresh(curr_epoch)
         epoch_tic = time.time()
         if sampler is not None:
             sampler.set_epoch(curr_epoch)

@@ -4,3 +4,4 @@ from .tta import TTA_MODES, tta_ops, tta_predict, tta_view  # noqa: F401
 from .metrics import batch_surface_metrics, compute_hd, surface_metrics_from_reduction  # noqa: F401
 from .crf_refine import check_crf_refine_params, crf_refine  # noqa: F401
 from .random_walker import check_rw_params, expand_scribbles, random_walker  # noqa: F401
+from .random_walker import SharedMaps, check_rw_prior_params, random_walker_prior, refresh_dataset, refresh_scribbles  # noqa: F401

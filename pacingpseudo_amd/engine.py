@@ -633,6 +633,10 @@ class StepEngine:
         # of the consistency term comes from a forward-only pass that reads the optimizer's EMA shadow.  None: the step as it was.
         self.teacher = None
         self.teacher_resync = None       # callable: shadow := parameters wherever the optimizer has not averaged yet (invalidate_packed)
+        # --cr_uncertainty (set_uncertainty): the teacher call of the consistency term is masked by the entropy of the teacher's mean
+        # soft-max over noisy passes.  None: the step as it was -- no launch, no buffer, no output key, libpacingpseudo_unc.so not loaded.
+        self.unc = None                  # dict(passes, sigma, clip, start, seed)
+        self.unc_state = None            # (seed, step) of the noise generator: ONE int64[2] device buffer, owned by the engine
         # 16-bit storage of activations / activation gradients for TRAINING plans (`--storage fp16`, BASELINE config 5; PP_ACT_H16=1
         # forces it for A/B runs).  Forward-only plans (validation, inference at native slice sizes) stay fp32.
         # the regularisers on the weak logits that are switched on: {name: parameters}, constants of the run (checked here, before
@@ -719,6 +723,8 @@ class StepEngine:
         with their key (teacher_key), so a captured step is captured again."""
         self.teacher = dict(slabs) if slabs else None
         self.teacher_resync = resync if self.teacher is not None else None
+        if self.teacher is None:
+            self.unc = None              # the uncertainty mask is a mask on the teacher call
         for p in self.plans.values():
             p.teacher_plan = None
 
@@ -727,6 +733,96 @@ class StepEngine:
         if self.teacher is None:
             return None
         return tuple((i, f.params.data_ptr(), e.data_ptr()) for i, (f, e) in sorted(self.teacher.items()))
+
+    # ------------------------------------------------------------------ the uncertainty mask of the teacher call
+    def set_uncertainty(self, passes=None, sigma=0.1, clip=0.2, start=0.75, seed=0) -> None:
+        """``--cr_uncertainty``: from now on the teacher call of the consistency term acts where the entropy of the teacher's mean
+        soft-max over `passes` noisy passes is below theta(epoch) (utils/uncertainty.py has the definition).  Needs an attached
+        teacher.  ``set_uncertainty(None)`` (or 0) switches it off.  The (seed, step) state of the generator is one device buffer of
+        the ENGINE, created at the first call and kept at its address ever after -- plans and captured graphs come and go around
+        it; every call with settings rewrites it to (seed, 0), set_uncertainty_state restores a saved pair.  In a data-parallel
+        run the seed is mixed with the rank (call parallel.attach first), so the ranks perturb their shards independently."""
+        if not passes:
+            self.unc = None
+            return
+        if self.teacher is None:
+            raise ValueError('the uncertainty mask is a mask on the EMA teacher\'s call: attach_teacher(optimizer) first (--cr_teacher ema)')
+        from .utils.uncertainty import check_uncertainty_params
+        prm = check_uncertainty_params(passes, sigma, clip, start, seed, K=self.backbone.num_classes)
+        self.unc = prm
+        self.set_uncertainty_state((prm['seed'] + self.rank * 0x9E3779B97F4A7C15) & ((1 << 64) - 1), 0)
+
+    def set_uncertainty_state(self, seed: int, step: int) -> None:
+        """Write (seed, step) into the engine's state buffer, in place (``--resume``: before the first step)."""
+        from .utils.uncertainty import state_tensor
+        new = state_tensor(seed, step, self.device)
+        if self.unc_state is None or self.unc_state.device != new.device:
+            self.unc_state = new
+        else:
+            self.unc_state.copy_(new)
+
+    def uncertainty_state(self):
+        """(seed, step) as unsigned Python integers (synchronises), or None when the feature was never configured."""
+        if self.unc_state is None:
+            return None
+        a, b = (int(v) & ((1 << 64) - 1) for v in self.unc_state.tolist())
+        return a, b
+
+    def uncertainty_stats(self) -> torch.Tensor:
+        """double[3] on the device, written by the most recent training step: (sum of the mask, sum of the entropy over valid
+        pixels, number of valid pixels).  A buffer of the teacher plan: read it before the next step."""
+        tp = self.last_plan.teacher_plan if self.last_plan is not None else None
+        if tp is None or getattr(tp, 'unc', None) is None:
+            raise RuntimeError('uncertainty_stats: no training step with the uncertainty mask has run')
+        return tp.unc['stats']
+
+    def uncertainty_key(self):
+        """What a captured step bakes in of the uncertainty mask: the settings and the ADDRESS of the state buffer (its content is
+        read by the kernels, so a replay draws new noise).  theta changes per epoch, which the capture key contains already."""
+        if self.unc is None:
+            return None
+        u = self.unc
+        return (u['passes'], u['sigma'], u['clip'], u['start'], self.unc_state.data_ptr())
+
+    def _uncertainty_buffers(self, tp: _Plan, B, K, Cin, H, W):
+        """acc, mask, noisy image, the noisy passes' logits, stats and workspace: buffers of the TEACHER plan."""
+        from ._unc import unc
+        bufs = getattr(tp, 'unc', None)
+        if bufs is None:
+            dev = self.device
+            f32 = dict(device=dev, dtype=torch.float32)
+            nws = unc.punc_workspace_bytes(B, K, H * W)
+            if nws == 0:
+                raise RuntimeError(f'punc_workspace_bytes({B}, {K}, {H * W}) = 0: {unc.punc_last_error().decode()}')
+            bufs = tp.unc = dict(acc=torch.empty((B, K, H, W), **f32), mask=torch.empty((B, 1, H, W), **f32),
+                                 noisy=torch.empty((B, Cin, H, W), **f32), logits=torch.empty((B, K, H, W), **f32),
+                                 stats=torch.zeros(3, device=dev, dtype=torch.float64),
+                                 ws=torch.empty(nws // 8, device=dev, dtype=torch.float64), ws_bytes=nws)
+        return bufs
+
+    def _uncertainty_passes(self, tp: _Plan, image, logits_t, theta: float, valid_mask, st) -> None:
+        """Behind the clean teacher pass, on the main stream, with the teacher's packs of this step: for every pass noise ->
+        image pack -> the teacher plan's forward into ONE reused logits buffer -> punc_accumulate; then one punc_advance.  With
+        sigma = 0 the only launch is punc_accumulate on the clean logits.  Leaves tp.unc['mask'] and tp.unc['stats']."""
+        from ._unc import unc
+        u = self.unc
+        B, Cin, H, W = image.shape
+        K = self.backbone.num_classes
+        b = self._uncertainty_buffers(tp, B, K, Cin, H, W)
+        vptr = valid_mask.data_ptr() if valid_mask is not None else None
+        tail = (vptr, float(theta), b['acc'].data_ptr(), b['mask'].data_ptr(), None, b['stats'].data_ptr(), b['ws'].data_ptr(),
+                b['ws_bytes'], st)
+        if u['sigma'] == 0.0:
+            unc.punc_accumulate(logits_t.data_ptr(), B, K, H * W, 0, 1, *tail)
+            return
+        T = u['passes']
+        for t in range(T):
+            unc.punc_noise_add(image.data_ptr(), image.numel(), u['sigma'], u['clip'], self.unc_state.data_ptr(), t,
+                               b['noisy'].data_ptr(), st)
+            tp.K.pp_pack_image_nchw_to_nhwc(b['noisy'].data_ptr(), B, Cin, H, W, tp.x0.ptr, tp.x0.ld, tp.x0.C, st)
+            self._unet_forward(tp, False, st, b['logits'])
+            unc.punc_accumulate(b['logits'].data_ptr(), B, K, H * W, t, T, *tail)
+        unc.punc_advance(self.unc_state.data_ptr(), st)
 
     def _teacher_offset(self, p) -> int:
         """Bytes from parameter `p` to its averaged copy.  A parameter outside every slab the optimizer updates (a frozen encoder
@@ -758,7 +854,7 @@ class StepEngine:
             plan.teacher_plan = tp
         return tp
 
-    def _teacher_forward(self, plan: _Plan, image, st) -> torch.Tensor:
+    def _teacher_forward(self, plan: _Plan, image, st, unc_args=None) -> torch.Tensor:
         """Logits (B,K,H,W) of the backbone under the averaged weights for the weak images, on the main stream: eval-mode
         BatchNorm from the model's live running statistics, nothing recorded for a backward pass, no parameter or buffer written.
         The packs are rebuilt in every step (no packed_key shortcut: a host decision a hipGraph replay would skip)."""
@@ -771,6 +867,8 @@ class StepEngine:
             tp.K.pp_pack_image_nchw_to_nhwc(image.data_ptr(), B, Cin, H, W, tp.x0.ptr, tp.x0.ld, tp.x0.C, st)
             logits = torch.empty((B, self.backbone.num_classes, H, W), device=image.device, dtype=torch.float32)
             self._unet_forward(tp, False, st, logits)
+            if unc_args is not None:         # (theta, valid_mask): the noisy passes, with the same packs and nothing recorded either
+                self._uncertainty_passes(tp, image, logits, unc_args[0], unc_args[1], st)
         finally:
             self._rec = rec
         return logits
@@ -1264,9 +1362,18 @@ class StepEngine:
         # are those of the student, as without a teacher.
         do_teacher = bool(do_cr and self.teacher is not None)
         logits_t = None
+        unc_mask = None                  # --cr_uncertainty: (B,1,H,W) mask of the teacher call, a buffer of the teacher plan
         if do_teacher:
+            unc_args = None
+            if self.unc is not None:
+                from .utils.uncertainty import uncertainty_threshold
+                vm = batch.get('valid_mask')
+                unc_args = (uncertainty_threshold(step or 0, self.unc['start'], K, getattr(args, 'ramp_up_scale', 5.0)),
+                            self._check_input(vm, 'valid_mask') if vm is not None else None)
             with prof_range('forward: teacher (EMA weights, weak view)'):
-                logits_t = self._teacher_forward(plan, image, st)
+                logits_t = self._teacher_forward(plan, image, st, unc_args)
+            if unc_args is not None:
+                unc_mask = plan.teacher_plan.unc['mask']
         plan.begin_forward((bool(bn_training), bool(self.aux.training) if self.aux is not None else False, self._frozen))
         self._rec = {} if need_grad else None
         with prof_range('pack weights + images'):
@@ -1361,7 +1468,8 @@ class StepEngine:
             plan.K.pp_seg_losses_fwd(logits.data_ptr(), None, plan.target.data_ptr(), mask_ptr,
                                   B, K, H * W, args.ignored_index, int(do_ent), 0, plan.sums.data_ptr(),
                                   plan.ws.data_ptr(), plan.ws_bytes, st)
-            plan.K.pp_seg_losses_fwd(logits_t.data_ptr(), zs.data_ptr(), plan.target.data_ptr(), mask_ptr,
+            plan.K.pp_seg_losses_fwd(logits_t.data_ptr(), zs.data_ptr(), plan.target.data_ptr(),
+                                  unc_mask.data_ptr() if unc_mask is not None else mask_ptr,      # (the mask holds valid_mask already)
                                   B, K, H * W, args.ignored_index, 0, variant, plan.sums_teacher.data_ptr(),
                                   plan.ws.data_ptr(), plan.ws_bytes, st)
         else:
@@ -1390,7 +1498,8 @@ class StepEngine:
         plan.K.pp_losses_finalize(plan.sums.data_ptr(), 1 if mask_ptr else 0, loss_pce.data_ptr(),
                                loss_ent.data_ptr() if do_ent else None, loss_cr.data_ptr() if (do_cr and not do_teacher) else None, st)
         if do_teacher:
-            plan.K.pp_losses_finalize(plan.sums_teacher.data_ptr(), 1 if mask_ptr else 0, None, None, loss_cr.data_ptr(), st)
+            plan.K.pp_losses_finalize(plan.sums_teacher.data_ptr(), 1 if (mask_ptr or unc_mask is not None) else 0, None, None,
+                                   loss_cr.data_ptr(), st)
         out['segmentation/logits'] = logits[:B]
         out['loss_pce'] = loss_pce
         if do_ent:
@@ -1400,6 +1509,8 @@ class StepEngine:
             out['segmentation/logits_strong'] = logits[B:]
             if do_teacher:
                 out['segmentation/logits_teacher'] = logits_t
+                if unc_mask is not None:
+                    out['segmentation/uncertainty_mask'] = unc_mask.view(B, 1, H, W)      # (a fresh tensor object per step over the plan's buffer)
         for op in regs.values():     # the ratio of each pair, summed over the ranks by now
             out[op.reg.key] = torch.empty((), device=dev, dtype=torch.float32)
             op.finalize(out[op.reg.key].data_ptr(), reg_mptr is not None, st)
@@ -1428,7 +1539,7 @@ class StepEngine:
                              aux_group=aux_group, logits_aux=out.get('logits_aux_cls'), frozen=self._frozen,
                              drop=self.last_drop_masks if do_aux else None, regs=tuple(regs), reg_mask=reg_mptr is not None)
             if do_teacher:
-                self.last.update(teacher=plan.teacher_plan, logits_teacher=logits_t)
+                self.last.update(teacher=plan.teacher_plan, logits_teacher=logits_t, teacher_mask=unc_mask)
         return out
 
     def _aux_input(self, plan, aux_group, st) -> View:
@@ -1523,7 +1634,9 @@ class StepEngine:
                 plan.K.pp_seg_losses_bwd(logits.data_ptr(), None, plan.target.data_ptr(), mptr, B, K, H * W, args.ignored_index,
                                       int(S['do_ent']), 0, 1, plan.sums.data_ptr(), gp('loss_pce'), gp('loss_ent'), None,
                                       plan.loss_scale, plan.dlogits.data_ptr(), None, st)
-                plan.K.pp_seg_losses_bwd(S['logits_teacher'].data_ptr(), zs_ptr, plan.target.data_ptr(), mptr, B, K, H * W,
+                tm = S.get('teacher_mask')      # --cr_uncertainty: the buffer the forward's teacher call read
+                plan.K.pp_seg_losses_bwd(S['logits_teacher'].data_ptr(), zs_ptr, plan.target.data_ptr(),
+                                      tm.data_ptr() if tm is not None else mptr, B, K, H * W,
                                       args.ignored_index, 0, S['variant'], 1, plan.sums_teacher.data_ptr(), tp.zero.data_ptr(), None,
                                       gp('loss_cr'), plan.loss_scale, tp.dlogits_discard.data_ptr(), dzs_ptr, st)
             else:

@@ -64,7 +64,9 @@ class GraphedStep:
                 id(getattr(m, 'flat', None)),
                 # --cr_teacher ema: teacher on / off, the shadow slab's address, and the teacher plans whose buffers a capture bakes in
                 eng.teacher_key() if hasattr(eng, 'teacher_key') else None,
-                tuple(id(p.teacher_plan) for p in eng.plans.values() if p.trainable and p.teacher_plan is not None))
+                tuple(id(p.teacher_plan) for p in eng.plans.values() if p.trainable and p.teacher_plan is not None),
+                # --cr_uncertainty: passes / sigma / clip / start and the ADDRESS of the (seed, step) buffer (the kernels read its content)
+                eng.uncertainty_key() if hasattr(eng, 'uncertainty_key') else None)
 
     def _capture(self, batch, epoch, key):
         comm = self.model.engine.comm

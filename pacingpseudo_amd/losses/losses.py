@@ -224,7 +224,11 @@ class _TeacherLoss(torch.autograd.Function):
 def teacher_consistency_loss(student_logits, teacher_logits, variant='ce_loss', valid_mask=None):
     """Consistency of a student's (strong-view) logits with a teacher's (weak-view) logits, the teacher a constant (mean teacher):
     the form `variant` of --loss_cr_variants with softmax(teacher_logits) -- hard_ce_loss: its arg-max -- as the target, masked
-    mean.  Returns the 0-dim loss; differentiable in `student_logits` only (the teacher's ``.grad`` stays None)."""
+    mean.  Returns the 0-dim loss; differentiable in `student_logits` only (the teacher's ``.grad`` stays None).
+
+    `valid_mask` (N, 1, H, W) fp32 is any per-pixel weight of the masked mean ``sum(m d) / max(sum(m), 1e-8)``: the batch's valid
+    mask, or the uncertainty mask ``m = utils.uncertainty_mask(noisy teacher logits, theta, valid_mask)`` of ``--cr_uncertainty``
+    (which already holds the valid mask).  An all-zero mask gives a loss of 0 with a zero gradient."""
     zs, zt = _check(student_logits, 'student_logits'), _check(teacher_logits, 'teacher_logits')
     if variant not in _VARIANT:
         raise ValueError(f'variant must be one of {sorted(_VARIANT)}, got {variant!r}')

@@ -91,13 +91,18 @@ class ConsistencyRegulr(nn.Module):
         return self
 
     # ---- mean teacher --------------------------------------------------------------------------
-    def attach_teacher(self, optimizer):
+    def attach_teacher(self, optimizer, uncertainty=None):
         """``--cr_teacher ema``: from now on the consistency term pulls the student's strong-view prediction towards what the
         optimizer's EMA weights predict for the weak view (mean teacher); no gradient reaches the teacher, and ``--detach_weak_cr``
         has nothing left to do.  The optimizer creates its shadow slab now (not at its first step) and the engine reads every
         teacher parameter at ``live address + (shadow - parameter slab)``; parameters outside the slab (frozen encoder stages)
         read as their live values.  Training-mode outputs gain ``segmentation/logits_teacher``.  ``attach_teacher(None)`` detaches.
-        Call it again after anything that re-flattens the model (``.cuda()``, ``freeze_encoder``)."""
+        Call it again after anything that re-flattens the model (``.cuda()``, ``freeze_encoder``).
+
+        ``uncertainty=dict(passes=T, sigma=, clip=, start=, seed=)`` (``--cr_uncertainty``): the teacher call acts only where the
+        entropy of the teacher's mean soft-max over T noisy passes is below a threshold relaxed over the epochs
+        (``StepEngine.set_uncertainty``, utils/uncertainty.py); training-mode outputs gain ``segmentation/uncertainty_mask`` behind
+        the teacher's logits.  None leaves the setting as it is (off unless ``set_uncertainty`` was called)."""
         if optimizer is None:
             self.engine.set_teacher(None)
             return self
@@ -109,6 +114,13 @@ class ConsistencyRegulr(nn.Module):
         shadow = optimizer.ema_shadow(flat)          # ValueError when ema_decay is off
         optimizer.ema_resync(flat)
         self.engine.set_teacher({id(flat): (flat, shadow)}, resync=lambda: optimizer.ema_resync(flat))
+        if uncertainty is not None:
+            self.engine.set_uncertainty(**uncertainty)
+        return self
+
+    def set_uncertainty(self, passes=None, **kw):
+        """``StepEngine.set_uncertainty`` for an attached teacher; ``set_uncertainty(None)`` switches the mask off."""
+        self.engine.set_uncertainty(passes, **kw)
         return self
 
     def _flatten(self):
@@ -147,6 +159,8 @@ class ConsistencyRegulr(nn.Module):
                 keys += ['loss_cr', 'segmentation/logits_strong']
                 if getattr(getattr(self, 'engine', None), 'teacher', None) is not None:
                     keys.append('segmentation/logits_teacher')
+                    if getattr(self.engine, 'unc', None) is not None:
+                        keys.append('segmentation/uncertainty_mask')
             keys += [r.key for r in active_regularisers(a)]
             if a.do_aux_path:
                 keys += ['logits_aux_cls', 'loss_aux_cls']

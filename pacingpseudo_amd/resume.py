@@ -42,7 +42,8 @@ ABSENT_DEFAULTS = {'clip_grad_norm': 0.0, 'ema_decay': 0.0, 'ema_val_interval': 
                    'do_loss_ms': False, 'loss_ms_weight': 0.1, 'ramp_up_loss_ms': False, 'ms_tv_weight': 1.0,
                    'freeze_encoder': 0, 'init_from': None, 'init_reset_head': False,
                    'rw_scribbles': False, 'rw_beta': 13.0, 'rw_threshold': 0.9, 'rw_eps': 1e-4, 'rw_tol': 1e-6, 'rw_max_iters': 10000,
-                   'rw_refresh': 0, 'rw_refresh_start': 0, 'rw_prior_gamma': 0.1}
+                   'rw_refresh': 0, 'rw_refresh_start': 0, 'rw_prior_gamma': 0.1,
+                   'cr_uncertainty': 0, 'cr_uncertainty_sigma': 0.1, 'cr_uncertainty_clip': 0.2, 'cr_uncertainty_start': 0.75}
 # attributes the drivers add to the namespace after parsing (not flags)
 _DERIVED = frozenset({'child', 'train_ls', 'val_ls'})
 
@@ -268,6 +269,10 @@ def capture(args, epoch: int, model, optimizer, best, valdice, rngs, world: int,
         extra = dict(best_ema_avg=float(best_ema['avg']), best_ema_epoch=int(best_ema['epoch']),
                      best_ema_avg_class=[float(v) for v in best_ema['avg_class']],
                      valdice_ema=torch.from_numpy(np.asarray(valdice_ema[:epoch + 1], dtype=np.float64).copy()))
+    if engine is not None and getattr(engine, 'unc', None) is not None:
+        # --cr_uncertainty only: (seed, step) of the noise generator as rank 0 holds them (the other ranks differ in the seed, which
+        # they re-derive from --seed and their rank; the step is the same everywhere)
+        extra['uncertainty_state'] = [int(v) for v in engine.uncertainty_state()]
     return dict(
         **extra,
         format=FORMAT, version=VERSION, args=flag_dict(args), world_size=int(world), epoch=int(epoch),
@@ -292,6 +297,9 @@ def restore(st: dict, model, optimizer, valdice):
     engine = getattr(model, 'engine', None)
     if engine is not None and st.get('loss_scale') is not None:
         engine.set_loss_scale(st['loss_scale'])
+    if engine is not None and getattr(engine, 'unc', None) is not None and st.get('uncertainty_state') is not None:
+        # the saved STEP into the engine's state buffer, in place, before the first step; the seed is this rank's own
+        engine.set_uncertainty_state(engine.uncertainty_state()[0], int(st['uncertainty_state'][1]))
     flat = getattr(model, 'flat', None)
     if flat is not None and st.get('guard') is not None:
         flat.guard.copy_(st['guard'].to(flat.guard.device))

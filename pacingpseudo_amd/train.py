@@ -32,6 +32,7 @@ from . import finetune, resume
 from .regop import REGULARISERS, active_regularisers
 from .optim import add_clip_flag, add_ema_flags, log_clip_stats, positive_float, positive_int
 from .utils.random_walker import add_rw_flags, add_rw_refresh_flags, check_rw_params, check_rw_refresh_flags
+from .utils.uncertainty import check_uncertainty_params, uncertainty_threshold
 
 parser = argparse.ArgumentParser(description='PacingPseudo training on MI355X (flag surface of the reference driver)')
 
@@ -185,6 +186,19 @@ parser.add_argument('--cr_teacher', type=str, default='none', choices=['none', '
                     help='ema: the consistency loss pulls the strong-view prediction towards the prediction of the EMA weights for the '
                          'weak view (mean teacher; needs --do_decoder_consistency and --ema_decay > 0; the teacher gets no gradient, '
                          'so --detach_weak_cr has nothing to do); none: towards the weak-view prediction of the same weights')
+# ... and its uncertainty mask (UA-MT / USTM; libpacingpseudo_unc.so, utils/uncertainty.py): the teacher call acts
+# only where the entropy of the teacher's mean soft-max over T noise-perturbed passes is below a threshold relaxed over the epochs
+parser.add_argument('--cr_uncertainty', type=int, default=0,
+                    help='T noisy teacher passes per step for the uncertainty mask of the consistency term, 1..16 (needs --cr_teacher '
+                         'ema; 0: off, the step as it was; untuned first value)')
+parser.add_argument('--cr_uncertainty_sigma', type=float, default=0.1,
+                    help='standard deviation of the Gaussian input noise of those passes, >= 0; 0 needs --cr_uncertainty 1 and masks '
+                         'by the plain entropy of the clean teacher pass (untuned first value)')
+parser.add_argument('--cr_uncertainty_clip', type=float, default=0.2,
+                    help='the noise is clamped to [-clip, +clip], >= 0 (untuned first value)')
+parser.add_argument('--cr_uncertainty_start', type=float, default=0.75,
+                    help='the entropy threshold starts at this fraction of ln K and ramps up to ln K (--ramp_up_scale), in (0, 1] '
+                         '(untuned first value)')
 add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
 add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
@@ -253,6 +267,15 @@ def parse_args(argv=None):
             parser.error('--cr_teacher ema: the teacher is the weak side of the consistency term; add --do_decoder_consistency')
         if not args.ema_decay > 0.0:
             parser.error('--cr_teacher ema: the teacher is the EMA of the weights; set --ema_decay D with 0 < D < 1')
+    if args.cr_uncertainty:
+        if args.cr_teacher != 'ema':
+            parser.error('--cr_uncertainty: the mask acts on the EMA teacher\'s side of the consistency term; add --cr_teacher ema')
+        try:
+            check_uncertainty_params(args.cr_uncertainty, args.cr_uncertainty_sigma, args.cr_uncertainty_clip, args.cr_uncertainty_start,
+                                     K=DATASETS.get(args.dataset, DATASETS['chaos'])['num_classes'] if args.num_classes is None
+                                     else args.num_classes)
+        except (ValueError, NotImplementedError) as e:
+            parser.error(f'--cr_uncertainty / --cr_uncertainty_sigma / --cr_uncertainty_clip / --cr_uncertainty_start: {e}')
     return args
 
 
@@ -300,7 +323,10 @@ def train_interface(args, resume_state=None):
     else:
         raise ValueError('Unimplemented optimizer')
     if args.cr_teacher == 'ema':                  # the shadow slab exists from here on (resume.restore then loads the saved one)
-        model.attach_teacher(optimizer)
+        # --cr_uncertainty: behind parallel.attach (the noise seed is mixed with the rank); resume.restore puts the saved step back
+        model.attach_teacher(optimizer, uncertainty=dict(passes=args.cr_uncertainty, sigma=args.cr_uncertainty_sigma,
+                                                         clip=args.cr_uncertainty_clip, start=args.cr_uncertainty_start,
+                                                         seed=int(args.seed) & ((1 << 64) - 1)) if args.cr_uncertainty else None)
 
     args.gpu_augment = not args.cpu_input          # the reference's recipe is the default; --cpu_input opts out
     if args.augmentations != 'TransformsColor' and not args.gpu_augment:
@@ -449,6 +475,13 @@ def train_interface(args, resume_state=None):
         regs = [(r.key, gaussian_ramp_up(t=curr_epoch, base_value=getattr(args, r.weight), scale=args.ramp_up_scale)
                  if getattr(args, r.ramp) else getattr(args, r.weight)) for r in active_regularisers(args)]
         acc_reg = torch.zeros(len(regs), device=device, dtype=torch.float64)
+        # --cr_uncertainty: [sum over steps of kept / valid pixels, sum of the mean entropy over valid pixels]
+        unc_on = bool(args.cr_uncertainty)
+        acc_unc = torch.zeros(2, device=device, dtype=torch.float64) if unc_on else None
+        if unc_on and rank == 0:
+            logging.info("epoch: {:03d}, uncertainty threshold theta: {:.6f} (ln K = {:.6f})".format(
+                curr_epoch, uncertainty_threshold(curr_epoch, args.cr_uncertainty_start, args.num_classes, args.ramp_up_scale),
+                np.log(args.num_classes)))
         n_img = 0
         for idx, batch in enumerate(train_loader):
             if args.max_iters and idx >= args.max_iters:
@@ -504,6 +537,9 @@ def train_interface(args, resume_state=None):
                     acc[4] += net_outputs['loss_memory'].detach() * args.loss_memory_weight
             for i, (key, w) in enumerate(regs):
                 acc_reg[i] += net_outputs[key].detach() * (w * n)
+            if unc_on:
+                ust = model.engine.uncertainty_stats()          # double[3] on the device: (sum m, sum u over valid, valid pixels)
+                acc_unc += ust[:2] / ust[2].clamp(min=1.0)
             acc[5] += n
             acc[6] += 1
             n_img += n
@@ -559,6 +595,10 @@ def train_interface(args, resume_state=None):
             scalars.add('losses/loss_memory', a[4] / its, curr_epoch)
             for i, (key, _) in enumerate(regs):
                 scalars.add(f'train/{key}', a[7 + i] / cnt, curr_epoch)
+            if unc_on:
+                au = acc_unc.cpu().numpy()
+                scalars.add('CR/uncertainty_kept', au[0] / its, curr_epoch)
+                scalars.add('CR/uncertainty_mean', au[1] / its, curr_epoch)
             scalars.add('lr/current_lr', new_lr, curr_epoch)
             scalars.add('losses/loss_pce_val', loss_pce_val, curr_epoch)
             for i, nm in enumerate(names):

@@ -272,6 +272,72 @@ def dice_loss_fn(input, target):
     return _DiceLoss.apply(_check(input, 'input'), _check(target, 'target'))
 
 
+class _BoundaryLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, phi):
+        from .._dist import dist
+        N, K, H, W = z.shape
+        with torch.cuda.device(z.device):
+            nws = dist.pdist_boundary_loss_workspace(N, K, H, W)
+            ws = torch.empty(max(nws // 8, 1), device=z.device, dtype=torch.float64)
+            out = torch.empty((), device=z.device, dtype=torch.float32)
+            dist.pdist_boundary_loss_fwd(z.data_ptr(), phi.data_ptr(), N, K, H, W, out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                         stream_ptr())
+        ctx.save_for_backward(z, phi)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from .._dist import dist
+        z, phi = ctx.saved_tensors
+        N, K, H, W = z.shape
+        g = g.to(torch.float32).contiguous()
+        dz = torch.empty_like(z)
+        with torch.cuda.device(z.device):
+            dist.pdist_boundary_loss_bwd(z.data_ptr(), phi.data_ptr(), N, K, H, W, g.data_ptr(), dz.data_ptr(), stream_ptr())
+        return dz, None
+
+
+def boundary_loss(input, target, dist_maps=None, spacing=(1., 1.)):
+    """Boundary loss of Kervadec et al. (MIDL 2019): mean over n, the foreground classes k = 1 .. K-1 (k = 0 when K = 1) and the pixels
+    of softmax_k(input) * phi_k, phi the signed distance maps of the label (``utils.signed_distance_maps``: negative inside a
+    class, positive outside, in units of `spacing`).  `target`: the one-hot label (N, K, H, W) as ``dice_loss_fn`` takes it (its
+    arg-max is the class map) or an int64 class map (N, H, W); with `dist_maps` (N, K, H, W) fp32 given, that phi is used as it is
+    and `target` is not read.  phi receives no gradient.  The reference has no such loss (upper_bound_chaos.py --do_loss_boundary)."""
+    from ..utils.distance import MAX_CLASSES, MAX_SIDE, check_spacing, signed_distance_maps
+    if not (torch.is_tensor(input) and input.dtype == torch.float32 and input.dim() == 4):
+        raise ValueError('input must be a 4-D float32 CUDA tensor (N,K,H,W)')
+    N, K, H, W = input.shape
+    if min(input.shape) < 1 or K > MAX_CLASSES or max(H, W) > MAX_SIDE or input.numel() >= 2 ** 31:
+        raise ValueError(f'input is {tuple(input.shape)}: need 1 <= K <= {MAX_CLASSES}, 1 <= H, W <= {MAX_SIDE}, N*K*H*W < 2^31')
+    spacing = check_spacing(spacing)
+    if dist_maps is not None:
+        if not (torch.is_tensor(dist_maps) and dist_maps.dtype == torch.float32 and tuple(dist_maps.shape) == (N, K, H, W)):
+            raise ValueError(f'dist_maps must be a float32 tensor of input\'s shape {(N, K, H, W)}')
+        if not (dist_maps.is_cuda and dist_maps.device == input.device):
+            raise ValueError('dist_maps must be a CUDA tensor on input\'s device')
+    else:
+        if not torch.is_tensor(target):
+            raise ValueError(f'target must be a torch tensor, got {type(target).__name__}')
+        if target.dim() == 4:
+            if tuple(target.shape) != (N, K, H, W):
+                raise ValueError(f'a one-hot target must have input\'s shape {(N, K, H, W)}, got {tuple(target.shape)}')
+        elif target.dim() == 3:
+            if target.dtype != torch.int64 or tuple(target.shape) != (N, H, W):
+                raise ValueError(f'a class-map target must be int64 {(N, H, W)}, got {target.dtype} {tuple(target.shape)}')
+        else:
+            raise ValueError(f'target must be one-hot (N, K, H, W) or an int64 class map (N, H, W), got {tuple(target.shape)}')
+        if not (target.is_cuda and target.device == input.device):
+            raise ValueError('target must be a CUDA tensor on input\'s device')
+    if not input.is_cuda:
+        raise ValueError('input must be a CUDA tensor: there is no CPU path')
+    if dist_maps is None:
+        with torch.no_grad():
+            cls = torch.argmax(target, dim=1) if target.dim() == 4 else target
+            dist_maps = signed_distance_maps(cls, K, spacing)
+    return _BoundaryLoss.apply(input.contiguous(), dist_maps.detach().contiguous())
+
+
 class _RegLoss(torch.autograd.Function):
     """One regulariser of regop.REGULARISERS on its own: a RegOp over buffers of this call."""
 

@@ -9,7 +9,8 @@ The step runs through ``UNet.forward`` (one autograd node over the engine's stat
 ``partial_cross_entropy_loss`` / ``dice_loss_fn``; the training set goes through the reference's WEAK augmentation list
 (upper_bound_chaos.py:132-137) on the GPU (``augment.DeviceAugmenter(do_strong=False)``; ``--cpu_input`` selects the minimal CPU
 path); validation at the native slice size with device-side meters; widened ``choices`` and the --synthetic / --image_size /
---max_iters additions are those of ``pacingpseudo_amd.train``.
+--max_iters additions are those of ``pacingpseudo_amd.train``.  ``--do_loss_boundary`` (not in the reference) adds the boundary loss
+of Kervadec et al. on signed distance maps recomputed per step from the augmented label (``losses.boundary_loss``).
 """
 from __future__ import annotations
 
@@ -73,17 +74,25 @@ add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo
 add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
 finetune.add_flags(parser)                    # --freeze_encoder N / --init_from PATH / --init_reset_head (pacingpseudo_amd/finetune.py)
+# ---- boundary loss (Kervadec et al., MIDL 2019): mean of soft-max x the signed distance map of the label, recomputed per step on the
+# device from the augmented label (libpacingpseudo_dist.so); the reference has no such term.  Off: the step is the reference's.
+parser.add_argument('--do_loss_boundary', action='store_true', default=False,
+                    help='add loss_boundary_weight * boundary_loss(logits, label) (pixel units) to cross entropy + Dice')
+parser.add_argument('--loss_boundary_weight', type=float, default=0.01,
+                    help="weight of the boundary loss; 0.01 is Kervadec's initial alpha, here an untuned first value")
+parser.add_argument('--ramp_up_loss_boundary', type=int, default=0,
+                    help='0: constant weight; E > 0: the weight of epoch e is gaussian_ramp_up(e, loss_boundary_weight, max_t=E)')
 
 
 def train_interface(args, resume_state=None):
     from .augment import AugConfig, DeviceAugmenter, collate_raw
     from .data import SyntheticPhantoms, collate_by_shape, dataset_class, expand_compact, loader_context
-    from .losses.losses import dice_loss_fn, partial_cross_entropy_loss
+    from .losses.losses import boundary_loss, dice_loss_fn, partial_cross_entropy_loss
     from .models import UNet
     from .models.unet import norm_kwargs
     from .optim import FusedAdam
     from .train import _class_names
-    from .utils import cosine_lr_decay, linear_lr_decay, poly_lr_decay
+    from .utils import cosine_lr_decay, gaussian_ramp_up, linear_lr_decay, poly_lr_decay
     from .utils.metrics import ValAccumulator
     from .utils.scalars import ScalarLog
 
@@ -126,6 +135,7 @@ def train_interface(args, resume_state=None):
         raise ValueError('Unimplemented learning rate decay policy.')
     valdice = np.zeros(args.epoch)
     ema_on = bool(args.ema_decay)                  # --ema_decay: see pacingpseudo_amd/train.py
+    bl_on = bool(args.do_loss_boundary)            # --do_loss_boundary: off = the parent's step, log lines and scalar tags
     valdice_ema = np.zeros(args.epoch) if ema_on else None
     best_ema = dict(avg=0, epoch=0, avg_class=[])
     aug_stream = torch.cuda.Stream() if (augmenter is not None and os.environ.get('PP_AUG_STREAM', '1') != '0') else None
@@ -139,9 +149,11 @@ def train_interface(args, resume_state=None):
         start_epoch = resume_state['epoch'] + 1
 
     def validate():
-        """One pass over the validation slices with the weights the model holds: (per-class Dice, loss_ce, loss_dice)."""
+        """One pass over the validation slices with the weights the model holds: (per-class Dice, loss_ce, loss_dice,
+        loss_boundary -- None without --do_loss_boundary)."""
         meters = ValAccumulator(args.num_classes, device)              # Dice meters + n-weighted loss_ce, on the device
         dsum = torch.zeros(1, device=device, dtype=torch.float64)       # n-weighted loss_dice
+        bsum = torch.zeros(1, device=device, dtype=torch.float64)       # n-weighted loss_boundary
         for groups in val_loader:
             for batch in groups:
                 batch = expand_compact(batch, args.num_classes, device)      # uint8 class maps -> one-hot planes, on the device
@@ -151,13 +163,20 @@ def train_interface(args, resume_state=None):
                     target = torch.argmax(label, dim=1).long()
                     meters.update(logits, label, partial_cross_entropy_loss(logits, target, args.ignored_index))
                     dsum += dice_loss_fn(logits, label).double() * image.shape[0]
+                    if bl_on:
+                        bsum += boundary_loss(logits, target).double() * image.shape[0]
         dsc, val_ce, n_val = meters.result()                            # the host sync of the validation epoch
-        return dsc, val_ce, float(dsum) / max(n_val, 1)
+        return dsc, val_ce, float(dsum) / max(n_val, 1), (float(bsum) / max(n_val, 1) if bl_on else None)
 
     for curr_epoch in range(start_epoch, args.epoch):
         epoch_tic = time.time()
         optimizer, new_lr = decay[args.lr_decay](optimizer, curr_epoch, args.epoch, args.lr)
-        acc = torch.zeros(3, device=device, dtype=torch.float64)        # sum ce*n, sum dice*n, n (read once per epoch)
+        # sum ce*n, sum dice*n, n (read once per epoch); with --do_loss_boundary also sum boundary*n
+        acc = torch.zeros(4 if bl_on else 3, device=device, dtype=torch.float64)
+        bl_weight = 0.0
+        if bl_on:
+            bl_weight = (gaussian_ramp_up(curr_epoch, args.loss_boundary_weight, max_t=args.ramp_up_loss_boundary)
+                         if args.ramp_up_loss_boundary > 0 else args.loss_boundary_weight)
         for idx, batch in enumerate(train_loader):
             if args.max_iters and idx >= args.max_iters:
                 break
@@ -174,22 +193,27 @@ def train_interface(args, resume_state=None):
                 loss_dice = dice_loss_fn(logits, label)
                 loss = loss + loss_dice
                 acc[1] += loss_dice.detach() * n
+            if bl_on:
+                loss_bl = boundary_loss(logits, target)
+                loss = loss + bl_weight * loss_bl
+                acc[3] += loss_bl.detach() * n
             acc[2] += n
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()
         a = acc.cpu().numpy()
         cnt = max(a[2], 1)
-        logging.info("epoch: {:03d}, lr: {:.6f}, loss_ce: {:.6f}, loss_dice: {:.6f}, {:.2f} s/epoch".format(
-            curr_epoch, new_lr, a[0] / cnt, a[1] / cnt, time.time() - epoch_tic))
+        logging.info("epoch: {:03d}, lr: {:.6f}, loss_ce: {:.6f}, loss_dice: {:.6f}, {}{:.2f} s/epoch".format(
+            curr_epoch, new_lr, a[0] / cnt, a[1] / cnt, "loss_boundary: {:.6f}, ".format(a[3] / cnt) if bl_on else "",
+            time.time() - epoch_tic))
         log_clip_stats(optimizer, curr_epoch, scalars, logging.info)      # --clip_grad_norm: behind the sync above
 
         model.eval()                                   # upper_bound_chaos.py:180, never undone
         tic = time.time()
-        dsc, val_ce, val_dice = validate()
+        dsc, val_ce, val_dice, val_bl = validate()
         avg_all = np.mean([dsc[_] for _ in range(1, args.num_classes)])
-        logging.info("val: {:03d}, loss_ce: {:.6f}, loss_dice: {:.6f}, {:.2f} s/epoch".format(
-            curr_epoch, val_ce, val_dice, time.time() - tic))
+        logging.info("val: {:03d}, loss_ce: {:.6f}, loss_dice: {:.6f}, {}{:.2f} s/epoch".format(
+            curr_epoch, val_ce, val_dice, "loss_boundary: {:.6f}, ".format(val_bl) if bl_on else "", time.time() - tic))
         logging.info("[" + ", ".join("{}: {:.4f}".format(nm, dsc[i]) for i, nm in enumerate(names))
                      + ", All: {:.4f}]".format(avg_all))
         # scalar tags of upper_bound_chaos.py:176-178, :216-224
@@ -198,6 +222,10 @@ def train_interface(args, resume_state=None):
         scalars.add('lr/current_lr', new_lr, curr_epoch)
         scalars.add('losses/loss_ce_val', val_ce, curr_epoch)
         scalars.add('losses/loss_dice_val', val_dice, curr_epoch)
+        if bl_on:
+            scalars.add('losses/loss_boundary_train', a[3] / cnt, curr_epoch)
+            scalars.add('losses/loss_boundary_val', val_bl, curr_epoch)
+            scalars.add('losses/boundary_weight', bl_weight, curr_epoch)
         for i, nm in enumerate(names):
             scalars.add(f'DSC/{nm}', dsc[i], curr_epoch)
         scalars.add('DSC/All', avg_all, curr_epoch)
@@ -217,7 +245,7 @@ def train_interface(args, resume_state=None):
             with optimizer.ema_weights():
                 if ema_val:
                     tic = time.time()
-                    dsc_e, ce_e, dice_e = validate()
+                    dsc_e, ce_e, dice_e = validate()[:3]
                     avg_e = np.mean([dsc_e[_] for _ in range(1, args.num_classes)])
                     valdice_ema[curr_epoch] = avg_e
                     logging.info("val_ema: {:03d}, loss_ce: {:.6f}, loss_dice: {:.6f}, {:.2f} s/epoch".format(
@@ -254,6 +282,8 @@ def train_interface(args, resume_state=None):
 def train_main(argv=None):
     from .train import DATASETS, apply_dataset_preset, split_dir
     args = apply_dataset_preset(parser.parse_args(argv))
+    if args.ramp_up_loss_boundary < 0 or not np.isfinite(args.loss_boundary_weight):
+        parser.error('--loss_boundary_weight must be finite and --ramp_up_loss_boundary >= 0')
     # one process: the upper bound has no data-parallel path
     state_file, resume_state = resume.open_state(parser, args, 1) if args.resume else (None, None)
     if 'LOCAL_RANK' not in os.environ:

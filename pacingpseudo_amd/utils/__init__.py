@@ -6,3 +6,4 @@ from .crf_refine import check_crf_refine_params, crf_refine  # noqa: F401
 from .random_walker import check_rw_params, expand_scribbles, random_walker  # noqa: F401
 from .random_walker import SharedMaps, check_rw_prior_params, random_walker_prior, refresh_dataset, refresh_scribbles  # noqa: F401
 from .uncertainty import add_noise, check_uncertainty_params, uncertainty_mask, uncertainty_threshold  # noqa: F401
+from .distance import distance_transform_edt, signed_distance_maps  # noqa: F401

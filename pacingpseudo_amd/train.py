@@ -32,6 +32,7 @@ from . import finetune, resume
 from .regop import REGULARISERS, active_regularisers
 from .optim import add_clip_flag, add_ema_flags, log_clip_stats, positive_float, positive_int
 from .utils.random_walker import add_rw_flags, add_rw_refresh_flags, check_rw_params, check_rw_refresh_flags
+from .utils.geodesic import add_geo_flags, check_geo_params
 from .utils.uncertainty import check_uncertainty_params, uncertainty_threshold
 
 parser = argparse.ArgumentParser(description='PacingPseudo training on MI355X (flag surface of the reference driver)')
@@ -209,6 +210,9 @@ add_rw_flags(parser)                          # --rw_scribbles / --rw_beta / --r
 # ... and its second half: every N epochs the walker runs again with the network's own soft-max as a unary prior beside the seeds
 # (libpacingpseudo_rwp.so) and the pseudo-labels are replaced, between epochs, never inside a step
 add_rw_refresh_flags(parser)                  # --rw_refresh / --rw_refresh_start / --rw_prior_gamma
+# the other classical expansion, also once before the first step: geodesic distance of the seeds on the normalised image
+# (libpacingpseudo_geo.so).  One of the two: --geo_scribbles with --rw_scribbles is an error
+add_geo_flags(parser)                         # --geo_scribbles / --geo_lambda / --geo_ratio / --geo_max_dist / --geo_max_sweeps
 
 
 # The reference ships ONE driver (train_chaos.py) and three dataset packages that differ only in class tables and
@@ -262,6 +266,12 @@ def parse_args(argv=None):
         check_rw_refresh_flags(args.rw_refresh, args.rw_refresh_start, args.rw_prior_gamma)
     except ValueError as e:
         parser.error(f'--rw_refresh / --rw_refresh_start / --rw_prior_gamma: {e}')
+    try:
+        check_geo_params(args.geo_lambda, args.geo_ratio, args.geo_max_dist, args.geo_max_sweeps)
+    except (ValueError, NotImplementedError) as e:
+        parser.error(f'--geo_lambda / --geo_ratio / --geo_max_dist / --geo_max_sweeps: {e}')
+    if args.geo_scribbles and args.rw_scribbles:
+        parser.error('--geo_scribbles and --rw_scribbles both expand the scribbles before the first step: give one of them')
     if args.cr_teacher == 'ema':
         if not args.do_decoder_consistency:
             parser.error('--cr_teacher ema: the teacher is the weak side of the consistency term; add --do_decoder_consistency')
@@ -366,6 +376,19 @@ def train_interface(args, resume_state=None):
                 logging.warning('random-walker scribbles: %d systems stopped at --rw_max_iters %d before --rw_tol %g, first slices: %s',
                                 rw_summary['unconverged'], prm['max_iters'], prm['tol'], rw_summary['unconverged_slices'][:8])
             np.savez(os.path.join(args.child, 'rw_scribbles.npz'), **rw_report, **{'param_' + k: v for k, v in prm.items()})
+    if getattr(args, 'geo_scribbles', False):
+        # the same place and the same contract as --rw_scribbles: every rank computes the full list (the same bits on each, and
+        # in a resumed run), --rw_refresh starts from it, validation data are not touched
+        from .utils.geodesic import expand_dataset_geo, summarize_geo, summary_line_geo
+        gprm = check_geo_params(args.geo_lambda, args.geo_ratio, args.geo_max_dist, args.geo_max_sweeps, K=args.num_classes)
+        train_dataset.scribble_override, geo_report = expand_dataset_geo(train_dataset, args.num_classes, device, gprm)
+        geo_summary = summarize_geo(geo_report)
+        if rank == 0:
+            logging.info(summary_line_geo(geo_summary))
+            if geo_summary['unconverged']:
+                logging.warning('geodesic scribbles: %d planes stopped at --geo_max_sweeps %d, first slices: %s',
+                                geo_summary['unconverged'], gprm['max_sweeps'], geo_summary['unconverged_slices'][:8])
+            np.savez(os.path.join(args.child, 'geo_scribbles.npz'), **geo_report, **{'param_' + k: v for k, v in gprm.items()})
     # --rw_refresh: the maps live in ONE shared-memory buffer from before the loaders exist, so that the persistent workers see what
     # a refresh writes into it.  Until the first refresh it holds the --rw_scribbles expansion if given, else the scribbles on disk;
     # a resumed run loads the maps of the last refresh the saved epoch had seen.

@@ -7,3 +7,4 @@ from .random_walker import check_rw_params, expand_scribbles, random_walker  # n
 from .random_walker import SharedMaps, check_rw_prior_params, random_walker_prior, refresh_dataset, refresh_scribbles  # noqa: F401
 from .uncertainty import add_noise, check_uncertainty_params, uncertainty_mask, uncertainty_threshold  # noqa: F401
 from .distance import distance_transform_edt, signed_distance_maps  # noqa: F401
+from .geodesic import check_geo_params, expand_dataset_geo, geodesic_distance, geodesic_expand_scribbles  # noqa: F401

@@ -1,13 +1,15 @@
 #!/usr/bin/env python
 """Offline random-walker expansion of scribbles (pacingpseudo_amd/utils/random_walker.py): the same call the
 training driver makes with --rw_scribbles, written to disk -- to train from later without the flag, or to look at the pseudo-labels.
+With --method geo it is the geodesic expansion of --geo_scribbles instead (pacingpseudo_amd/utils/geodesic.py).
 
     python scripts/expand_scribbles.py --file_list train_fold1.txt --data_root ./data/chaos --out ./data/chaos_rw
     python scripts/expand_scribbles.py --synthetic 4 --image_size 32 --out /tmp/rw
 
 Every slice becomes one .npz in --out with the keys of its source (uid / img / lab / scb): `scb` is the expanded map (the ignore
 index where the walker is not confident), the original is kept as `scb_orig`, and `rw_maxprob` (float16) is the walker's largest
-class probability per pixel.  The summary line is the driver's.  Needs the MI355X: there is no CPU path."""
+class probability per pixel (--method geo: `geo_mindist`, the smallest geodesic distance over the classes, in its place).  The
+summary line is the driver's.  Needs the MI355X: there is no CPU path."""
 import argparse
 import os
 import sys
@@ -20,6 +22,7 @@ if ROOT not in sys.path:
 
 
 def build_parser():
+    from pacingpseudo_amd.utils.geodesic import add_geo_flags
     from pacingpseudo_amd.utils.random_walker import add_rw_flags
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     src = ap.add_mutually_exclusive_group(required=True)
@@ -30,7 +33,9 @@ def build_parser():
     ap.add_argument('--seed', type=int, default=1, help='seed of the synthetic phantoms')
     ap.add_argument('--num_classes', type=int, default=5, help='classes incl. background; the ignore index is this number')
     ap.add_argument('--out', type=str, required=True, help='output directory')
+    ap.add_argument('--method', choices=('rw', 'geo'), default='rw', help='random walker (--rw_* flags) or geodesic distance (--geo_* flags)')
     add_rw_flags(ap)                               # --rw_beta ... (--rw_scribbles is implied here)
+    add_geo_flags(ap)                              # --geo_lambda ... (--geo_scribbles is implied by --method geo)
     return ap
 
 
@@ -40,8 +45,13 @@ def main(argv=None):
     import torch
     from pacingpseudo_amd.data import NpzSlices, SyntheticPhantoms
     from pacingpseudo_amd.utils.random_walker import check_rw_params, expand_dataset, summarize, summary_line
+    from pacingpseudo_amd.utils.geodesic import check_geo_params, expand_dataset_geo, summarize_geo, summary_line_geo
+    geo = args.method == 'geo'
     try:
-        prm = check_rw_params(args.rw_beta, args.rw_eps, args.rw_tol, args.rw_max_iters, args.rw_threshold, K=args.num_classes)
+        if geo:
+            prm = check_geo_params(args.geo_lambda, args.geo_ratio, args.geo_max_dist, args.geo_max_sweeps, K=args.num_classes)
+        else:
+            prm = check_rw_params(args.rw_beta, args.rw_eps, args.rw_tol, args.rw_max_iters, args.rw_threshold, K=args.num_classes)
     except (ValueError, NotImplementedError) as e:
         ap.error(str(e))
     if args.synthetic:
@@ -54,7 +64,10 @@ def main(argv=None):
         if len(set(names)) != len(names):
             ap.error('--file_list: two slices share a file name; the output directory is flat')
     os.makedirs(args.out, exist_ok=True)
-    maps, rep = expand_dataset(ds, args.num_classes, torch.device('cuda'), prm, keep_maxprob=True)
+    if geo:
+        maps, rep = expand_dataset_geo(ds, args.num_classes, torch.device('cuda'), prm, keep_mindist=True)
+    else:
+        maps, rep = expand_dataset(ds, args.num_classes, torch.device('cuda'), prm, keep_maxprob=True)
     for i, name in enumerate(names):
         if args.synthetic:
             img, lab, scb = ds.raw_arrays(i)
@@ -62,8 +75,14 @@ def main(argv=None):
         else:
             z = np.load(ds.files[i])
             keys, scb = {k: z[k] for k in z.files if k != 'scb'}, z['scb']
-        np.savez(os.path.join(args.out, name), **keys, scb=maps[i].astype(np.asarray(scb).dtype), scb_orig=scb,
-                 rw_maxprob=rep['maxprob'][i])
+        extra = dict(geo_mindist=rep['mindist'][i]) if geo else dict(rw_maxprob=rep['maxprob'][i])
+        np.savez(os.path.join(args.out, name), **keys, scb=maps[i].astype(np.asarray(scb).dtype), scb_orig=scb, **extra)
+    if geo:
+        s = summarize_geo(rep)
+        print(summary_line_geo(s))
+        if s['unconverged']:
+            print(f'warning: {s["unconverged"]} planes stopped at --geo_max_sweeps, first slices: {s["unconverged_slices"][:8]}')
+        return s
     s = summarize(rep)
     print(summary_line(s))
     if s['unconverged']:

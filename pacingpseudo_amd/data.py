@@ -287,3 +287,52 @@ class SyntheticPhantoms(NpzSlices):
     def __getitem__(self, i):
         self._index = int(i)
         return self._sample(*self.raw_arrays(i))
+
+
+class SyntheticVolumes(NpzSlices):
+    """`n` deterministic slices that stack to `n // depth` volumes of `depth` slices each (inference.py --synthetic N --synthetic_depth
+    D): per volume K-1 ellipsoids on noise, a slice is the cross-section at its depth; names[i] = 'vol###_slice###'.  Scribbles as in
+    SyntheticPhantoms: a short stroke inside each structure of the slice."""
+
+    def __init__(self, n, num_classes, depth, size=256, train=False, seed=1, native=True, compact=True):
+        depth = int(depth)
+        if depth < 1 or n < 1 or n % depth != 0:
+            raise ValueError(f'{n} slices do not stack to volumes of {depth} slices: n must be a positive multiple of depth')
+        super().__init__([None] * n, num_classes, size, False, 1.0, train, seed, False, native, compact)
+        self.depth = depth
+        self.base_seed = seed + (0 if train else 10_000)
+        self.names = [f'vol{i // depth:03d}_slice{i % depth:03d}' for i in range(n)]
+
+    def raw_arrays(self, i):
+        v, s = divmod(int(i), self.depth)
+        S, K, D = self.size, self.K, self.depth
+        vol_rng = np.random.default_rng(self.base_seed * 100_003 + 7_919 * v + 1)       # the volume's ellipsoids: the same for all its slices
+        rng = np.random.default_rng(self.base_seed * 100_003 + 104_729 + i)              # the slice's noise and strokes
+        yy, xx = np.mgrid[0:S, 0:S].astype(np.float32)
+        z = (s + 0.5) / D                                                               # depth of the slice in [0, 1]
+        lab = np.zeros((S, S), np.int64)
+        scb = np.full((S, S), K, np.int64)
+        img = rng.normal(0, 0.3, (S, S)).astype(np.float32)
+        for c in range(1, K):
+            cz = vol_rng.uniform(0.3, 0.7)
+            cy, cx = vol_rng.uniform(0.25, 0.75, 2) * S
+            rz = vol_rng.uniform(0.3, 0.6)
+            ry, rx = vol_rng.uniform(0.08, 0.18, 2) * S
+            m = ((z - cz) / rz) ** 2 + ((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 < 1
+            lab[m] = c
+            img[m] += 0.6 + 0.35 * c
+        for c in range(K):
+            ys, xs = np.nonzero(lab == c)
+            if len(ys) == 0:
+                continue
+            j = rng.integers(len(ys))
+            y0, x0 = int(ys[j]), int(xs[j])
+            for t in range(int(0.08 * S)):                           # a short horizontal stroke
+                x = min(S - 1, x0 + t)
+                if lab[y0, x] == c:
+                    scb[y0, x] = c
+        return img, lab, scb
+
+    def __getitem__(self, i):
+        self._index = int(i)
+        return self._sample(*self.raw_arrays(i))

@@ -103,6 +103,38 @@ parser.add_argument('--crf_sigma_rgb', type=float, default=0.1, help='width of i
 parser.add_argument('--crf_sigma_smooth', type=float, default=1.5, help='width of the smoothness kernel, in offsets (an untuned first value)')
 parser.add_argument('--crf_w_bilateral', type=float, default=4.0, help='weight of the bilateral message, in logit units (an untuned first value)')
 parser.add_argument('--crf_w_smooth', type=float, default=1.0, help='weight of the smoothness message, in logit units (an untuned first value)')
+
+
+# volume-wise evaluation (utils/volume.py): beside the per-slice scores, which stay what they are, the slices are
+# stacked per patient volume, filtered in 3-D and scored as volumes
+def _spacing_mm(text):
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'{text!r} is not a number')
+    if not (np.isfinite(value) and value > 0.0):
+        raise argparse.ArgumentTypeError(f'{text!r}: a finite distance in millimetres, > 0')
+    return value
+
+
+parser.add_argument('--volumes', action='store_true', default=False,
+                    help='also score per patient volume: the class maps that leave the --tta / --crf_refine stage are stacked by volume id and '
+                         'slice number (--volume_regex), filtered in 3-D with --keep_largest_cc, and scored with Dice and HD95 in 3-D '
+                         '(and HD, ASSD, NSD with --surface_metrics); eval_data.npz gains vol_ids, vol_slices, vol_dicearr, vol_hd95arr, ...; '
+                         'needs --slice_spacing on real data')
+parser.add_argument('--volume_regex', type=str, default=None, metavar='REGEX',
+                    help='how a slice\'s file name (without directory and extension) splits into the named groups (?P<volume>...) and '
+                         '(?P<slice>digits); default: the trailing run of digits is the slice number, everything before it -- less a '
+                         'separating "_", "-" or "slice" -- the volume id')
+parser.add_argument('--slice_spacing', type=_spacing_mm, default=None, metavar='MM',
+                    help='distance between neighbouring slices in millimetres for --volumes; slice thickness is not in the .npz files, so '
+                         'there is no per-data-set default (with --synthetic: the in-plane spacing)')
+parser.add_argument('--cc_connectivity_3d', type=int, default=1, choices=[1, 2, 3],
+                    help='neighbourhood of the 3-D --keep_largest_cc of --volumes: 1 = 6 neighbours (what the surfaces use), 2 = 18, 3 = 26')
+parser.add_argument('--synthetic_depth', type=int, default=0, metavar='D',
+                    help='with --synthetic N: the phantom slices are cross-sections of N / D volumes of D slices each (ellipsoids), named '
+                         'vol###_slice###; N must be a multiple of D')
+VOLUME_FLAGS = ('volumes', 'volume_regex', 'slice_spacing', 'cc_connectivity_3d', 'synthetic_depth')
 CRF_FLAGS = ('crf_refine', 'crf_radius', 'crf_dilation', 'crf_sigma_xy', 'crf_sigma_rgb', 'crf_sigma_smooth', 'crf_w_bilateral', 'crf_w_smooth')
 
 
@@ -122,6 +154,27 @@ def parse_args(argv=None):
         crf_settings(args)
     except (ValueError, NotImplementedError) as e:
         parser.error(f'--crf_refine / --crf_radius / --crf_dilation / --crf_sigma_* / --crf_w_*: {e}')
+    if args.synthetic_depth < 0:
+        parser.error(f'--synthetic_depth {args.synthetic_depth}: a number of slices per volume, >= 1')
+    if args.synthetic_depth and not args.synthetic:
+        parser.error('--synthetic_depth shapes the phantoms of --synthetic N: pass --synthetic as well')
+    if args.synthetic_depth and args.synthetic % args.synthetic_depth != 0:
+        parser.error(f'--synthetic {args.synthetic} is not a multiple of --synthetic_depth {args.synthetic_depth}: the slices do not stack to whole volumes')
+    if args.volumes:
+        if args.synthetic and not args.synthetic_depth:
+            parser.error('--volumes with --synthetic N needs --synthetic_depth D: the phantoms of --synthetic alone are unrelated slices')
+        if not args.synthetic and args.slice_spacing is None:
+            parser.error('--volumes needs --slice_spacing MM on real data: slice thickness is not in the .npz files, so there is no per-data-set default')
+        if args.volume_regex is not None:
+            from .utils.volume import group_volumes
+            try:
+                group_volumes([], args.volume_regex)
+            except ValueError as e:
+                parser.error(f'--volume_regex: {e}')
+    else:
+        given = [f for f in ('volume_regex', 'slice_spacing') if getattr(args, f)] + (['cc_connectivity_3d'] if args.cc_connectivity_3d != 1 else [])
+        if given:
+            parser.error(f'--{given[0]} belongs to --volumes: pass --volumes as well')
     return args
 
 
@@ -142,7 +195,7 @@ def load_backbone(model, state_dict):
 
 
 def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False, cc_connectivity=1, tta='none', extra=None,
-             surface_metrics=False, nsd_tolerance=2.0, crf=None):
+             surface_metrics=False, nsd_tolerance=2.0, crf=None, volume_maps=None):
     """-> (dicearr, hd95arr), both (slices, classes) float32 with NaN where the reference skips a class.  With keep_largest_cc the
     arg-max is filtered on the device first (utils.postprocess.keep_largest_components) and both metrics score the filtered map;
     then -> (dicearr, hd95arr, ncomp, removed): ncomp (slices, classes) int32 = components per class before filtering, removed
@@ -155,7 +208,9 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
     hd95arr.  With crf = a dict of utils.crf_refine's keyword arguments (iterations, radius, ...) the logits -- with tta the log of
     the mean probabilities, clamped at 1e-30 -- are refined against the image before anything else sees them: the refined
     probabilities and their class map take the place of the logits and their arg-max in the filter and in every metric, and `extra`
-    receives crf_changed: (slices,) int64 = pixels whose class differs from the unrefined arg-max."""
+    receives crf_changed: (slices,) int64 = pixels whose class differs from the unrefined arg-max.  A list passed as `volume_maps`
+    receives one (class map, label) pair of uint8 (H, W) device tensors per slice, in data-set order: the hard map that leaves the
+    tta / crf stage, BEFORE the 2-D filter, for score_volumes; nothing else changes."""
     from .data import expand_compact
     from .utils.metrics import batch_dice_counts, batch_hd95, batch_surface_metrics
     from .utils.postprocess import keep_largest_components
@@ -190,6 +245,9 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
                     crf_rows.extend((crf_cls != before).flatten(1).sum(1).tolist())
             # the first-maximum arg-max the last stage left beside its probabilities; None: logits.argmax(1), taken where it is needed
             argmax = crf_cls if crf is not None else (tta_cls if use_tta else None)
+            if volume_maps is not None:
+                unfiltered = (argmax if argmax is not None else logits.argmax(1)).to(torch.uint8)
+                volume_maps.extend(zip(unfiltered.unbind(0), label.argmax(1).to(torch.uint8).unbind(0)))
             if keep_largest_cc:
                 raw = argmax if argmax is not None else logits.argmax(1)
                 pred, stats = keep_largest_components(raw, num_classes, cc_connectivity, return_stats=True)
@@ -226,6 +284,62 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
     return np.array(dice_rows, np.float32), np.array(hd_rows, np.float32)
 
 
+def score_volumes(volume_maps, groups, num_classes, spacing, keep_largest_cc=False, connectivity=1, surface_metrics=False,
+                  nsd_tolerance=2.0):
+    """The per-volume half of --volumes.  volume_maps: evaluate's list of (class map, label) per slice; groups: utils.group_volumes'
+    {volume id: slice indices in slice order}; spacing (sz, sy, sx) in mm.  Per volume the slices are stacked on the device, filtered
+    in 3-D (keep_largest_cc) and scored.  -> dict of the vol_* arrays of eval_data.npz: vol_ids, vol_slices, vol_dicearr, vol_hd95arr
+    (volumes, K) float32 with NaN as in the slice arrays; with surface_metrics vol_hdarr, vol_assdarr, vol_nsdarr; with
+    keep_largest_cc vol_ncomp, vol_removed (volumes, K) int32 = components per class before filtering, voxels set to background."""
+    from .utils.volume import keep_largest_components_3d, volume_dice, volume_surface_metrics
+    rows = {'dice': [], 'hdp': [], 'hd': [], 'assd': [], 'nsd': [], 'ncomp': [], 'removed': []}
+    out = {}
+    for vid, idx in groups.items():
+        shapes = {tuple(volume_maps[i][0].shape) for i in idx}
+        if len(shapes) != 1:
+            raise ValueError(f'volume {vid!r}: its {len(idx)} slices have different shapes {sorted(shapes)}; they do not stack')
+        raw = torch.stack([volume_maps[i][0] for i in idx])
+        lab = torch.stack([volume_maps[i][1] for i in idx])
+        pred = raw.to(torch.int64)
+        if keep_largest_cc:
+            pred, stats = keep_largest_components_3d(pred, num_classes, connectivity, return_stats=True)
+            stats = stats.cpu().numpy()
+            rows['ncomp'].append(stats[:, 0])
+            rows['removed'].append(stats[:, 1])
+        rows['dice'].append(volume_dice(pred, lab, num_classes))
+        sm = volume_surface_metrics(pred, lab, num_classes, spacing, tolerance=nsd_tolerance)
+        for key in ('hdp', 'hd', 'assd', 'nsd'):
+            rows[key].append(sm[key])
+    out['vol_ids'] = np.array(list(groups))
+    out['vol_slices'] = np.array([len(idx) for idx in groups.values()], np.int64)
+    out['vol_dicearr'] = np.array(rows['dice'], np.float32).reshape(-1, num_classes)
+    out['vol_hd95arr'] = np.array(rows['hdp'], np.float32).reshape(-1, num_classes)
+    if surface_metrics:
+        for key in ('hd', 'assd', 'nsd'):
+            out[f'vol_{key}arr'] = np.array(rows[key], np.float32).reshape(-1, num_classes)
+    if keep_largest_cc:
+        out['vol_ncomp'] = np.array(rows['ncomp'], np.int32).reshape(-1, num_classes)
+        out['vol_removed'] = np.array(rows['removed'], np.int32).reshape(-1, num_classes)
+    return out
+
+
+def _foreground_mean(arr, num_classes):
+    """The slice line's rule on any (items, classes) array: per class the mean of its values that are not NaN (0 for a class without
+    one: AvgMeter.avg of an empty meter), then the mean over the foreground classes."""
+    means = []
+    for cls in range(1, num_classes):
+        col = arr[:, cls]
+        col = col[~np.isnan(col)]
+        means.append(float(np.mean(col.astype(np.float64))) if col.size else 0.0)
+    return np.mean(means)
+
+
+def _volume_scores(args, volume_maps, groups, num_classes, spacing):
+    return score_volumes(volume_maps, groups, num_classes, spacing, keep_largest_cc=args.keep_largest_cc,
+                         connectivity=args.cc_connectivity_3d, surface_metrics=getattr(args, 'surface_metrics', False),
+                         nsd_tolerance=args.nsd_tolerance)
+
+
 def main_interface(args):
     from .data import NpzSlices, SyntheticPhantoms, collate_by_shape, loader_context
     from .models import UNet
@@ -240,7 +354,11 @@ def main_interface(args):
     model = UNet(input_ch=args.input_ch, init_ch=args.init_ch, max_ch=args.max_ch, num_classes=num_classes,
                  output_stride=args.output_stride, is_stride_conv=args.is_stride_conv, is_trans_conv=args.is_trans_conv,
                  elab_end_points=args.elab_end_points, **norm_kwargs(args)).to(device)
-    if args.synthetic:
+    volumes = getattr(args, 'volumes', False)
+    if args.synthetic and getattr(args, 'synthetic_depth', 0):
+        from .data import SyntheticVolumes
+        test_dataset = SyntheticVolumes(args.synthetic, num_classes, args.synthetic_depth, size=size, train=False, seed=args.seed)
+    elif args.synthetic:
         test_dataset = SyntheticPhantoms(args.synthetic, num_classes, size=size, train=False, seed=args.seed, native=True, compact=True)
     else:
         test_dataset = NpzSlices(args.test_ls, num_classes, size=size, train=False, seed=args.seed, native=True, compact=True)
@@ -254,15 +372,25 @@ def main_interface(args):
     surface = dict(surface_metrics=True, nsd_tolerance=args.nsd_tolerance) if getattr(args, 'surface_metrics', False) else {}
     crf = crf_settings(args)
     refine = dict(crf=crf) if crf is not None else {}      # without the flag the evaluate call is the parent's
+    if volumes:                                            # the grouping first: a file name that does not fit fails before the model runs
+        from .utils.volume import group_volumes
+        names = test_dataset.names if args.synthetic else [os.path.splitext(os.path.basename(f))[0] for f in args.test_ls]
+        groups = group_volumes(names, args.volume_regex)
+        slice_spacing = args.slice_spacing if args.slice_spacing is not None else spacing[0]
+        volume_maps = []
+        refine['volume_maps'] = volume_maps
+        logging.info('Volumes: {} of {} slices, spacing (z, y, x) = {} mm'.format(len(groups), len(names), (slice_spacing,) + tuple(spacing)))
     if args.keep_largest_cc:
         dicearr, hd95arr, ncomp, removed = evaluate(model, loader, num_classes, spacing, device, True, args.cc_connectivity, tta, extra, **surface,
                                                     **refine)
-        np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, ncomp=ncomp, removed=removed, **extra)
+        vol = _volume_scores(args, volume_maps, groups, num_classes, (slice_spacing,) + tuple(spacing)) if volumes else {}
+        np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, ncomp=ncomp, removed=removed, **extra, **vol)
         logging.info('Largest-component filter (connectivity {}): {} pixels set to background, {} of {} slices changed'.format(
             args.cc_connectivity, int(removed.sum()), int((removed > 0).sum()), len(removed)))
     else:
         dicearr, hd95arr = evaluate(model, loader, num_classes, spacing, device, tta=tta, extra=extra, **surface, **refine)
-        np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, **extra)
+        vol = _volume_scores(args, volume_maps, groups, num_classes, (slice_spacing,) + tuple(spacing)) if volumes else {}
+        np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, **extra, **vol)
     if tta != 'none':
         from .utils.tta import tta_ops
         changed = extra['tta_changed']
@@ -296,6 +424,17 @@ def main_interface(args):
             means.append(np.mean([meters[_].avg for _ in range(1, num_classes)]))
         logging.info('Fold {}, overall HD: {:.2f}, overall ASSD: {:.2f}, overall NSD at {:g} mm: {:.4f}'.format(
             args.fold, means[0], means[1], args.nsd_tolerance, means[2]))
+    if volumes:
+        line = 'Fold {}, overall volume Dice: {:.4f}, overall volume HD95: {:.2f}'.format(
+            args.fold, _foreground_mean(vol['vol_dicearr'], num_classes), _foreground_mean(vol['vol_hd95arr'], num_classes))
+        if surface:
+            line += ', overall volume HD: {:.2f}, overall volume ASSD: {:.2f}, overall volume NSD at {:g} mm: {:.4f}'.format(
+                _foreground_mean(vol['vol_hdarr'], num_classes), _foreground_mean(vol['vol_assdarr'], num_classes), args.nsd_tolerance,
+                _foreground_mean(vol['vol_nsdarr'], num_classes))
+        logging.info(line)
+        if args.keep_largest_cc:
+            logging.info('Largest-component filter in 3-D (connectivity {}): {} voxels set to background in {} volumes'.format(
+                args.cc_connectivity_3d, int(vol['vol_removed'].sum()), len(groups)))
     logging.info('Shape of the Dice array: {}'.format(dicearr.shape))
     logging.info('Shape of the HD95 array: {}'.format(hd95arr.shape))
     return dicearr, hd95arr
@@ -334,7 +473,8 @@ def main(argv=None):
     log.addHandler(logging.StreamHandler(sys.stdout))
     # without --surface_metrics the log is what it was before the flag existed: its two entries are left out of the dump
     shown = [(k, v) for k, v in args._get_kwargs() if (args.surface_metrics or k not in ('surface_metrics', 'nsd_tolerance'))
-             and (args.crf_refine or k not in CRF_FLAGS)]        # the same for --crf_refine and its eight entries
+             and (args.crf_refine or k not in CRF_FLAGS)         # the same for --crf_refine and its eight entries
+             and (args.volumes or args.synthetic_depth or k not in VOLUME_FLAGS)]      # ... and for --volumes and its companions
     logging.info(''.join(f'{k}={v}\n' for k, v in shown))
     if not args.synthetic:
         from .train import split_dir                              # the same table the trainers read their fold lists from

@@ -8,3 +8,5 @@ from .random_walker import SharedMaps, check_rw_prior_params, random_walker_prio
 from .uncertainty import add_noise, check_uncertainty_params, uncertainty_mask, uncertainty_threshold  # noqa: F401
 from .distance import distance_transform_edt, signed_distance_maps  # noqa: F401
 from .geodesic import check_geo_params, expand_dataset_geo, geodesic_distance, geodesic_expand_scribbles  # noqa: F401
+from .volume import (distance_transform_edt_3d, group_volumes, keep_largest_components_3d, label_components_3d, volume_dice,  # noqa: F401
+                     volume_surface_metrics)

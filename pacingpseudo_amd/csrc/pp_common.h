@@ -315,7 +315,9 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 #define H_LD 72            // halves per LDS row: 32 hi + 32 lo + 8 pad (144 B: ds_read_b128 conflict-free as for fp32)
 #define F16_LO_SCALE 2048.f
 
-// power-of-two scale that brings `amax` into [2^9, 2^10) (1 when amax is 0 / not finite)
+// power-of-two scale that brings `amax` into [2^9, 2^10) (1 when amax is 0 / not finite).  The exponent is clamped as in ps_scales
+// (pp_wino.hip): below 2^-117 the scale 2^(10 - e) is no fp32 number (inf, and every staged value inf or NaN); a maximum below
+// 2^-100 is staged as far below 2^10 as it lies below 2^-100 and loses fp16 bits instead (docs/operand_range.md).
 __device__ __forceinline__ void f16_scales(const float* amax, float& s_in, float& s_out) {
   s_in = 1.f; s_out = 1.f;
   if (amax) {
@@ -323,6 +325,7 @@ __device__ __forceinline__ void f16_scales(const float* amax, float& s_in, float
     if (m > 0.f && m < 3.0e38f) {
       int e;
       (void)frexpf(m, &e);                       // m = f * 2^e, f in [0.5, 1)
+      e = e < -100 ? -100 : (e > 100 ? 100 : e);
       s_in = ldexpf(1.f, 10 - e);
       s_out = ldexpf(1.f, e - 10);
     }

@@ -24,13 +24,17 @@ result turns it into NaN and fails the float64 comparison, a write outside an ou
 engine allocates for it) and starts as 0xFF, so a query that is too small, a kernel that writes a few bytes past it and a kernel
 that relies on what an earlier layer left in the workspace all show.  The run's entry-point table (_Checked) holds every device
 pointer of a launch to this: one that points into no banded buffer of the run is a failing result line.
+The operands have one magnitude per kind (Profile: the default, CENSUS); tests/test_gpu_operand_range.py runs the same adapters at
+others.
 A recorded launch without a replay adapter fails the census by name.  Outside the census: the stand-alone AuxPath.forward (it calls
 the library directly, not through a plan) and --precision fp16 (fp16-grade by design, tested on its own).
 """
+import contextlib
 import ctypes
 import math
 import zlib
 from collections import defaultdict
+from typing import NamedTuple, Optional
 
 import pytest
 import torch
@@ -69,14 +73,81 @@ def census():
 
 
 # ------------------------------------------------------------------------------------------------------------------ operands
+class Profile(NamedTuple):
+    """Magnitudes of the operands of a replay.  The default is the point the censuses run at; tests/test_gpu_operand_range.py
+    moves it (`with operands(profile):` around a replay)."""
+    act: float = 1.0                # activations (forward input, the weight gradient's x) times this
+    weight: float = 1.0             # weights times this
+    grad: Optional[float] = None    # scale of the gradient operand dz; None: G_FP32 / G_16 by storage
+    unit: bool = False              # |dz| = 2^-4u, u uniform in [0, 1), random sign, instead of randn: no element far below the largest
+    peak: Optional[float] = None    # dz rescaled (in float64, rounded once) so that max |dz| is this
+    spread: int = 0                 # output channel c of dz times 2^(-spread * c / (O - 1))
+    balance: bool = False           # ... and output channel c of the weights times the inverse, so every channel contributes alike
+    pow2: int = 0                   # dz times 2^pow2 AFTER it was rounded to the storage type (exact while nothing leaves the normal range)
+    zero: bool = False              # dz == 0
+    amax: Optional[float] = None    # the max |dz| cell the launch is handed; None: the true maximum of dz
+
+
+CENSUS = Profile()
+_PROFILE = [CENSUS]
+
+
+@contextlib.contextmanager
+def operands(profile):
+    prev, _PROFILE[0] = _PROFILE[0], profile
+    try:
+        yield
+    finally:
+        _PROFILE[0] = prev
+
+
 class _Ops:
     """Seeded operands of one replay; activation-type tensors are rounded to the key's storage type (identical for the 16-bit
-    entry and its fp32 twin)."""
+    entry and its fp32 twin).  Their magnitudes are the current Profile's."""
 
     def __init__(self, key):
         self.storage = key[0]
         self.g = torch.Generator().manual_seed(zlib.crc32(repr(key[1:]).encode()))
-        self.gs = G_FP32 if self.storage == 'fp32' else G_16
+        self.prof = _PROFILE[0]
+        self.gs = (G_FP32 if self.storage == 'fp32' else G_16) if self.prof.grad is None else self.prof.grad
+
+    def _chan(self, O_):
+        """per-output-channel factors 2^(-spread * c / (O - 1))"""
+        return torch.pow(2.0, -self.prof.spread * torch.arange(O_, dtype=torch.float64) / max(O_ - 1, 1))
+
+    def grad(self, B, H, W, ld, O_):
+        """The gradient operand dz of a 3x3 launch (NHWC, row length ld, O_ channels); the census profile: act(..., self.gs)."""
+        p = self.prof
+        if p.unit:
+            v = torch.pow(2.0, -4.0 * torch.rand(B, H, W, O_, generator=self.g)) * self.gs
+            v = torch.where(torch.rand(B, H, W, O_, generator=self.g) < 0.5, -v, v)
+        else:
+            v = self.randn(B, H, W, O_, scale=self.gs)
+        if p.spread:
+            v = (v.double() * self._chan(O_)).float()
+        if p.peak is not None:
+            v = (v.double() * (p.peak / float(v.abs().max()))).float()
+        v = self.r(v)
+        if p.zero:
+            v = torch.zeros_like(v)
+        if p.pow2:
+            v = v * 2.0 ** p.pow2
+        t = torch.full((B, H, W, ld), 5.0)
+        t[..., :O_] = v
+        return t
+
+    def weights(self, O_, I):
+        """(O_, I, 3, 3) weights of a 3x3 launch"""
+        w = self.randn(O_, I, 3, 3, scale=1 / math.sqrt(9 * I))
+        if self.prof.weight != 1.0:
+            w = w * self.prof.weight
+        if self.prof.balance and self.prof.spread:
+            w = (w.double() / self._chan(O_).view(-1, 1, 1, 1)).float()
+        return w
+
+    def cell(self, dz):
+        """the max |dz| cell of a split-fp16 gradient launch: the true maximum of the operand, or the profile's value"""
+        return _amax(dz) if self.prof.amax is None else _b(torch.tensor([self.prof.amax], dtype=torch.float32))
 
     def r(self, t):
         return t if self.storage == 'fp32' else t.to(MANT[self.storage][2]).float()
@@ -259,7 +330,7 @@ def _pack_wino(w, O_, I, tile, f16, K=None):
 def _conv_in(ops, lz, run, ld, C, B, H, W, scale=1.0):
     """The input of a launch: plain, or lazy (lz = ('lazy', ld, groups): raw z + coefficient rows): (device tensor, lazy struct or
     None, fp64 NCHW value the convolution sees, materialised-y tensor for the bit-identity check or None)."""
-    x = ops.act(B, H, W, ld, C, scale)
+    x = ops.act(B, H, W, ld, C, scale * ops.prof.act)
     if lz is None:
         return run.d(x), None, _n64(x, C) if run.want_ref else None, None
     from pacingpseudo_amd._lib import PpLazyIn
@@ -283,7 +354,7 @@ def _direct_fwd(key, run):
     _, ld_in, C, _, bias, _, ld_out, N, B, H, W, dil, acc = a[:13]
     ops = _Ops(key)
     x, _, x64, _ = _conv_in(ops, None, run, ld_in, C, B, H, W)
-    w = _b(ops.randn(N, C, 3, 3, scale=1 / math.sqrt(9 * C)))
+    w = _b(ops.weights(N, C))
     b = _b(ops.randn(N))
     prior = ops.r(ops.randn(B, H, W, N)) if acc else None
     wf, _ = _pack_direct(w, N, C, f16)
@@ -312,7 +383,7 @@ def _wino_fwd(key, run):
     lib = _L()
     ops = _Ops(key)
     x, _, x64, _ = _conv_in(ops, None, run, ld_in, C, B, H, W)
-    w = _b(ops.randn(N, C, 3, 3, scale=1 / math.sqrt(9 * C)))
+    w = _b(ops.weights(N, C))
     b = _b(ops.randn(N))
     prior = ops.r(ops.randn(B, H, W, N)) if acc else None
     U, _ = _pack_wino(w, N, C, lib.pp_conv3x3_wino_tile(H, W, dil), f16, run.K)
@@ -343,7 +414,7 @@ def _bn_fwd(key, run):
     ops = _Ops(key)
     x, lz, x64, ymat = _conv_in(ops, a[-2] if name.endswith('_lazy') else None, run, ld_in, C, B, H, W)
     stats_ptr = a[21] if wino else a[19]
-    w = _b(ops.randn(N, C, 3, 3, scale=1 / math.sqrt(9 * C)))
+    w = _b(ops.weights(N, C))
     b = _b(ops.randn(N))
     sc = _b((torch.rand(N, generator=ops.g) + 0.5))
     sh = _b(ops.randn(N))
@@ -407,11 +478,11 @@ def _bwd_data(key, run):
     wino, f16 = 'wino' in name, name.endswith('_f16x3')
     _, ld_dz, O_, _, _, ld_dx, I, B, H, W, dil, acc = a[:12]
     ops = _Ops(key)
-    dz = run.d(ops.act(B, H, W, ld_dz, O_, ops.gs))
-    w = _b(ops.randn(O_, I, 3, 3, scale=1 / math.sqrt(9 * I)))
+    dz = run.d(ops.grad(B, H, W, ld_dz, O_))
+    w = _b(ops.weights(O_, I))
     prior = ops.r(ops.randn(B, H, W, I, scale=ops.gs)) if acc else None
     dx = run.out(B, H, W, ld_dx, I, prior)
-    am = _amax(dz[..., :O_]) if (f16 and a[-2]) else None
+    am = ops.cell(dz[..., :O_]) if (f16 and a[-2]) else None
     lib = _L()
     if wino:
         _, Ub = _pack_wino(w, O_, I, lib.pp_conv3x3_wino_tile(H, W, dil), f16, run.K)
@@ -452,14 +523,14 @@ def _bwd_weight(key, run):
         _, ld_dz, O_, _, ld_x, Cpad, I, B, H, W, dil, _, acc = a[:13]
         vcached = None
     ops = _Ops(key)
-    dz = run.d(ops.act(B, H, W, ld_dz, O_, ops.gs))
+    dz = run.d(ops.grad(B, H, W, ld_dz, O_))
     x, lz, x64, ymat = _conv_in(ops, a[-2] if name.endswith('_lazy') else None, run, ld_x, Cpad, B, H, W)
     if Cpad > I:            # the padded input channels of the first layer hold zeros
         x[..., I:Cpad] = 0
         if x64 is not None:
             x64[:, I:] = 0
     prior = ops.randn(O_, I, 3, 3) * ops.gs if acc else None
-    am = _amax(dz[..., :O_]) if (f16 and a[-3 if name.endswith('_lazy') else -2]) else None
+    am = ops.cell(dz[..., :O_]) if (f16 and a[-3 if name.endswith('_lazy') else -2]) else None
     outs = []
     for src, lzs in ((x, lz),) + (((ymat, None),) if lz is not None else ()):
         dw = _b(prior.clone() if acc else torch.full((O_, I, 3, 3), 5.0))

@@ -134,6 +134,24 @@ parser.add_argument('--cc_connectivity_3d', type=int, default=1, choices=[1, 2, 
 parser.add_argument('--synthetic_depth', type=int, default=0, metavar='D',
                     help='with --synthetic N: the phantom slices are cross-sections of N / D volumes of D slices each (ellipsoids), named '
                          'vol###_slice###; N must be a multiple of D')
+# a size threshold and hole filling around --keep_largest_cc (utils/morphology.py): threshold -> keep-largest -> fill
+parser.add_argument('--min_component_size', type=int, default=0, metavar='P',
+                    help='post-process the arg-max on the device before scoring: components of a foreground class with fewer than P pixels '
+                         'of their slice become background (0 = off; neighbourhood: --cc_connectivity); runs before --keep_largest_cc; '
+                         'eval_data.npz gains small_removed')
+parser.add_argument('--fill_holes', action='store_true', default=False,
+                    help='post-process the arg-max on the device before scoring: a background region of a slice that does not reach the '
+                         'slice border and touches one single class takes that class (one that touches several classes is left); runs '
+                         'after --keep_largest_cc; eval_data.npz gains holes_filled and holes_mixed; with --volumes the stacked maps are '
+                         'filled in 3-D')
+parser.add_argument('--fill_holes_connectivity', type=int, default=1, choices=[1, 2],
+                    help='neighbourhood of --fill_holes: 1 = 4-neighbourhood (scipy.ndimage.binary_fill_holes\' default), 2 = 8-neighbourhood')
+parser.add_argument('--min_component_size_3d', type=int, default=0, metavar='V',
+                    help='with --volumes: 3-D components of a foreground class with fewer than V voxels become background before the 3-D '
+                         '--keep_largest_cc (0 = off; neighbourhood: --cc_connectivity_3d); eval_data.npz gains vol_small_removed')
+parser.add_argument('--fill_holes_connectivity_3d', type=int, default=1, choices=[1, 2, 3],
+                    help='neighbourhood of the 3-D --fill_holes of --volumes: 1 = 6 neighbours, 2 = 18, 3 = 26')
+MORPH_FLAGS = ('min_component_size', 'fill_holes', 'fill_holes_connectivity', 'min_component_size_3d', 'fill_holes_connectivity_3d')
 VOLUME_FLAGS = ('volumes', 'volume_regex', 'slice_spacing', 'cc_connectivity_3d', 'synthetic_depth')
 CRF_FLAGS = ('crf_refine', 'crf_radius', 'crf_dilation', 'crf_sigma_xy', 'crf_sigma_rgb', 'crf_sigma_smooth', 'crf_w_bilateral', 'crf_w_smooth')
 
@@ -147,6 +165,19 @@ def crf_settings(args):
                                    args.crf_sigma_smooth, args.crf_w_bilateral, args.crf_w_smooth)
 
 
+def morph_settings(args):
+    """The checked values of MORPH_FLAGS as utils.morphology.check_morph_params returns them (ValueError otherwise)."""
+    from .utils.morphology import check_morph_params
+    return check_morph_params(getattr(args, 'min_component_size', 0), getattr(args, 'fill_holes', False),
+                              getattr(args, 'fill_holes_connectivity', 1), getattr(args, 'min_component_size_3d', 0),
+                              getattr(args, 'fill_holes_connectivity_3d', 1), volumes=getattr(args, 'volumes', False))
+
+
+def morph_used(args):
+    """Whether any of MORPH_FLAGS differs from its default: only then do they show in the log's argument dump."""
+    return any(getattr(args, f, parser.get_default(f)) != parser.get_default(f) for f in MORPH_FLAGS)
+
+
 def parse_args(argv=None):
     """parser.parse_args plus the checks that span several flags (argparse errors: exit status 2), before anything is built."""
     args = parser.parse_args(argv)
@@ -154,6 +185,14 @@ def parse_args(argv=None):
         crf_settings(args)
     except (ValueError, NotImplementedError) as e:
         parser.error(f'--crf_refine / --crf_radius / --crf_dilation / --crf_sigma_* / --crf_w_*: {e}')
+    try:
+        morph_settings(args)
+    except ValueError as e:
+        parser.error(str(e))
+    if args.fill_holes_connectivity != 1 and not args.fill_holes:
+        parser.error('--fill_holes_connectivity belongs to --fill_holes: pass --fill_holes as well')
+    if args.fill_holes_connectivity_3d != 1 and not args.fill_holes:
+        parser.error('--fill_holes_connectivity_3d belongs to --fill_holes: pass --fill_holes as well')
     if args.synthetic_depth < 0:
         parser.error(f'--synthetic_depth {args.synthetic_depth}: a number of slices per volume, >= 1')
     if args.synthetic_depth and not args.synthetic:
@@ -195,7 +234,8 @@ def load_backbone(model, state_dict):
 
 
 def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False, cc_connectivity=1, tta='none', extra=None,
-             surface_metrics=False, nsd_tolerance=2.0, crf=None, volume_maps=None):
+             surface_metrics=False, nsd_tolerance=2.0, crf=None, volume_maps=None, min_component_size=0, fill_holes=False,
+             fill_holes_connectivity=1):
     """-> (dicearr, hd95arr), both (slices, classes) float32 with NaN where the reference skips a class.  With keep_largest_cc the
     arg-max is filtered on the device first (utils.postprocess.keep_largest_components) and both metrics score the filtered map;
     then -> (dicearr, hd95arr, ncomp, removed): ncomp (slices, classes) int32 = components per class before filtering, removed
@@ -210,12 +250,23 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
     probabilities and their class map take the place of the logits and their arg-max in the filter and in every metric, and `extra`
     receives crf_changed: (slices,) int64 = pixels whose class differs from the unrefined arg-max.  A list passed as `volume_maps`
     receives one (class map, label) pair of uint8 (H, W) device tensors per slice, in data-set order: the hard map that leaves the
-    tta / crf stage, BEFORE the 2-D filter, for score_volumes; nothing else changes."""
+    tta / crf stage, BEFORE the 2-D filter, for score_volumes; nothing else changes.  With min_component_size = P > 0 the
+    components of a foreground class with fewer than P pixels become background (utils.morphology.remove_small_components,
+    cc_connectivity) BEFORE the keep-largest filter, with fill_holes the cavities of one class are closed
+    (utils.morphology.fill_holes, fill_holes_connectivity) AFTER it -- threshold, keep-largest, fill -- and every metric scores the
+    result.  `removed` stays what the keep-largest stage alone set to background, the number of returned values depends on
+    keep_largest_cc alone, and `extra` receives small_removed and holes_filled, (slices, classes) int32 pixel counts, and
+    holes_mixed (slices,) int32 = cavities left because they touch several classes."""
     from .data import expand_compact
     from .utils.metrics import batch_dice_counts, batch_hd95, batch_surface_metrics
     from .utils.postprocess import keep_largest_components
     from .utils.tta import tta_ops, tta_predict
     use_tta = len(tta_ops(tta)) > 1
+    do_small, do_fill = min_component_size > 0, bool(fill_holes)
+    if do_small or do_fill:
+        from .utils.morphology import fill_holes as fill_holes_2d
+        from .utils.morphology import remove_small_components
+    small_rows, filled_rows, mixed_rows = [], [], []
     if crf is not None:
         from .utils.crf_refine import check_crf_refine_params, crf_refine
         crf = check_crf_refine_params(**crf)
@@ -248,11 +299,21 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
             if volume_maps is not None:
                 unfiltered = (argmax if argmax is not None else logits.argmax(1)).to(torch.uint8)
                 volume_maps.extend(zip(unfiltered.unbind(0), label.argmax(1).to(torch.uint8).unbind(0)))
-            if keep_largest_cc:
+            filtered = keep_largest_cc or do_small or do_fill
+            if filtered:
                 raw = argmax if argmax is not None else logits.argmax(1)
-                pred, stats = keep_largest_components(raw, num_classes, cc_connectivity, return_stats=True)
-                ncomp_rows.extend(stats[..., 0].tolist())
-                removed_rows.extend((pred != raw).flatten(1).sum(1).tolist())
+                if do_small:                                               # threshold -> keep-largest -> fill
+                    raw, stats = remove_small_components(raw, num_classes, min_component_size, cc_connectivity, return_stats=True)
+                    small_rows.extend(stats[..., 1].tolist())
+                pred = raw
+                if keep_largest_cc:
+                    pred, stats = keep_largest_components(raw, num_classes, cc_connectivity, return_stats=True)
+                    ncomp_rows.extend(stats[..., 0].tolist())
+                    removed_rows.extend((pred != raw).flatten(1).sum(1).tolist())
+                if do_fill:
+                    pred, stats = fill_holes_2d(pred, num_classes, fill_holes_connectivity, return_stats=True)
+                    filled_rows.extend(stats[..., 1].tolist())
+                    mixed_rows.extend(stats[:, 0, 0].tolist())
                 # the counting kernel takes an arg-max itself: the arg-max of a one-hot map is the map, exactly
                 scores = torch.nn.functional.one_hot(pred, num_classes).permute(0, 3, 1, 2)
             else:
@@ -263,7 +324,7 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
                 dice = 2.0 * inter / np.maximum(ps + ts, 1e-8)             # inference.py:211-213 (no smoothing term here)
             dice[(ps == 0) & (ts == 0)] = np.nan                           # :208-209
             dice_rows.extend(dice.tolist())
-            hard = pred if keep_largest_cc else (argmax if argmax is not None else logits.argmax(1))
+            hard = pred if filtered else (argmax if argmax is not None else logits.argmax(1))
             if surface_metrics:
                 sm = batch_surface_metrics(hard, label.argmax(1), num_classes, spacing, tolerance=nsd_tolerance)
                 hd_rows.extend(sm['hdp'].tolist())
@@ -278,6 +339,11 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
     if surface_metrics and extra is not None:
         for key, rows in surf_rows.items():
             extra[key + 'arr'] = np.array(rows, np.float32).reshape(-1, num_classes)
+    if do_small and extra is not None:
+        extra['small_removed'] = np.array(small_rows, np.int32).reshape(-1, num_classes)
+    if do_fill and extra is not None:
+        extra['holes_filled'] = np.array(filled_rows, np.int32).reshape(-1, num_classes)
+        extra['holes_mixed'] = np.array(mixed_rows, np.int32)
     if keep_largest_cc:
         return (np.array(dice_rows, np.float32), np.array(hd_rows, np.float32),
                 np.array(ncomp_rows, np.int32).reshape(-1, num_classes), np.array(removed_rows, np.int64))
@@ -285,14 +351,19 @@ def evaluate(model, loader, num_classes, spacing, device, keep_largest_cc=False,
 
 
 def score_volumes(volume_maps, groups, num_classes, spacing, keep_largest_cc=False, connectivity=1, surface_metrics=False,
-                  nsd_tolerance=2.0):
+                  nsd_tolerance=2.0, min_component_size=0, fill_holes=False, fill_holes_connectivity=1):
     """The per-volume half of --volumes.  volume_maps: evaluate's list of (class map, label) per slice; groups: utils.group_volumes'
     {volume id: slice indices in slice order}; spacing (sz, sy, sx) in mm.  Per volume the slices are stacked on the device, filtered
     in 3-D (keep_largest_cc) and scored.  -> dict of the vol_* arrays of eval_data.npz: vol_ids, vol_slices, vol_dicearr, vol_hd95arr
     (volumes, K) float32 with NaN as in the slice arrays; with surface_metrics vol_hdarr, vol_assdarr, vol_nsdarr; with
-    keep_largest_cc vol_ncomp, vol_removed (volumes, K) int32 = components per class before filtering, voxels set to background."""
+    keep_largest_cc vol_ncomp, vol_removed (volumes, K) int32 = components per class before filtering, voxels set to background.
+    With min_component_size = V > 0 the 3-D components of a foreground class with fewer than V voxels go first (connectivity), with
+    fill_holes the 3-D cavities of one class are closed last (fill_holes_connectivity): vol_small_removed, vol_holes_filled
+    (volumes, K) int32 voxel counts and vol_holes_mixed (volumes,) int32 = cavities left because they touch several classes."""
     from .utils.volume import keep_largest_components_3d, volume_dice, volume_surface_metrics
-    rows = {'dice': [], 'hdp': [], 'hd': [], 'assd': [], 'nsd': [], 'ncomp': [], 'removed': []}
+    rows = {'dice': [], 'hdp': [], 'hd': [], 'assd': [], 'nsd': [], 'ncomp': [], 'removed': [], 'small': [], 'filled': [], 'mixed': []}
+    if min_component_size > 0 or fill_holes:
+        from .utils.morphology import fill_holes_3d, remove_small_components_3d
     out = {}
     for vid, idx in groups.items():
         shapes = {tuple(volume_maps[i][0].shape) for i in idx}
@@ -301,11 +372,19 @@ def score_volumes(volume_maps, groups, num_classes, spacing, keep_largest_cc=Fal
         raw = torch.stack([volume_maps[i][0] for i in idx])
         lab = torch.stack([volume_maps[i][1] for i in idx])
         pred = raw.to(torch.int64)
+        if min_component_size > 0:                                        # threshold -> keep-largest -> fill, as in evaluate
+            pred, stats = remove_small_components_3d(pred, num_classes, min_component_size, connectivity, return_stats=True)
+            rows['small'].append(stats[:, 1].cpu().numpy())
         if keep_largest_cc:
             pred, stats = keep_largest_components_3d(pred, num_classes, connectivity, return_stats=True)
             stats = stats.cpu().numpy()
             rows['ncomp'].append(stats[:, 0])
             rows['removed'].append(stats[:, 1])
+        if fill_holes:
+            pred, stats = fill_holes_3d(pred, num_classes, fill_holes_connectivity, return_stats=True)
+            stats = stats.cpu().numpy()
+            rows['filled'].append(stats[:, 1])
+            rows['mixed'].append(stats[0, 0])
         rows['dice'].append(volume_dice(pred, lab, num_classes))
         sm = volume_surface_metrics(pred, lab, num_classes, spacing, tolerance=nsd_tolerance)
         for key in ('hdp', 'hd', 'assd', 'nsd'):
@@ -320,6 +399,11 @@ def score_volumes(volume_maps, groups, num_classes, spacing, keep_largest_cc=Fal
     if keep_largest_cc:
         out['vol_ncomp'] = np.array(rows['ncomp'], np.int32).reshape(-1, num_classes)
         out['vol_removed'] = np.array(rows['removed'], np.int32).reshape(-1, num_classes)
+    if min_component_size > 0:
+        out['vol_small_removed'] = np.array(rows['small'], np.int32).reshape(-1, num_classes)
+    if fill_holes:
+        out['vol_holes_filled'] = np.array(rows['filled'], np.int32).reshape(-1, num_classes)
+        out['vol_holes_mixed'] = np.array(rows['mixed'], np.int32)
     return out
 
 
@@ -335,9 +419,15 @@ def _foreground_mean(arr, num_classes):
 
 
 def _volume_scores(args, volume_maps, groups, num_classes, spacing):
+    m = morph_settings(args)
+    morph = {}                                             # without the flags the score_volumes call is the parent's
+    if m['min_component_size_3d']:
+        morph['min_component_size'] = m['min_component_size_3d']
+    if m['fill_holes']:
+        morph.update(fill_holes=True, fill_holes_connectivity=m['fill_holes_connectivity_3d'])
     return score_volumes(volume_maps, groups, num_classes, spacing, keep_largest_cc=args.keep_largest_cc,
                          connectivity=args.cc_connectivity_3d, surface_metrics=getattr(args, 'surface_metrics', False),
-                         nsd_tolerance=args.nsd_tolerance)
+                         nsd_tolerance=args.nsd_tolerance, **morph)
 
 
 def main_interface(args):
@@ -372,6 +462,11 @@ def main_interface(args):
     surface = dict(surface_metrics=True, nsd_tolerance=args.nsd_tolerance) if getattr(args, 'surface_metrics', False) else {}
     crf = crf_settings(args)
     refine = dict(crf=crf) if crf is not None else {}      # without the flag the evaluate call is the parent's
+    morph = morph_settings(args)
+    if morph['min_component_size']:
+        refine['min_component_size'] = morph['min_component_size']
+    if morph['fill_holes']:
+        refine.update(fill_holes=True, fill_holes_connectivity=morph['fill_holes_connectivity'])
     if volumes:                                            # the grouping first: a file name that does not fit fails before the model runs
         from .utils.volume import group_volumes
         names = test_dataset.names if args.synthetic else [os.path.splitext(os.path.basename(f))[0] for f in args.test_ls]
@@ -391,6 +486,14 @@ def main_interface(args):
         dicearr, hd95arr = evaluate(model, loader, num_classes, spacing, device, tta=tta, extra=extra, **surface, **refine)
         vol = _volume_scores(args, volume_maps, groups, num_classes, (slice_spacing,) + tuple(spacing)) if volumes else {}
         np.savez(os.path.join(args.child, 'eval_data'), dicearr=dicearr, hd95arr=hd95arr, **extra, **vol)
+    if morph['min_component_size']:
+        small = extra['small_removed']
+        logging.info('Size threshold ({} pixels, connectivity {}): {} pixels set to background, {} of {} slices changed'.format(
+            morph['min_component_size'], args.cc_connectivity, int(small.sum()), int((small.sum(1) > 0).sum()), len(small)))
+    if morph['fill_holes']:
+        filled = extra['holes_filled']
+        logging.info('Hole filling (connectivity {}): {} pixels filled, {} of {} slices changed, {} cavities between several classes left'.format(
+            morph['fill_holes_connectivity'], int(filled.sum()), int((filled.sum(1) > 0).sum()), len(filled), int(extra['holes_mixed'].sum())))
     if tta != 'none':
         from .utils.tta import tta_ops
         changed = extra['tta_changed']
@@ -435,6 +538,12 @@ def main_interface(args):
         if args.keep_largest_cc:
             logging.info('Largest-component filter in 3-D (connectivity {}): {} voxels set to background in {} volumes'.format(
                 args.cc_connectivity_3d, int(vol['vol_removed'].sum()), len(groups)))
+        if morph['min_component_size_3d']:
+            logging.info('Size threshold in 3-D ({} voxels, connectivity {}): {} voxels set to background in {} volumes'.format(
+                morph['min_component_size_3d'], args.cc_connectivity_3d, int(vol['vol_small_removed'].sum()), len(groups)))
+        if morph['fill_holes']:
+            logging.info('Hole filling in 3-D (connectivity {}): {} voxels filled in {} volumes, {} cavities between several classes left'.format(
+                morph['fill_holes_connectivity_3d'], int(vol['vol_holes_filled'].sum()), len(groups), int(vol['vol_holes_mixed'].sum())))
     logging.info('Shape of the Dice array: {}'.format(dicearr.shape))
     logging.info('Shape of the HD95 array: {}'.format(hd95arr.shape))
     return dicearr, hd95arr
@@ -474,7 +583,8 @@ def main(argv=None):
     # without --surface_metrics the log is what it was before the flag existed: its two entries are left out of the dump
     shown = [(k, v) for k, v in args._get_kwargs() if (args.surface_metrics or k not in ('surface_metrics', 'nsd_tolerance'))
              and (args.crf_refine or k not in CRF_FLAGS)         # the same for --crf_refine and its eight entries
-             and (args.volumes or args.synthetic_depth or k not in VOLUME_FLAGS)]      # ... and for --volumes and its companions
+             and (args.volumes or args.synthetic_depth or k not in VOLUME_FLAGS)       # ... and for --volumes and its companions
+             and (morph_used(args) or k not in MORPH_FLAGS)]     # ... and for the size threshold and hole filling
     logging.info(''.join(f'{k}={v}\n' for k, v in shown))
     if not args.synthetic:
         from .train import split_dir                              # the same table the trainers read their fold lists from

@@ -10,3 +10,5 @@ from .distance import distance_transform_edt, signed_distance_maps  # noqa: F401
 from .geodesic import check_geo_params, expand_dataset_geo, geodesic_distance, geodesic_expand_scribbles  # noqa: F401
 from .volume import (distance_transform_edt_3d, group_volumes, keep_largest_components_3d, label_components_3d, volume_dice,  # noqa: F401
                      volume_surface_metrics)
+from .morphology import (binary_fill_holes, check_morph_params, fill_holes, fill_holes_3d, remove_small_components,  # noqa: F401
+                         remove_small_components_3d)

@@ -54,7 +54,8 @@ class GraphedStep:
         return (int(epoch), bool(m.backbone.training), bool(m.aux_path.training),
                 tuple((k, tuple(v.shape), v.dtype, v.device.index) for k, v in sorted(batch.items()) if torch.is_tensor(v)),
                 float(getattr(eng, 'loss_scale', 1.0)), str(getattr(eng, 'storage', 'fp32')), id(eng.comm), bool(eng.sync_bn),
-                tuple((float(g.get('weight_decay', 0.0)), tuple(g.get('betas', ())), float(g.get('momentum', 0.0)),
+                tuple((float(g.get('weight_decay', 0.0)), bool(g.get('exempt_1d', False)),      # exempt_1d: mask or no mask in the launch
+                       tuple(g.get('betas', ())), float(g.get('momentum', 0.0)),
                        g.get('max_grad_norm'),          # baked into the clip finalize launch (None: no clip launches at all)
                        g.get('ema_decay'))              # baked into the *_step_ema launches (None: the plain entry points)
                       for g in self.opt.param_groups),

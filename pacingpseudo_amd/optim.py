@@ -1,4 +1,5 @@
-"""FusedAdam / FusedSGD: ``torch.optim.Adam`` / ``torch.optim.SGD`` semantics in one HIP kernel per slab segment.
+"""FusedAdam / FusedSGD / FusedAdamW: ``torch.optim.Adam`` / ``torch.optim.SGD`` / ``torch.optim.AdamW`` semantics in one HIP kernel per
+slab segment.
 
 Reference call site: train_chaos.py:218-223 (Adam, lr 1e-4, L2-coupled weight decay 3e-4) and
 train_chaos.py:313-315 (zero_grad / backward / step).  The class keeps the ``torch.optim.Optimizer`` protocol
@@ -118,6 +119,26 @@ def add_ema_flags(parser) -> None:
                              'ckps/ema_ckp_<e>.pth / best_ema_ckp.pth; training itself does not depend on it; 0 = off')
     parser.add_argument('--ema_val_interval', type=_positive_int, default=1,
                         help='with --ema_decay: validate the averaged weights every this many epochs (and after the last one)')
+
+
+WD_HELP = ('weight decay, used as given: with --optimizer adam / momentum an L2 term added to the gradient (the reference\'s 0.0003); '
+           'with --optimizer adamw DECOUPLED from the gradient, p *= 1 - lr * wd per step -- not comparable with the L2 value of '
+           '--optimizer adam (torch.optim.AdamW defaults to 0.01), and no value has been tuned here: with adamw the default is an '
+           'untuned first value')
+
+
+def add_wd_exempt_flag(parser) -> None:
+    """``--wd_exempt_1d`` of both training drivers (resume.py knows the default for state files older than the flag)."""
+    parser.add_argument('--wd_exempt_1d', action='store_true', default=False,
+                        help='with --optimizer adamw: do not decay parameters with one dimension or none (BatchNorm / GroupNorm '
+                             'affine parameters and biases); decided per element inside the update kernel')
+
+
+def check_optimizer_flags(parser, args) -> None:
+    """The check that spans --optimizer and --wd_exempt_1d (an argparse error: exit status 2)."""
+    if args.wd_exempt_1d and args.optimizer != 'adamw':
+        parser.error(f'--wd_exempt_1d needs --optimizer adamw: the kernels of --optimizer {args.optimizer} decay through the '
+                     'gradient and have no exemption')
 
 
 def log_clip_stats(optimizer, epoch: int, scalars=None, log=None) -> None:
@@ -451,6 +472,92 @@ class FusedAdam(_SlabOptimizer):
                             lib.pp_adam_step_dev(*common, st)
                         else:
                             lib.pp_adam_step_clip(*common, clip_dev, st)
+                    flat.version += 1
+        return None
+
+
+def check_adamw_hyper(lr, betas, eps, weight_decay) -> None:
+    """What libpacingpseudo_opt.so would refuse at the first step, refused when the optimizer is built."""
+    for name, value in (('lr', lr), ('eps', eps), ('weight_decay', weight_decay)):
+        value = float(value)
+        if not (value >= 0.0 and value < math.inf):          # NaN compares false
+            raise ValueError(f'invalid AdamW hyper-parameter: {name} must be finite and >= 0, got {value!r}')
+    if len(betas) != 2 or not all(0.0 <= float(b) < 1.0 for b in betas):
+        raise ValueError(f'invalid AdamW hyper-parameter: betas must be two values in [0, 1), got {betas!r}')
+
+
+def decay_exempt_mask(flat) -> torch.Tensor:
+    """One byte per element of ``flat.params`` (uint8, on the host): 1 for every element of a parameter with ``ndim <= 1`` -- the
+    affine parameters of BatchNorm / GroupNorm and the biases, which ``FusedAdamW(exempt_1d=True)`` does not decay -- 0 for every
+    other parameter and for the alignment padding (it holds zeros, and zeros stay zeros under both the decay and the Adam move).
+    A marked run starts wherever its tensor starts: FlatSlab aligns segments, not parameters."""
+    mask = torch.zeros(int(flat.numel), dtype=torch.uint8)
+    for p, off in flat.offsets.items():
+        if p.ndim <= 1:
+            mask[off:off + p.numel()] = 1
+    return mask
+
+
+class FusedAdamW(_SlabOptimizer):
+    """``torch.optim.AdamW(params, lr, betas, eps, weight_decay)`` (non-amsgrad): the decay is decoupled from the gradient,
+    ``p *= 1 - lr * weight_decay`` before the Adam move, and never enters the moments.  ``exempt_1d``: parameters with
+    ``ndim <= 1`` are not decayed; the decision is taken per ELEMENT inside the kernel from a byte mask laid over the slab
+    (``decay_exempt_mask``), because those tensors are interleaved with the convolution weights inside the segments the kernel
+    is launched over.  Everything else -- device-side step counts and learning rate, the overflow guard, ``max_grad_norm``,
+    ``ema_decay``, ``state_dict()`` -- is ``FusedAdam``'s.  The update kernels are libpacingpseudo_opt.so's (``_opt.py``); the
+    norm kernels of the clipping stay in the per-step library."""
+    STATE_KEYS = ('m', 'v')
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, exempt_1d=False, max_grad_norm=None,
+                 ema_decay=None):
+        check_adamw_hyper(lr, betas, eps, weight_decay)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, exempt_1d=bool(exempt_1d),
+                                      max_grad_norm=check_max_grad_norm(max_grad_norm), ema_decay=check_ema_decay(ema_decay)))
+        self._init_state()
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        for g, saved in zip(self.param_groups, sd['param_groups']):
+            g['exempt_1d'] = bool(saved.get('exempt_1d', False))          # a state dict older than the key: off
+
+    def _exempt_ptr(self, group, flat, state):
+        """Address of the slab's exemption mask on the device, or None with ``exempt_1d`` off (the kernel then reads no mask).
+        Built once, on first use, next to m and v, and never reallocated: its address is baked into a captured hipGraph."""
+        if not group.get('exempt_1d', False):
+            return None
+        mask = state.get('exempt')
+        if mask is None:
+            mask = decay_exempt_mask(flat).to(flat.params.device)
+            state['exempt'] = mask
+        return mask.data_ptr()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            raise NotImplementedError('closures are not supported')
+        from ._opt import opt
+        st = stream_ptr()
+        with prof_range('optimizer: AdamW'):
+            for group in self.param_groups:
+                b1, b2 = group['betas']
+                for flat, state, active in self._segments_with_grads(group):
+                    skip = flat.guard.data_ptr() if getattr(flat, 'guard_on', False) else None      # 16-bit storage: overflow guard
+                    lr_dev = self.lr_scalar(group, flat.params.device).data_ptr()
+                    exempt = self._exempt_ptr(group, flat, state)
+                    clip_dev = self._clip_launch(group, flat, state, active, skip, st)
+                    ema = self._ema_ptr(group, state)
+                    for j, (name, a, b, step_ptr) in enumerate(active):
+                        common = (flat.params.data_ptr() + 4 * a, flat.grads.data_ptr() + 4 * a,
+                                  state['m'].data_ptr() + 4 * a, state['v'].data_ptr() + 4 * a, b - a,
+                                  float(group['lr']), lr_dev, float(b1), float(b2), float(group['eps']),
+                                  float(group['weight_decay']), step_ptr, skip, 1 if j == 0 else 0,
+                                  None if exempt is None else exempt + a)
+                        if ema is not None:
+                            opt.popt_adamw_step_ema(*common, ema + 4 * a, group['ema_decay'], clip_dev, st)
+                        elif clip_dev is None:
+                            opt.popt_adamw_step(*common, st)
+                        else:
+                            opt.popt_adamw_step_clip(*common, clip_dev, st)
                     flat.version += 1
         return None
 

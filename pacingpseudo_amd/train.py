@@ -30,7 +30,7 @@ import torch
 
 from . import finetune, resume
 from .regop import REGULARISERS, active_regularisers
-from .optim import add_clip_flag, add_ema_flags, log_clip_stats, positive_float, positive_int
+from .optim import WD_HELP, add_clip_flag, add_ema_flags, add_wd_exempt_flag, check_optimizer_flags, log_clip_stats, positive_float, positive_int
 from .utils.random_walker import add_rw_flags, add_rw_refresh_flags, check_rw_params, check_rw_refresh_flags
 from .utils.geodesic import add_geo_flags, check_geo_params
 from .utils.uncertainty import check_uncertainty_params, uncertainty_threshold
@@ -80,11 +80,12 @@ _flags('optimisation', '86-112', [
     ('ignored_index', dict(type=int, default=None, help='label value of unlabelled pixels (= the extra scribble plane; default: the --dataset preset, 5 for chaos)')),
     ('epoch', dict(type=int, default=400, help='epochs; also the horizon of the LR schedule and of the memory momentum')),
     ('batch_size', dict(type=int, default=12, help='images per GPU and step')),
-    ('optimizer', dict(type=str, default='adam', choices=['adam', 'momentum'], help='FusedAdam or FusedSGD (one kernel over the flat parameter slab)')),
+    ('optimizer', dict(type=str, default='adam', choices=['adam', 'momentum', 'adamw'],
+                       help='FusedAdam, FusedSGD or FusedAdamW (one kernel over the flat parameter slab); adamw decouples --wd from the gradient')),
     ('momentum', dict(type=float, default=0.9, help='momentum of --optimizer momentum')),
     ('lr', dict(type=float, default=0.0001, help='learning rate at epoch 0')),
     ('lr_decay', dict(type=str, default='poly', choices=['linear', 'poly', 'cosine'], help='per-epoch schedule')),
-    ('wd', dict(type=float, default=0.0003, help='L2 weight decay, added to the gradient')),
+    ('wd', dict(type=float, default=0.0003, help=WD_HELP)),
     ('ckp_interval', dict(type=int, default=10000, help='write ckps/ckp_<epoch>.pth every this many epochs (and at the end)')),
 ])
 _flags('entropy minimisation', '114-126', [
@@ -202,6 +203,7 @@ parser.add_argument('--cr_uncertainty_start', type=float, default=0.75,
                          '(untuned first value)')
 add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
 add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
+add_wd_exempt_flag(parser)                    # --wd_exempt_1d, with --optimizer adamw (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
 finetune.add_flags(parser)                    # --freeze_encoder N / --init_from PATH / --init_reset_head (pacingpseudo_amd/finetune.py)
 # random-walker expansion of the training scribbles, once before the first step (libpacingpseudo_prep.so); the
@@ -253,6 +255,7 @@ def apply_dataset_preset(args, argv=None):
 def parse_args(argv=None):
     """parser.parse_args plus the checks that span several flags (argparse errors: exit status 2)."""
     args = parser.parse_args(argv)
+    check_optimizer_flags(parser, args)
     for r in REGULARISERS.values():
         try:
             r.check(**r.args_params(args))
@@ -294,7 +297,7 @@ def train_interface(args, resume_state=None):
     from .data import SyntheticPhantoms, collate_by_shape, dataset_class, expand_compact, loader_context
     from .models import ConsistencyRegulr
     from .models.unet import norm_kwargs
-    from .optim import FusedAdam, FusedSGD
+    from .optim import FusedAdam, FusedAdamW, FusedSGD
     from .utils import AvgMeter, cosine_lr_decay, gaussian_ramp_up, linear_lr_decay, poly_lr_decay
     from .losses.losses import weighted_loss_sum
     from .utils.metrics import ValAccumulator
@@ -330,6 +333,9 @@ def train_interface(args, resume_state=None):
     elif args.optimizer == 'momentum':
         optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.wd,
                              max_grad_norm=args.clip_grad_norm or None, ema_decay=args.ema_decay or None)
+    elif args.optimizer == 'adamw':
+        optimizer = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.wd, exempt_1d=args.wd_exempt_1d,
+                               max_grad_norm=args.clip_grad_norm or None, ema_decay=args.ema_decay or None)
     else:
         raise ValueError('Unimplemented optimizer')
     if args.cr_teacher == 'ema':                  # the shadow slab exists from here on (resume.restore then loads the saved one)

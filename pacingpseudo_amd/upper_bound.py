@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import finetune, resume
-from .optim import add_clip_flag, add_ema_flags, log_clip_stats
+from .optim import WD_HELP, add_clip_flag, add_ema_flags, add_wd_exempt_flag, check_optimizer_flags, log_clip_stats
 
 parser = argparse.ArgumentParser()
 parser.add_argument('--gpu', type=str, default='1')
@@ -52,11 +52,12 @@ parser.add_argument('--loss_dice', action='store_true', default=True)
 parser.add_argument('--ignored_index', type=int, default=None, help='default: the --dataset preset (5 for chaos)')
 parser.add_argument('--epoch', type=int, default=400)
 parser.add_argument('--batch_size', type=int, default=12)
-parser.add_argument('--optimizer', type=str, default='adam', choices=['adam'])
+parser.add_argument('--optimizer', type=str, default='adam', choices=['adam', 'adamw'],
+                    help='FusedAdam or FusedAdamW (one kernel over the flat parameter slab); adamw decouples --wd from the gradient')
 parser.add_argument('--momentum', type=float, default=0.9)
 parser.add_argument('--lr', type=float, default=0.0001)
 parser.add_argument('--lr_decay', type=str, default='poly', choices=['linear', 'poly', 'cosine'])
-parser.add_argument('--wd', type=float, default=0.0003)
+parser.add_argument('--wd', type=float, default=0.0003, help=WD_HELP)
 parser.add_argument('--ckp_interval', type=int, default=10000)
 # ---- additions of this implementation (same meaning as in pacingpseudo_amd.train)
 parser.add_argument('--synthetic', type=int, default=0)
@@ -72,6 +73,7 @@ parser.add_argument('--norm_groups', type=int, default=8, help='channel groups o
 parser.add_argument('--gpu_augment', action='store_true', help='accepted for compatibility: the GPU pipeline is the default')
 add_clip_flag(parser)                         # --clip_grad_norm X (pacingpseudo_amd/optim.py)
 add_ema_flags(parser)                         # --ema_decay D / --ema_val_interval N (pacingpseudo_amd/optim.py)
+add_wd_exempt_flag(parser)                    # --wd_exempt_1d, with --optimizer adamw (pacingpseudo_amd/optim.py)
 resume.add_flags(parser)                      # --state_interval N / --resume PATH (pacingpseudo_amd/resume.py)
 finetune.add_flags(parser)                    # --freeze_encoder N / --init_from PATH / --init_reset_head (pacingpseudo_amd/finetune.py)
 # ---- boundary loss (Kervadec et al., MIDL 2019): mean of soft-max x the signed distance map of the label, recomputed per step on the
@@ -90,7 +92,7 @@ def train_interface(args, resume_state=None):
     from .losses.losses import boundary_loss, dice_loss_fn, partial_cross_entropy_loss
     from .models import UNet
     from .models.unet import norm_kwargs
-    from .optim import FusedAdam
+    from .optim import FusedAdam, FusedAdamW
     from .train import _class_names
     from .utils import cosine_lr_decay, gaussian_ramp_up, linear_lr_decay, poly_lr_decay
     from .utils.metrics import ValAccumulator
@@ -104,8 +106,12 @@ def train_interface(args, resume_state=None):
                  elab_end_points=args.elab_end_points, **norm_kwargs(args)).cuda()
     finetune.init_model(args, model, parser, logging.info)      # --init_from / --freeze_encoder: before the optimizer exists
     logging.info(model)
-    optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd, max_grad_norm=args.clip_grad_norm or None,
-                          ema_decay=args.ema_decay or None)
+    if args.optimizer == 'adamw':
+        optimizer = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.wd, exempt_1d=args.wd_exempt_1d,
+                               max_grad_norm=args.clip_grad_norm or None, ema_decay=args.ema_decay or None)
+    else:
+        optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd, max_grad_norm=args.clip_grad_norm or None,
+                              ema_decay=args.ema_decay or None)
     ds_kw = dict(num_classes=args.num_classes, size=args.image_size, seed=args.seed)
     # the reference trains the upper bound with the whole WEAK pipeline (upper_bound_chaos.py:132-137: base_transforms =
     # Scaling, Elastic, Rotation, Mirroring, GaussianNoise, RandomCrop; no strong view): the same device pipeline as
@@ -279,9 +285,16 @@ def train_interface(args, resume_state=None):
     return valdice
 
 
+def parse_args(argv=None):
+    """parser.parse_args plus the check that spans --optimizer and --wd_exempt_1d (an argparse error: exit status 2)."""
+    args = parser.parse_args(argv)
+    check_optimizer_flags(parser, args)
+    return args
+
+
 def train_main(argv=None):
     from .train import DATASETS, apply_dataset_preset, split_dir
-    args = apply_dataset_preset(parser.parse_args(argv))
+    args = apply_dataset_preset(parse_args(argv))
     if args.ramp_up_loss_boundary < 0 or not np.isfinite(args.loss_boundary_weight):
         parser.error('--loss_boundary_weight must be finite and --ramp_up_loss_boundary >= 0')
     # one process: the upper bound has no data-parallel path

@@ -338,6 +338,97 @@ def boundary_loss(input, target, dist_maps=None, spacing=(1., 1.)):
     return _BoundaryLoss.apply(input.contiguous(), dist_maps.detach().contiguous())
 
 
+LOVASZ_MIN_CLASSES, LOVASZ_MAX_CLASSES = 2, 32
+
+
+class _LovaszSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, cls, ignore_index, per_image, classes_all, parts):
+        from .._lov import lov
+        N, K, H, W = z.shape
+        P = N * H * W
+        has_ignore = int(ignore_index is not None)
+        ign = int(ignore_index) if has_ignore else 0
+        with torch.cuda.device(z.device):
+            nws = lov.plov_loss_workspace(N, K, H, W, int(per_image))
+            ws = torch.empty(max(nws // 8, 1), device=z.device, dtype=torch.float64)
+            out = torch.empty((), device=z.device, dtype=torch.float32)
+            weights = torch.empty((K, P), device=z.device, dtype=torch.float32)
+            scale = torch.empty(N * K if per_image else K, device=z.device, dtype=torch.float32)
+            errors = torch.empty((K, P), device=z.device, dtype=torch.float32) if parts else None
+            perm = torch.empty((N * K, H * W) if per_image else (K, P), device=z.device, dtype=torch.int32) if parts else None
+            lov.plov_loss_fwd(z.data_ptr(), cls.data_ptr(), N, K, H, W, has_ignore, ign, int(per_image), int(classes_all), out.data_ptr(),
+                              weights.data_ptr(), scale.data_ptr(), errors.data_ptr() if parts else None,
+                              perm.data_ptr() if parts else None, ws.data_ptr(), ws.numel() * 8, stream_ptr())
+        ctx.save_for_backward(z, cls, weights, scale)
+        ctx.flags = (has_ignore, ign, int(per_image))
+        if parts:
+            ctx.mark_non_differentiable(errors, perm, weights)
+            return out, errors, perm, weights
+        return out
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        from .._lov import lov
+        z, cls, weights, scale = ctx.saved_tensors
+        N, K, H, W = z.shape
+        has_ignore, ign, per_image = ctx.flags
+        g = g.to(torch.float32).contiguous()
+        dz = torch.empty_like(z)
+        with torch.cuda.device(z.device):
+            lov.plov_loss_bwd(z.data_ptr(), cls.data_ptr(), N, K, H, W, has_ignore, ign, per_image, weights.data_ptr(), scale.data_ptr(),
+                              g.data_ptr(), dz.data_ptr(), stream_ptr())
+        return dz, None, None, None, None, None
+
+
+def lovasz_softmax_loss(input, target, ignore_index=None, per_image=False, classes='present', return_parts=False):
+    """Lovasz-softmax loss of Berman, Triki and Blaschko (CVPR 2018) on softmax(input): for every class c the errors
+    e_i = |[target_i == c] - p_ci| of the valid pixels, sorted in descending order (ties in ascending (n, y, x) pixel index), weighted
+    by the increments of the Jaccard loss along that order and summed; the mean over the classes that occur (``classes='present'``)
+    or over all K (``'all'``).  ``per_image``: that loss per image, averaged over all N images (an image without a present class
+    counts 0).  A pixel is valid when 0 <= target < K and target != ignore_index; any other value is ignored.  No valid pixel of a
+    present class at all: loss 0, gradient 0.  A non-finite logit gives NaN.
+
+    `input` fp32 (N, K, H, W) with 2 <= K <= 32 and N*K*H*W < 2^31; `target` the one-hot label (N, K, H, W) as ``dice_loss_fn`` takes
+    it (its arg-max is the class map) or an int64 class map (N, H, W).  Sorted, scanned and reduced on the device
+    (libpacingpseudo_lov.so) without a device-to-host read; same bits in every run.
+
+    ``return_parts=True`` returns (loss, errors, perm, weights), the last three detached: errors fp32 (K, N*H*W), e in pixel order (0
+    at ignored pixels); perm int32, one row per segment -- (K, N*H*W), or (N*K, H*W) image-major with ``per_image`` -- of FLATTENED
+    (n, y, x) pixel indices into N*H*W in sorted order, in both modes, the segment's ignored pixels last in ascending index order;
+    weights fp32 (K, N*H*W), the increment g at every pixel's rank in its segment, in pixel order (0 at ignored pixels).
+    The reference has no such loss (upper_bound_chaos.py --do_loss_lovasz)."""
+    if not (torch.is_tensor(input) and input.dtype == torch.float32 and input.dim() == 4):
+        raise ValueError('input must be a 4-D float32 CUDA tensor (N,K,H,W)')
+    N, K, H, W = input.shape
+    if min(input.shape) < 1 or not LOVASZ_MIN_CLASSES <= K <= LOVASZ_MAX_CLASSES or input.numel() >= 2 ** 31:
+        raise ValueError(f'input is {tuple(input.shape)}: need {LOVASZ_MIN_CLASSES} <= K <= {LOVASZ_MAX_CLASSES}, no empty axis, N*K*H*W < 2^31')
+    if classes not in ('present', 'all'):
+        raise ValueError(f"classes must be 'present' or 'all', got {classes!r}")
+    if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or not -2 ** 63 <= ignore_index < 2 ** 63):
+        raise ValueError(f'ignore_index must be None or an integer, got {ignore_index!r}')
+    for name, flag in (('per_image', per_image), ('return_parts', return_parts)):
+        if not isinstance(flag, (bool, int)) or flag not in (0, 1):
+            raise ValueError(f'{name} must be a bool, got {flag!r}')
+    if not torch.is_tensor(target):
+        raise ValueError(f'target must be a torch tensor, got {type(target).__name__}')
+    if target.dim() == 4:
+        if tuple(target.shape) != (N, K, H, W):
+            raise ValueError(f'a one-hot target must have input\'s shape {(N, K, H, W)}, got {tuple(target.shape)}')
+    elif target.dim() == 3:
+        if target.dtype != torch.int64 or tuple(target.shape) != (N, H, W):
+            raise ValueError(f'a class-map target must be int64 {(N, H, W)}, got {target.dtype} {tuple(target.shape)}')
+    else:
+        raise ValueError(f'target must be one-hot (N, K, H, W) or an int64 class map (N, H, W), got {tuple(target.shape)}')
+    if not (target.is_cuda and target.device == input.device):
+        raise ValueError('target must be a CUDA tensor on input\'s device')
+    if not input.is_cuda:
+        raise ValueError('input must be a CUDA tensor: there is no CPU path')
+    with torch.no_grad():
+        cls = (torch.argmax(target, dim=1) if target.dim() == 4 else target).contiguous()
+    return _LovaszSoftmax.apply(input.contiguous(), cls, ignore_index, bool(per_image), classes == 'all', bool(return_parts))
+
+
 class _RegLoss(torch.autograd.Function):
     """One regulariser of regop.REGULARISERS on its own: a RegOp over buffers of this call."""
 

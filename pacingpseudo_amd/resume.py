@@ -46,7 +46,8 @@ ABSENT_DEFAULTS = {'clip_grad_norm': 0.0, 'ema_decay': 0.0, 'ema_val_interval': 
                    'cr_uncertainty': 0, 'cr_uncertainty_sigma': 0.1, 'cr_uncertainty_clip': 0.2, 'cr_uncertainty_start': 0.75,
                    'do_loss_boundary': False, 'loss_boundary_weight': 0.01, 'ramp_up_loss_boundary': 0,
                    'geo_scribbles': False, 'geo_lambda': 20.0, 'geo_ratio': 0.25, 'geo_max_dist': float('inf'), 'geo_max_sweeps': 100000,
-                   'wd_exempt_1d': False}
+                   'wd_exempt_1d': False,
+                   'do_loss_lovasz': False, 'loss_lovasz_weight': 1.0, 'ramp_up_loss_lovasz': 0, 'lovasz_per_image': False}
 # attributes the drivers add to the namespace after parsing (not flags)
 _DERIVED = frozenset({'child', 'train_ls', 'val_ls'})
 

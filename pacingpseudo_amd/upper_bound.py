@@ -10,7 +10,8 @@ The step runs through ``UNet.forward`` (one autograd node over the engine's stat
 (upper_bound_chaos.py:132-137) on the GPU (``augment.DeviceAugmenter(do_strong=False)``; ``--cpu_input`` selects the minimal CPU
 path); validation at the native slice size with device-side meters; widened ``choices`` and the --synthetic / --image_size /
 --max_iters additions are those of ``pacingpseudo_amd.train``.  ``--do_loss_boundary`` (not in the reference) adds the boundary loss
-of Kervadec et al. on signed distance maps recomputed per step from the augmented label (``losses.boundary_loss``).
+of Kervadec et al. on signed distance maps recomputed per step from the augmented label (``losses.boundary_loss``);
+``--do_loss_lovasz`` (not in the reference either) adds the Lovasz-softmax loss of Berman et al. (``losses.lovasz_softmax_loss``).
 """
 from __future__ import annotations
 
@@ -84,12 +85,22 @@ parser.add_argument('--loss_boundary_weight', type=float, default=0.01,
                     help="weight of the boundary loss; 0.01 is Kervadec's initial alpha, here an untuned first value")
 parser.add_argument('--ramp_up_loss_boundary', type=int, default=0,
                     help='0: constant weight; E > 0: the weight of epoch e is gaussian_ramp_up(e, loss_boundary_weight, max_t=E)')
+# ---- Lovasz-softmax loss (Berman, Triki, Blaschko, CVPR 2018): the convex extension of the per-class Jaccard loss on the sorted pixel
+# errors, sorted and scanned on the device (libpacingpseudo_lov.so); the reference has no such term.  Off: the step is the reference's.
+parser.add_argument('--do_loss_lovasz', action='store_true', default=False,
+                    help='add loss_lovasz_weight * lovasz_softmax_loss(logits, label, ignore_index=ignored_index) to cross entropy + Dice')
+parser.add_argument('--loss_lovasz_weight', type=float, default=1.0,
+                    help='weight of the Lovasz-softmax loss; 1.0 is an untuned first value')
+parser.add_argument('--ramp_up_loss_lovasz', type=int, default=0,
+                    help='0: constant weight; E > 0: the weight of epoch e is gaussian_ramp_up(e, loss_lovasz_weight, max_t=E)')
+parser.add_argument('--lovasz_per_image', action='store_true', default=False,
+                    help='the Lovasz-softmax loss per image, averaged over the batch, instead of over the whole batch at once')
 
 
 def train_interface(args, resume_state=None):
     from .augment import AugConfig, DeviceAugmenter, collate_raw
     from .data import SyntheticPhantoms, collate_by_shape, dataset_class, expand_compact, loader_context
-    from .losses.losses import boundary_loss, dice_loss_fn, partial_cross_entropy_loss
+    from .losses.losses import boundary_loss, dice_loss_fn, lovasz_softmax_loss, partial_cross_entropy_loss
     from .models import UNet
     from .models.unet import norm_kwargs
     from .optim import FusedAdam, FusedAdamW
@@ -142,6 +153,7 @@ def train_interface(args, resume_state=None):
     valdice = np.zeros(args.epoch)
     ema_on = bool(args.ema_decay)                  # --ema_decay: see pacingpseudo_amd/train.py
     bl_on = bool(args.do_loss_boundary)            # --do_loss_boundary: off = the parent's step, log lines and scalar tags
+    lv_on = bool(args.do_loss_lovasz)              # --do_loss_lovasz: likewise; its fields and tags come after the boundary ones
     valdice_ema = np.zeros(args.epoch) if ema_on else None
     best_ema = dict(avg=0, epoch=0, avg_class=[])
     aug_stream = torch.cuda.Stream() if (augmenter is not None and os.environ.get('PP_AUG_STREAM', '1') != '0') else None
@@ -156,10 +168,11 @@ def train_interface(args, resume_state=None):
 
     def validate():
         """One pass over the validation slices with the weights the model holds: (per-class Dice, loss_ce, loss_dice,
-        loss_boundary -- None without --do_loss_boundary)."""
+        loss_boundary -- None without --do_loss_boundary, loss_lovasz -- None without --do_loss_lovasz)."""
         meters = ValAccumulator(args.num_classes, device)              # Dice meters + n-weighted loss_ce, on the device
         dsum = torch.zeros(1, device=device, dtype=torch.float64)       # n-weighted loss_dice
         bsum = torch.zeros(1, device=device, dtype=torch.float64)       # n-weighted loss_boundary
+        lsum = torch.zeros(1, device=device, dtype=torch.float64)       # n-weighted loss_lovasz
         for groups in val_loader:
             for batch in groups:
                 batch = expand_compact(batch, args.num_classes, device)      # uint8 class maps -> one-hot planes, on the device
@@ -171,15 +184,22 @@ def train_interface(args, resume_state=None):
                     dsum += dice_loss_fn(logits, label).double() * image.shape[0]
                     if bl_on:
                         bsum += boundary_loss(logits, target).double() * image.shape[0]
+                    if lv_on:
+                        lsum += lovasz_softmax_loss(logits, target, ignore_index=args.ignored_index,
+                                                    per_image=args.lovasz_per_image).double() * image.shape[0]
         dsc, val_ce, n_val = meters.result()                            # the host sync of the validation epoch
-        return dsc, val_ce, float(dsum) / max(n_val, 1), (float(bsum) / max(n_val, 1) if bl_on else None)
+        return (dsc, val_ce, float(dsum) / max(n_val, 1), (float(bsum) / max(n_val, 1) if bl_on else None),
+                (float(lsum) / max(n_val, 1) if lv_on else None))
 
     for curr_epoch in range(start_epoch, args.epoch):
         epoch_tic = time.time()
         optimizer, new_lr = decay[args.lr_decay](optimizer, curr_epoch, args.epoch, args.lr)
-        # sum ce*n, sum dice*n, n (read once per epoch); with --do_loss_boundary also sum boundary*n
-        acc = torch.zeros(4 if bl_on else 3, device=device, dtype=torch.float64)
-        bl_weight = 0.0
+        # sum ce*n, sum dice*n, n (read once per epoch); with --do_loss_boundary also sum boundary*n, with --do_loss_lovasz sum lovasz*n
+        acc = torch.zeros(5 if lv_on else (4 if bl_on else 3), device=device, dtype=torch.float64)
+        bl_weight = lv_weight = 0.0
+        if lv_on:
+            lv_weight = (gaussian_ramp_up(curr_epoch, args.loss_lovasz_weight, max_t=args.ramp_up_loss_lovasz)
+                         if args.ramp_up_loss_lovasz > 0 else args.loss_lovasz_weight)
         if bl_on:
             bl_weight = (gaussian_ramp_up(curr_epoch, args.loss_boundary_weight, max_t=args.ramp_up_loss_boundary)
                          if args.ramp_up_loss_boundary > 0 else args.loss_boundary_weight)
@@ -203,23 +223,28 @@ def train_interface(args, resume_state=None):
                 loss_bl = boundary_loss(logits, target)
                 loss = loss + bl_weight * loss_bl
                 acc[3] += loss_bl.detach() * n
+            if lv_on:
+                loss_lv = lovasz_softmax_loss(logits, target, ignore_index=args.ignored_index, per_image=args.lovasz_per_image)
+                loss = loss + lv_weight * loss_lv
+                acc[4] += loss_lv.detach() * n
             acc[2] += n
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()
         a = acc.cpu().numpy()
         cnt = max(a[2], 1)
-        logging.info("epoch: {:03d}, lr: {:.6f}, loss_ce: {:.6f}, loss_dice: {:.6f}, {}{:.2f} s/epoch".format(
+        logging.info("epoch: {:03d}, lr: {:.6f}, loss_ce: {:.6f}, loss_dice: {:.6f}, {}{}{:.2f} s/epoch".format(
             curr_epoch, new_lr, a[0] / cnt, a[1] / cnt, "loss_boundary: {:.6f}, ".format(a[3] / cnt) if bl_on else "",
-            time.time() - epoch_tic))
+            "loss_lovasz: {:.6f}, ".format(a[4] / cnt) if lv_on else "", time.time() - epoch_tic))
         log_clip_stats(optimizer, curr_epoch, scalars, logging.info)      # --clip_grad_norm: behind the sync above
 
         model.eval()                                   # upper_bound_chaos.py:180, never undone
         tic = time.time()
-        dsc, val_ce, val_dice, val_bl = validate()
+        dsc, val_ce, val_dice, val_bl, val_lv = validate()
         avg_all = np.mean([dsc[_] for _ in range(1, args.num_classes)])
-        logging.info("val: {:03d}, loss_ce: {:.6f}, loss_dice: {:.6f}, {}{:.2f} s/epoch".format(
-            curr_epoch, val_ce, val_dice, "loss_boundary: {:.6f}, ".format(val_bl) if bl_on else "", time.time() - tic))
+        logging.info("val: {:03d}, loss_ce: {:.6f}, loss_dice: {:.6f}, {}{}{:.2f} s/epoch".format(
+            curr_epoch, val_ce, val_dice, "loss_boundary: {:.6f}, ".format(val_bl) if bl_on else "",
+            "loss_lovasz: {:.6f}, ".format(val_lv) if lv_on else "", time.time() - tic))
         logging.info("[" + ", ".join("{}: {:.4f}".format(nm, dsc[i]) for i, nm in enumerate(names))
                      + ", All: {:.4f}]".format(avg_all))
         # scalar tags of upper_bound_chaos.py:176-178, :216-224
@@ -232,6 +257,10 @@ def train_interface(args, resume_state=None):
             scalars.add('losses/loss_boundary_train', a[3] / cnt, curr_epoch)
             scalars.add('losses/loss_boundary_val', val_bl, curr_epoch)
             scalars.add('losses/boundary_weight', bl_weight, curr_epoch)
+        if lv_on:
+            scalars.add('losses/loss_lovasz_train', a[4] / cnt, curr_epoch)
+            scalars.add('losses/loss_lovasz_val', val_lv, curr_epoch)
+            scalars.add('losses/lovasz_weight', lv_weight, curr_epoch)
         for i, nm in enumerate(names):
             scalars.add(f'DSC/{nm}', dsc[i], curr_epoch)
         scalars.add('DSC/All', avg_all, curr_epoch)
@@ -297,6 +326,8 @@ def train_main(argv=None):
     args = apply_dataset_preset(parse_args(argv))
     if args.ramp_up_loss_boundary < 0 or not np.isfinite(args.loss_boundary_weight):
         parser.error('--loss_boundary_weight must be finite and --ramp_up_loss_boundary >= 0')
+    if args.ramp_up_loss_lovasz < 0 or not np.isfinite(args.loss_lovasz_weight):
+        parser.error('--loss_lovasz_weight must be finite and --ramp_up_loss_lovasz >= 0')
     # one process: the upper bound has no data-parallel path
     state_file, resume_state = resume.open_state(parser, args, 1) if args.resume else (None, None)
     if 'LOCAL_RANK' not in os.environ:

@@ -12,3 +12,4 @@ from .volume import (distance_transform_edt_3d, group_volumes, keep_largest_comp
                      volume_surface_metrics)
 from .morphology import (binary_fill_holes, check_morph_params, fill_holes, fill_holes_3d, remove_small_components,  # noqa: F401
                          remove_small_components_3d)
+from .sorting import sort_descending  # noqa: F401

@@ -2,14 +2,14 @@
 scribble seeds on the device and the pseudo-labels taken from them (``train_chaos.py --geo_scribbles``,
 ``utils.geodesic_distance`` / ``utils.geodesic_expand_scribbles``, ``scripts/expand_scribbles.py --method geo``).
 
-It is loaded on first use, never at import.  As with ``_lib``, ``_prep``, ``_rwp``, ``_unc`` and ``_dist`` there is NO fallback: a
-missing or stale library raises.  Build it with ``python -c "import __graft_entry__ as g; g.build()"`` (or ``make geo``)."""
+It is loaded on first use, never at import, by the loader of ``_binding``.  There is NO fallback: a missing or stale library
+raises.  Build it with ``python -c "import __graft_entry__ as g; g.build()"`` (or ``make geo``)."""
 from __future__ import annotations
 
 import ctypes as C
 import os
 
-from ._lib import HipLibraryError
+from ._binding import CLibrary, HipLibraryError  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 GEO_LIB_PATH = os.path.join(_HERE, 'lib', 'libpacingpseudo_geo.so')
@@ -28,54 +28,14 @@ _PROTOS = {
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 MIN_GEO_VERSION = 100       # include/pacingpseudo_geo.h (pp_geodesic.hip: PGEO_VERSION)
-_NO_STATUS = ('pgeo_version', 'pgeo_last_error', 'pgeo_distance_workspace')      # a value, not a status code
 
 
-class _GeoLib:
-    def __init__(self, path=GEO_LIB_PATH):
-        self._path = path
-        self._dll = None
+class _GeoLib(CLibrary):
+    prefix, target, no_fallback = 'pgeo', 'geo', 'the geodesic distance transform has no CPU fallback'
+    int_values = ('pgeo_version',)
 
-    def load(self):
-        if self._dll is None:
-            path = self._path
-            if not os.path.exists(path):
-                raise HipLibraryError(
-                    f'{path} is missing: the geodesic distance transform has no CPU fallback. '
-                    'Build it first: python -c "import __graft_entry__ as g; g.build()" (or `make geo`)')
-            dll = C.CDLL(path)
-            have = -1
-            if hasattr(dll, 'pgeo_version'):
-                dll.pgeo_version.restype = i32
-                have = dll.pgeo_version()
-            if have < MIN_GEO_VERSION:
-                raise HipLibraryError(f'{path} reports pgeo_version() = {have}; this host side needs >= {MIN_GEO_VERSION} '
-                                      '(an older build of the library: rebuild with `make geo`)')
-            missing = [name for name in _PROTOS if not hasattr(dll, name)]
-            if missing:
-                raise HipLibraryError(f'{path} (pgeo_version {have}) lacks {len(missing)} entry point(s) this host side binds, e.g. '
-                                      f'{", ".join(missing[:4])}: header / library mismatch, rebuild with `make geo`')
-            for name, (res, args) in _PROTOS.items():
-                fn = getattr(dll, name)
-                fn.restype, fn.argtypes = res, args
-            self._dll = dll
-        return self._dll
-
-    def __getattr__(self, name):
-        if name.startswith('_'):
-            raise AttributeError(name)
-        fn = getattr(self.load(), name)
-        if name in _NO_STATUS:
-            return fn
-
-        def checked(*a):
-            rc = fn(*a)
-            if rc != 0:
-                msg = self.load().pgeo_last_error()
-                raise HipLibraryError(f'{name} failed (rc={rc}): {msg.decode() if msg else "?"}')
-        checked.__name__ = name
-        setattr(self, name, checked)             # cache the wrapper
-        return checked
+    def _spec(self):
+        return self._path or GEO_LIB_PATH, _PROTOS, MIN_GEO_VERSION
 
 
 geo = _GeoLib()

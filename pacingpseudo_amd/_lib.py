@@ -7,6 +7,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from ._binding import CLibrary, HipLibraryError
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PP_LIB_PATH') or os.path.join(_HERE, 'lib', 'libpacingpseudo_hip.so')   # override: kernel A/B tests
 
@@ -244,56 +246,16 @@ PROF_KINDS = ('conv_igemm', 'conv_wgrad', 'bn', 'spatial', 'loss', 'optim', 'mis
               'wino_xform', 'conv_f16x3', 'wino_gemm_f16x3', 'wino_wgrad_f16x3', 'conv_wgrad_f16x3', 'conv_halo_f16x3')
 
 
-class HipLibraryError(RuntimeError):
-    pass
+class _Lib(CLibrary):
+    prefix, target, no_fallback = 'pp', '', 'the pacingpseudo_amd compute path has no CPU fallback'
+    or_else = ', or point PP_LIB_PATH at a matching one'      # PP_LIB_PATH A/B runs, scripts/build_base.sh
+    int_values = ('pp_version', 'pp_conv3x3_wino_tile', 'pp_conv3x3_wino_bwd_weight_splits', 'pp_conv3x3_wino_bwd_weight_plan',
+                  'pp_conv3x3_bwd_weight_plan', 'pp_convtranspose_bwd_weight_splits', 'pp_conv3x3_lazy_ok', 'pp_conv3x3_lazy_ok_h16',
+                  'pp_conv3x3_lazy_ok_bf16', 'pp_range_push', 'pp_range_pop', 'pp_get_matrix_products', 'pp_get_wgrad_cus',
+                  'pp_grad_sumsq_rows')      # queries / range depth: no status code
 
-
-class _Lib:
-    def __init__(self):
-        self._dll = None
-
-    def load(self):
-        if self._dll is None:
-            if not os.path.exists(LIB_PATH):
-                raise HipLibraryError(
-                    f'{LIB_PATH} is missing: the pacingpseudo_amd compute path has no CPU fallback. '
-                    'Build it first: python -c "import __graft_entry__ as g; g.build()"')
-            dll = C.CDLL(LIB_PATH)
-            # a library of another revision (PP_LIB_PATH A/B runs, scripts/build_base.sh) must say so in words, not fail with an
-            # AttributeError in the middle of a step: version first, then every symbol the host side binds
-            have = -1
-            if hasattr(dll, 'pp_version'):
-                dll.pp_version.restype = i32
-                have = dll.pp_version()
-            if have < MIN_LIB_VERSION:
-                raise HipLibraryError(f'{LIB_PATH} reports pp_version() = {have}; this host side needs >= {MIN_LIB_VERSION} '
-                                      '(an older build of the library: rebuild with `make`, or point PP_LIB_PATH at a matching one)')
-            missing = [name for name in _PROTOS if not hasattr(dll, name)]
-            if missing:
-                raise HipLibraryError(f'{LIB_PATH} (pp_version {have}) lacks {len(missing)} entry point(s) this host side binds, e.g. '
-                                      f'{", ".join(missing[:4])}: header / library mismatch, rebuild with `make`')
-            for name, (res, args) in _PROTOS.items():
-                fn = getattr(dll, name)
-                fn.restype, fn.argtypes = res, args
-            self._dll = dll
-        return self._dll
-
-    def __getattr__(self, name):
-        if name.startswith('_'):
-            raise AttributeError(name)
-        fn = getattr(self.load(), name)
-        res = _PROTOS[name][0]
-        if res is not i32 or name in ('pp_version', 'pp_conv3x3_wino_tile', 'pp_conv3x3_wino_bwd_weight_splits', 'pp_conv3x3_wino_bwd_weight_plan', 'pp_conv3x3_bwd_weight_plan', 'pp_convtranspose_bwd_weight_splits', 'pp_conv3x3_lazy_ok', 'pp_conv3x3_lazy_ok_h16', 'pp_conv3x3_lazy_ok_bf16', 'pp_range_push', 'pp_range_pop', 'pp_get_matrix_products', 'pp_get_wgrad_cus', 'pp_grad_sumsq_rows'):      # sizes / queries / range depth: no status code
-            return fn
-
-        def checked(*a):
-            rc = fn(*a)
-            if rc != 0:
-                msg = self.load().pp_last_error()
-                raise HipLibraryError(f'{name} failed (rc={rc}): {msg.decode() if msg else "?"}')
-        checked.__name__ = name
-        setattr(self, name, checked)             # cache the wrapper
-        return checked
+    def _spec(self):
+        return LIB_PATH, _PROTOS, MIN_LIB_VERSION
 
 
 lib = _Lib()

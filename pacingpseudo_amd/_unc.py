@@ -2,14 +2,14 @@
 mean-teacher consistency term (``--cr_uncertainty``) -- noisy teacher inputs from a counter-based generator whose (seed, step) live
 on the device, the mean soft-max over the passes, its entropy, the mask and three statistics.
 
-It is loaded on first use, never at import.  As with ``_lib``, ``_prep`` and ``_rwp`` there is NO fallback: a missing or stale
-library raises.  Build it with ``python -c "import __graft_entry__ as g; g.build()"`` (or ``make unc``)."""
+It is loaded on first use, never at import, by the loader of ``_binding``.  There is NO fallback: a missing or stale library
+raises.  Build it with ``python -c "import __graft_entry__ as g; g.build()"`` (or ``make unc``)."""
 from __future__ import annotations
 
 import ctypes as C
 import os
 
-from ._lib import HipLibraryError
+from ._binding import CLibrary, HipLibraryError  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 UNC_LIB_PATH = os.path.join(_HERE, 'lib', 'libpacingpseudo_unc.so')
@@ -27,54 +27,14 @@ _PROTOS = {
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 MIN_UNC_VERSION = 100      # include/pacingpseudo_unc.h (pp_uncertainty.hip: PUNC_VERSION)
-_NO_STATUS = ('punc_version', 'punc_last_error', 'punc_workspace_bytes')      # a value, not a status code
 
 
-class _UncLib:
-    def __init__(self, path=UNC_LIB_PATH):
-        self._path = path
-        self._dll = None
+class _UncLib(CLibrary):
+    prefix, target, no_fallback = 'punc', 'unc', 'the uncertainty mask has no CPU fallback'
+    int_values = ('punc_version',)
 
-    def load(self):
-        if self._dll is None:
-            path = self._path
-            if not os.path.exists(path):
-                raise HipLibraryError(
-                    f'{path} is missing: the uncertainty mask has no CPU fallback. '
-                    'Build it first: python -c "import __graft_entry__ as g; g.build()" (or `make unc`)')
-            dll = C.CDLL(path)
-            have = -1
-            if hasattr(dll, 'punc_version'):
-                dll.punc_version.restype = i32
-                have = dll.punc_version()
-            if have < MIN_UNC_VERSION:
-                raise HipLibraryError(f'{path} reports punc_version() = {have}; this host side needs >= {MIN_UNC_VERSION} '
-                                      '(an older build of the library: rebuild with `make unc`)')
-            missing = [name for name in _PROTOS if not hasattr(dll, name)]
-            if missing:
-                raise HipLibraryError(f'{path} (punc_version {have}) lacks {len(missing)} entry point(s) this host side binds, e.g. '
-                                      f'{", ".join(missing[:4])}: header / library mismatch, rebuild with `make unc`')
-            for name, (res, args) in _PROTOS.items():
-                fn = getattr(dll, name)
-                fn.restype, fn.argtypes = res, args
-            self._dll = dll
-        return self._dll
-
-    def __getattr__(self, name):
-        if name.startswith('_'):
-            raise AttributeError(name)
-        fn = getattr(self.load(), name)
-        if name in _NO_STATUS:
-            return fn
-
-        def checked(*a):
-            rc = fn(*a)
-            if rc != 0:
-                msg = self.load().punc_last_error()
-                raise HipLibraryError(f'{name} failed (rc={rc}): {msg.decode() if msg else "?"}')
-        checked.__name__ = name
-        setattr(self, name, checked)             # cache the wrapper
-        return checked
+    def _spec(self):
+        return self._path or UNC_LIB_PATH, _PROTOS, MIN_UNC_VERSION
 
 
 unc = _UncLib()

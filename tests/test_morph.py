@@ -232,11 +232,8 @@ def test_header_binding_and_library_agree():
 
 
 def test_build_targets_are_wired():
-    mk = open(os.path.join(ROOT, 'Makefile')).read()
-    assert re.search(r'^all:.*\bmorph\b', mk, flags=re.M) and 'asan-morph:' in mk and re.search(r'^morph: ', mk, flags=re.M)
-    assert re.search(r'^\.PHONY:.*\bmorph\b.*\basan-morph\b', mk, flags=re.M)
-    entry = open(os.path.join(ROOT, '__graft_entry__.py')).read()
-    assert '_morph.morph.load()' in entry and '_morph.EXPORTED_SYMBOLS' in entry
+    from tests._wiring import wired
+    wired('morph', 'pacingpseudo_amd/csrc/morph/pp_morph.hip')
 
 
 def test_library_loads_without_a_gpu_and_refuses_bad_arguments():

@@ -255,10 +255,8 @@ def test_header_binding_and_library_agree():
 
 
 def test_build_targets_are_wired():
-    mk = open(os.path.join(ROOT, 'Makefile')).read()
-    assert re.search(r'^all:.*\bvol\b', mk, flags=re.M) and 'asan-vol:' in mk and re.search(r'^vol: ', mk, flags=re.M)
-    entry = open(os.path.join(ROOT, '__graft_entry__.py')).read()
-    assert '_vol.vol.load()' in entry and '_vol.EXPORTED_SYMBOLS' in entry
+    from tests._wiring import wired
+    wired('vol', 'pacingpseudo_amd/csrc/vol/pp_volume.hip')
 
 
 def test_library_loads_without_a_gpu_and_refuses_bad_arguments():

@@ -25,7 +25,8 @@ engine allocates for it) and starts as 0xFF, so a query that is too small, a ker
 that relies on what an earlier layer left in the workspace all show.  The run's entry-point table (_Checked) holds every device
 pointer of a launch to this: one that points into no banded buffer of the run is a failing result line.
 The operands have one magnitude per kind (Profile: the default, CENSUS); tests/test_gpu_operand_range.py runs the same adapters at
-others.
+others.  The pre-normalisation operand likewise (NormProfile: the default, NORM_CENSUS, leaves every draw as it is);
+tests/test_gpu_norm_range.py moves its mean-to-spread ratio and scale (docs/norm_range.md).
 A recorded launch without a replay adapter fails the census by name.  Outside the census: the stand-alone AuxPath.forward (it calls
 the library directly, not through a plan) and --precision fp16 (fp16-grade by design, tested on its own).
 """
@@ -101,6 +102,32 @@ def operands(profile):
         _PROFILE[0] = prev
 
 
+class NormProfile(NamedTuple):
+    """Where the pre-normalisation operand z of a replay lies.  The default is the point the censuses run at (|mean| <= 4 sigma);
+    tests/test_gpu_norm_range.py moves it (`with norm_operands(profile):` around a replay, docs/norm_range.md)."""
+    offset: Optional[float] = None  # r: the channel mean is +-r * sigma_c, sign alternating by channel; None: mu in [-2, 2] as drawn.
+    #                                 Fused epilogues (mode 1 / 2): the conv bias is +-r * (float64 deviation of the bias-free output)
+    scale: int = 0                  # z times 2^scale
+
+
+NORM_CENSUS = NormProfile()
+_NORM_PROFILE = [NORM_CENSUS]
+
+
+@contextlib.contextmanager
+def norm_operands(profile):
+    prev, _NORM_PROFILE[0] = _NORM_PROFILE[0], profile
+    try:
+        yield
+    finally:
+        _NORM_PROFILE[0] = prev
+
+
+def _signs(C, device=None):
+    """+1, -1, +1, ... per channel"""
+    return 1.0 - 2.0 * (torch.arange(C, device=device) % 2).float()
+
+
 class _Ops:
     """Seeded operands of one replay; activation-type tensors are rounded to the key's storage type (identical for the 16-bit
     entry and its fp32 twin).  Their magnitudes are the current Profile's."""
@@ -109,6 +136,7 @@ class _Ops:
         self.storage = key[0]
         self.g = torch.Generator().manual_seed(zlib.crc32(repr(key[1:]).encode()))
         self.prof = _PROFILE[0]
+        self.nprof = _NORM_PROFILE[0]
         self.gs = (G_FP32 if self.storage == 'fp32' else G_16) if self.prof.grad is None else self.prof.grad
 
     def _chan(self, O_):
@@ -419,6 +447,15 @@ def _bn_fwd(key, run):
     sc = _b((torch.rand(N, generator=ops.g) + 0.5))
     sh = _b(ops.randn(N))
     lib = _L()
+    off = ops.nprof.offset
+    if off is not None:
+        # the bias puts channel c of z = conv + bias at +-off deviations of its bias-free output from zero; the eval epilogue
+        # then normalises with that running mean: shift = beta - bias * scale, and y = z * scale + shift cancels
+        with _cudnn_off():
+            free = F.conv2d(x64 if x64 is not None else _n64(x if ymat is None else ymat, C), w.double(), None, 1, dil, dil)
+        b = _b((free.std((0, 2, 3), unbiased=False) * off * _signs(N, _dev())).float())
+        if mode == 2:
+            sh = _b((sh.double() - b.double() * sc.double()).float())
     if wino:
         tile = lib.pp_conv3x3_wino_tile(H, W, dil)
         U, _ = _pack_wino(w, N, C, tile, f16, run.K)
@@ -470,6 +507,24 @@ def _bn_fwd(key, run):
         run.stats_mag = {'stats sum': zc.abs().sum(1), 'stats sum of squares': 2 * zc.pow(2).sum(1)}
         run.res.append(('stats sum', part[:, :, 0].sum(1), zc.sum(1), TOL_SUMS, False))
         run.res.append(('stats sum of squares', part[:, :, 1].sum(1), zc.pow(2).sum(1), TOL_SUMS, False))
+        if off is not None:
+            # the sums alone do not show the cancellation of var = q / n - mean^2: the partial rows go through pp_bn_train_finalize
+            # as in a step, and its rows are held to the float64 statistics of the z this launch produced
+            n, eps, mom = zc.shape[1], 1e-5, 0.1
+            rows_d, rm, rv, nbt = _b(stats), _zeros(N), _full((N,), 1.0), _full((), 0, dtype=torch.int64)
+            coef = _full((4, groups, N), 7.0)
+            lib.pp_bn_train_finalize(rows_d.data_ptr(), r, N, n, groups, eps, mom, sc.data_ptr(), sh.data_ptr(), rm.data_ptr(),
+                                     rv.data_ptr(), nbt.data_ptr(), *(coef[i].data_ptr() for i in range(4)), run.st)
+            mean, var = zc.mean(1), zc.var(1, unbiased=False)
+            invstd = 1.0 / torch.sqrt(var + eps)
+            scale64 = sc.double() * invstd
+            rv64 = torch.ones(N, dtype=torch.float64, device=_dev())
+            for g in range(groups):
+                rv64 = (1 - mom) * rv64 + mom * var[g] * (n / max(n - 1, 1))
+            for i, (lab, ref64) in enumerate((('save_mean', mean), ('save_invstd', invstd), ('scale', scale64),
+                                              ('shift', sh.double() - mean * scale64))):
+                run.check('finalized ' + lab, coef[i], ref64, TOL_SUMS, act=False)
+            run.check('finalized running_var', rv, rv64, TOL_SUMS, act=False)
 
 
 def _bwd_data(key, run):

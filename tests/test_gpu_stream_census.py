@@ -7,7 +7,8 @@ training, accumulate flags, rows, class counts, slopes) on seeded operands:
   * rows of length ld hold 5.0 in the columns a call must not read, outputs start as 7.0 and their padding is checked afterwards;
     outputs that accumulate start from random content and the sum is compared;
   * normalisation operands are z = sigma_c * randn + mu_c (sigma in [0.5, 2], mu in [-2, 2] per channel), gamma[0] < 0, and the last
-    channel is the constant 0.5 -- it sums exactly, so its variance must be exactly 0 and invstd = 1 / sqrt(eps);  the partial rows
+    channel is the constant 0.5 -- it sums exactly, so its variance must be exactly 0 and invstd = 1 / sqrt(eps) (a NormProfile of
+    the convolution census moves the means to +-r sigma and scales z: tests/test_gpu_norm_range.py);  the partial rows
     of pp_bn_train_finalize[_lazy] are the float64 sums of such a z split into the recorded number of row chunks;
   * references in float64 on the device, one module call per statistics group in order: F.batch_norm / F.group_norm + leaky_relu
     and autograd, max_pool2d, interpolate(align_corners=True); the losses against the float64 restatements of tests/test_gpu_ops.py
@@ -51,8 +52,8 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle import pacing_oracle as O  # noqa: E402
-from tests.test_gpu_conv_census import (MANT, TOL, TOL_SUMS, _b, _dev, _empty, _full, _is_conv_launch, _L, _lazy64, _Ops, _p,  # noqa: E402
-                                        _Run, _ws, _zeros, replay as _replay)
+from tests.test_gpu_conv_census import (_NORM_PROFILE, MANT, NORM_CENSUS, TOL, TOL_SUMS, _b, _dev, _empty, _full, _is_conv_launch, _L, _lazy64,  # noqa: E402
+                                        _Ops, _p, _Run, _signs, _ws, _zeros, replay as _replay)
 
 TOL_BIL = 1e-5        # test_bilinear
 TOL_LOSS = 1e-5       # loss values, bank rows, up-sampled logits (tests/test_gpu_ops.py)
@@ -66,6 +67,7 @@ class _DOps(_Ops):
     def __init__(self, key):
         super().__init__(key)
         self.g = torch.Generator(device=_dev()).manual_seed(zlib.crc32(repr(key[1:]).encode()))
+        self.mu = self.sig = None          # per-channel mean and deviation of the last norm_z under a NormProfile
 
     def randn(self, *shape, scale=1.0):
         return torch.randn(*shape, generator=self.g, device=_dev()) * scale
@@ -88,17 +90,29 @@ class _DOps(_Ops):
         multiples of it, for the forms that pick the winner of a 2 x 2 window -- two values of a window are then equal or far
         enough apart that fp32 and float64 order y = lrelu(z * scale + shift) alike (a near-tie would move a whole dpool)."""
         sig, mu = self.rand(C) * 1.5 + 0.5, self.rand(C) * 4 - 2
+        prof = self.nprof
+        if prof.offset is not None:             # NormProfile: mean-to-spread ratio r, sign alternating by channel
+            mu = prof.offset * sig * _signs(C, _dev())
         z = self.randn(N, H, W, C) * sig + mu
         if grid:
             z = torch.round(z / grid) * grid
         z[..., C - 1] = 0.5
+        if prof.scale:
+            z = z * 2.0 ** prof.scale           # exact; the constant channel stays one whose sums are exact
+        if prof != NORM_CENSUS:
+            mu = mu.clone()
+            mu[C - 1] = 0.5
+            self.mu, self.sig = mu * 2.0 ** prof.scale, sig * 2.0 ** prof.scale
         return self.r(z)
 
     def affine(self, C):
-        """gamma (gamma[0] < 0), beta, running mean, running variance"""
+        """gamma (gamma[0] < 0), beta, running mean, running variance (under a NormProfile: of the z drawn before it)"""
         gamma = self.rand(C) + 0.5
         gamma[0] = -0.7
-        return gamma, self.randn(C), self.randn(C) * 0.1, self.rand(C) + 0.5
+        beta, rm, rv = self.randn(C), self.randn(C) * 0.1, self.rand(C) + 0.5
+        if self.mu is not None:
+            rm, rv = self.mu + rm * self.sig, rv * self.sig * self.sig
+        return gamma, beta, rm, rv
 
 
 def _out(run, shape, ld, C, prior=None, fill=7.0):
@@ -217,12 +231,22 @@ def _check_stats(run, z64, gamma, beta, rm, rv, eps, mom, coef, rmd, rvd, nbt):
         run.check(lab, coef[i], ref[i], TOL_SUMS, act=False)
     run.check('running_mean', rmd, rm64, TOL_SUMS, act=False)
     run.check('running_var', rvd, rv64, TOL_SUMS, act=False)
+    _varying_rows(run, ('save_invstd', 'scale', 'shift'), coef[1:], ref[1:], C)
     _flag(run, 'num_batches_tracked', int(nbt) == 3 + groups)
     # the constant channel: its sums are exact, the variance must be exactly 0
     want = 1.0 / math.sqrt(torch.tensor(eps).float().item())
-    _flag(run, 'constant channel: mean 0.5, variance exactly 0', bool((coef[0, :, C - 1] == 0.5).all())
+    const = float(z64[0, 0, C - 1])                    # 0.5, times a power of two under a NormProfile
+    _flag(run, 'constant channel: mean 0.5, variance exactly 0', bool((coef[0, :, C - 1] == const).all())
           and float((coef[1, :, C - 1].double() - want).abs().max()) <= 5e-7 * want)          # fp32 rounding of 1 / sqrt(eps)
     return ref
+
+
+def _varying_rows(run, labels, got, ref, C):
+    """Under a NormProfile the rows once more without the constant channel: its invstd = 1 / sqrt(eps) ~ 316 is the maximum the
+    whole row is relative to, which would hide the cancellation error of the varying channels a hundred times over."""
+    if _NORM_PROFILE[0] != NORM_CENSUS and C > 1:
+        for i, lab in enumerate(labels):
+            run.check(lab + ' of the varying channels', got[i][..., :C - 1], ref[i][..., :C - 1], TOL_SUMS, act=False)
 
 
 def _bn_finalize(key, run):
@@ -317,6 +341,9 @@ def _bn_fwd(key, run):
     scale = ops.rand(groups, C) + 0.5
     scale[:, 0] = -0.7
     shift = ops.randn(groups, C)
+    if ops.mu is not None:          # NormProfile: rows of a normalisation, shift = beta - mean * scale, so z * scale + shift cancels
+        scale = scale / ops.sig
+        shift = shift - ops.mu * scale
     sd, hd = _f32(run, scale), _f32(run, shift)
     y = _out(run, (N, H, W), ld_y, C)
     if pool:
@@ -510,6 +537,7 @@ def _gn_stats(key, run):
     ref = _gn_rows64(z.double().reshape(N, HW, C), G, gamma, beta, eps)
     for i, lab in enumerate(('save_mean', 'save_invstd', 'save_xbar', 'scale', 'shift')):
         run.check(lab, rows[i], ref[i], TOL_SUMS, act=False)
+    _varying_rows(run, ('save_invstd', 'scale', 'shift'), (rows[1], rows[3], rows[4]), (ref[1], ref[3], ref[4]), C)
 
 
 def _gn_bwd(key, run):
